@@ -2,6 +2,8 @@
 """Headline benchmark: all_reduce busbw + p50 latency, 1 GiB fp32 (BASELINE.json).
 
     python bench.py [--gpus N] [--steps K] [--warmup W]            # starts N ranks itself
+    python bench.py --gpus N --full                                # + p50, checks and every extra
+    python bench.py --gpus N --dump-outputs DIR                    # + the last timed step's result
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N \\
         --master-addr 127.0.0.1 --master-port P bench.py --gpus N  # or under torchrun
 
@@ -16,12 +18,27 @@ One rank per GPU, backend ``mi355x`` (this library). A "step" is one in-place
 elements per rank). W untimed warm-up steps, then exactly K steps bracketed by
 ``barrier + torch.cuda.synchronize()`` on both sides; the time is the MAX over
 ranks. busbw uses the nccl-tests convention ``S * 2(n-1)/n / t`` (0 at n=1,
-where all_reduce is a no-op). p50 = median over K individually-bracketed steps
-of the max-over-ranks time (BASELINE.md method). Rank 0 prints ONE JSON line.
+where all_reduce is a no-op: there the line's value is algbw, ``S / t``, so that
+it still follows the cost of the call). Rank 0 prints ONE JSON line.
 
-Extra fields (not part of the headline): K1 kernel bandwidth on this GPU, and
-for N>1 an A/B of the algorithms (RCCL vs the IPC peer-memory kernels) at the
-headline size and at small sizes, each with a correctness check.
+A plain run does only that: set up, warm up, time the K steps, print the line
+(``ms_per_step`` = the timed region / K). ``--dump-outputs DIR`` also writes what
+the last timed step left in each rank's tensor -- the inputs are seeded, so two
+builds can be compared output for output -- as ``DIR/all_reduce_rank<r>.npy``
+(float32; a fixed seeded sample of the elements when the tensor is larger than
+the file budget).
+
+``--full`` adds everything else: the RCCL environment pre-sweep before the GPU
+is touched, p50 = median over K individually-bracketed steps of the
+max-over-ranks time (BASELINE.md method), the correctness and finiteness checks
+of the headline path, the conformance pass and the extra fields (K1 kernel
+bandwidth on this GPU, and for N>1 an A/B of the algorithms (RCCL vs the IPC
+peer-memory kernels) at the headline size and at small sizes, torch's own
+ProcessGroupNCCL on the same rows, ..., each with a correctness check). Without
+``--full`` those fields of the line are null. A plain run on several GPUs still
+applies an RCCL environment verdict that an earlier pre-sweep persisted for this
+topology (``PDCC_RCCL_ENV_FILE``; ``0`` turns that off), so its figure depends on
+that earlier state.
 """
 from __future__ import annotations
 
@@ -80,7 +97,13 @@ def parse_args(argv=None):
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--bytes", type=int, default=NBYTES)
-    ap.add_argument("--extras", type=int, default=int(os.environ.get("PDCC_BENCH_EXTRAS", "1")))
+    ap.add_argument("--extras", type=int, default=int(os.environ.get("PDCC_BENCH_EXTRAS", "1")),
+                    help="with --full: 0 leaves the conformance pass and the extra sections out")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the RCCL environment pre-sweep, the p50 steps, the correctness checks, the "
+                         "conformance pass and the extras (a plain run only times the steps)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write each rank's result of the last step to DIR/*.npy")
     return ap.parse_args(argv)
 
 
@@ -252,33 +275,41 @@ def run_rank(args):
         csync()
         total = max_over_ranks(time.perf_counter() - t0)
     zc_timed = zc_delta(zc0, zc_counters(native), max_over_ranks)
-    finite = bool(torch.isfinite(x).all().item())
-    ms_per_step = total / args.steps * 1e3
+    ms_per_step = total / max(1, args.steps) * 1e3
+    if args.dump_outputs:
+        with section("dump_outputs"):
+            dump_outputs(args.dump_outputs, rank, world, x)
 
-    # ---- p50 of individually bracketed steps (BASELINE.md method)
-    with section("p50_steps"):
-        lat = []
-        for _ in range(args.steps):
+    p50 = finite = correct = None  # measured and checked with --full only
+    if args.full:
+        finite = bool(torch.isfinite(x).all().item())
+        # ---- p50 of individually bracketed steps (BASELINE.md method)
+        with section("p50_steps"):
+            lat = []
+            for _ in range(args.steps):
+                x.copy_(x0)
+                sync()
+                s0 = time.perf_counter()
+                dist.all_reduce(x)
+                csync()
+                lat.append(max_over_ranks(time.perf_counter() - s0))
+            p50 = statistics.median(lat)
+            finite = finite and bool(torch.isfinite(x).all().item())
             x.copy_(x0)
-            sync()
-            s0 = time.perf_counter()
-            dist.all_reduce(x)
-            csync()
-            lat.append(max_over_ranks(time.perf_counter() - s0))
-        p50 = statistics.median(lat)
-        finite = finite and bool(torch.isfinite(x).all().item())
-        x.copy_(x0)
-        del x0
 
-    # ---- correctness of the headline path
-    with section("correctness"):
-        y = torch.full((numel,), float(rank + 1), device=dev)
-        dist.all_reduce(y)
-        exp = world * (world + 1) / 2
-        correct = bool(torch.all(y == exp).item())
-        del y
+        # ---- correctness of the headline path
+        with section("correctness"):
+            y = torch.full((numel,), float(rank + 1), device=dev)
+            dist.all_reduce(y)
+            exp = world * (world + 1) / 2
+            correct = bool(torch.all(y == exp).item())
+            del y
+    del x0
 
-    value = busbw(args.bytes, world, ms_per_step / 1e3)
+    # the headline figure: busbw; at world 1 its factor 2(n-1)/n is 0 whatever the call costs, so the
+    # figure there is algbw (bytes over the time of one call), which still moves with the timed path
+    value = busbw(args.bytes, world, ms_per_step / 1e3) if world > 1 else (
+        args.bytes / (ms_per_step / 1e3) / 1e9 if ms_per_step > 0 else 0.0)
     try:  # the autotuner's decisions for the headline path (size bucket -> engine, times)
         EXTRAS_PARTIAL["autotune"] = native.autotune_table()
     except Exception:
@@ -292,11 +323,11 @@ def run_rank(args):
             "n_gpus": world,
             "steps": args.steps,
             "warmup": args.warmup,
-            "ms_per_step": round(ms_per_step, 4),
-            "p50_ms": round(p50 * 1e3, 4),
+            "ms_per_step": round(ms_per_step, 6),
+            "p50_ms": round(p50 * 1e3, 4) if p50 is not None else None,
             "baseline_p50_ms": BASELINE_P50_MS.get(world),
-            "busbw_p50_GBps": round(busbw(args.bytes, world, p50), 3),
-            "algbw_GBps": round(args.bytes / (ms_per_step / 1e3) / 1e9, 3) if world > 1 else None,
+            "busbw_p50_GBps": round(busbw(args.bytes, world, p50), 3) if p50 is not None else None,
+            "algbw_GBps": round(args.bytes / (ms_per_step / 1e3) / 1e9, 3) if ms_per_step > 0 else None,
             "higher_is_better": True,
             "scaling": "weak",
             "vs_baseline": round(value / BASELINE_BUSBW[world], 2) if world in BASELINE_BUSBW else None,
@@ -318,7 +349,7 @@ def run_rank(args):
             "data_finite": finite,
             # torch's own ProcessGroupNCCL on the same 1 GiB all_reduce (extras.torch_nccl): its p50 / ours
             "vs_torch_nccl": _vs_torch_nccl_headline(extras, p50, args.bytes),
-            "note": ("world=1: all_reduce is a no-op, busbw is 0 by the nccl-tests definition"
+            "note": ("world=1: all_reduce is a no-op and busbw is 0 by the nccl-tests definition; value is algbw"
                      + ("; RCCL rehearsal (1-rank communicators, PDCC_WORLD1_LOCAL=0)" if REHEARSAL else ""))
                     if world == 1 else "",
             "extras": extras,
@@ -337,8 +368,8 @@ def run_rank(args):
         sys.stderr.flush()
         os._exit(0)
 
-    extras = {}
-    if args.extras:
+    extras = {} if args.full else dict(EXTRAS_PARTIAL)
+    if args.full and args.extras:
         timer = threading.Timer(float(os.environ.get("PDCC_BENCH_EXTRAS_S", "240")), deadline, args=("extras",))
         timer.daemon = True
         timer.start()
@@ -372,10 +403,28 @@ def run_rank(args):
     dist.destroy_process_group()
 
 
+def dump_outputs(dirpath, rank, world, x):
+    """What the timed path left in this rank's tensor after its last step, as float32
+    ``all_reduce_rank<r>.npy``: the whole tensor if the ranks' files fit 16 MiB together,
+    otherwise the elements at a fixed, seeded set of positions (the same on every rank and
+    in every run, so two builds' files compare element for element)."""
+    import numpy as np
+    import torch
+
+    os.makedirs(dirpath, exist_ok=True)
+    keep = (16 << 20) // 4 // world
+    if x.numel() > keep:
+        idx = torch.randint(x.numel(), (keep,), generator=torch.Generator().manual_seed(20240611))
+        x = x[idx.to(x.device)]
+    np.save(os.path.join(dirpath, f"all_reduce_rank{rank}.npy"), x.detach().to("cpu", torch.float32).numpy())
+
+
 def rccl_env_presweep(store, rank, world, local, on_gpu, ngpu, args):
     """RCCL reads NCCL_BUFFSIZE / NCCL_PROTO once per process: measure them in fresh child
     ranks before this rank touches the GPU (utils/rccl_env.py), and apply the winner to this
     rank's own communicators (every rank applies the same one). Distinct GPUs only."""
+    if not args.full:
+        return {"skipped": "plain run: the sweep runs with --full"}
     if not on_gpu:
         return {"skipped": "CPU rehearsal (PDCC_BENCH_DEVICE=cpu)"}
     if world < 2 and not REHEARSAL:

@@ -21,19 +21,19 @@ for s in "$@"; do
     gputests) step gputests 1200 python -u -m pytest tests -m gpu -v --timeout 300 --timeout-method thread ;;
     graphbench) step graphbench 300 python scripts/graph_bench.py ;;
     graphbench1) GRAPH_BENCH_MODE=rccl1 step graphbench1 300 python scripts/graph_bench.py ;;
-    bench1) step bench1 600 python bench.py --gpus 1 --steps 20 --warmup 5 ;;
+    bench1) step bench1 600 python bench.py --gpus 1 --full --steps 20 --warmup 5 ;;
     bench2dbg) PDCC_BENCH_SMALL=1 PDCC_LOG_LEVEL=2 PDCC_BENCH_DEBUG_S=150 step bench2dbg 240 \
         python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 \
-        --master-port 29534 bench.py --gpus 2 --steps 3 --warmup 1 --bytes 67108864 ;;
+        --master-port 29534 bench.py --gpus 2 --full --steps 3 --warmup 1 --bytes 67108864 ;;
     kprof) step kprof 600 python scripts/kernel_bench.py ;;
     benchdeadline) PDCC_BENCH_SMALL=1 PDCC_BENCH_EXTRAS_S=4 step benchdeadline 300 python -m torch.distributed.run \
-        --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29535 bench.py --gpus 2 --steps 3 \
+        --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29535 bench.py --gpus 2 --full --steps 3 \
         --warmup 1 --bytes 67108864 ;;
     profile) step profile 1500 bash scripts/profile.sh ;;
     pmc) PDCC_PMC_ONLY=1 step pmc 600 bash scripts/profile.sh ;;
     trace) PDCC_TRACE_ONLY=1 step trace 900 bash scripts/profile.sh ;;
     k2sweep) step k2sweep 300 python scripts/k2_sweep.py ;;
-    bench2self) PDCC_BENCH_SMALL=1 step bench2self 600 python bench.py --gpus 2 --steps 3 --warmup 1 --bytes 67108864 ;;
+    bench2self) PDCC_BENCH_SMALL=1 step bench2self 600 python bench.py --gpus 2 --full --steps 3 --warmup 1 --bytes 67108864 ;;
     churn) step churn 300 python scripts/group_churn.py ;;
     graphprobe) step graphprobe 300 python scripts/graph_probe.py ;;
     graphrt) step graphrt 200 python scripts/graph_rt_probe.py ;;
@@ -76,7 +76,7 @@ for s in "$@"; do
     gpuA2) step gpuA2 600 python -u -m pytest tests/test_backend_gpu.py -v --timeout 300 --timeout-method thread \
         -k "world8 or list_all_to_all or conformance or ll_reduce_scatter" ;;
     bench2shared) PDCC_BENCH_SMALL=1 step bench2shared 600 python -m torch.distributed.run --nnodes=1 \
-        --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29533 bench.py --gpus 2 --steps 3 --warmup 1 \
+        --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29533 bench.py --gpus 2 --full --steps 3 --warmup 1 \
         --bytes 67108864 ;;
   esac
 done

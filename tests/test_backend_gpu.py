@@ -413,7 +413,7 @@ def test_sync_collective_after_async_is_ordered():
 
 @pytest.mark.parametrize("world", [2, 4])
 def test_conformance_pass_on_shared_gpu(world):
-    # the pass bench.py runs at N > 1 (golden table x 4 ops, random fp32/bf16 vs an fp64
+    # the pass bench.py --full runs at N > 1 (golden table x 4 ops, random fp32/bf16 vs an fp64
     # reference, all eight LL kinds, zero-copy pull/push, async ordering, shared communicator)
     res = _gpu_launch(W.conformance_probe, world, timeout_s=120)
     for r in res:

@@ -25,7 +25,7 @@ def _run(args, extra_env=None, timeout=240):
 
 @pytest.mark.parametrize("n", [1, 4])
 def test_bench_self_launch_prints_one_line(n):
-    r = _run(["--gpus", str(n), "--bytes", "4096", "--steps", "2", "--warmup", "1"])
+    r = _run(["--gpus", str(n), "--full", "--bytes", "4096", "--steps", "2", "--warmup", "1"])
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
     assert len(lines) == 1, r.stdout
@@ -36,8 +36,9 @@ def test_bench_self_launch_prints_one_line(n):
     assert rec["higher_is_better"] is True and rec["scaling"] == "weak"
     assert rec["data_finite"] is True  # x is restored between phases (no +inf at large W)
     assert rec["config"]["algo"] == "shm"  # the engine that actually served the timed steps
+    assert rec["value"] > 0 and rec["ms_per_step"] > 0  # (world 1: algbw, busbw's factor is 0 there)
     if n > 1:
-        assert rec["value"] > 0 and rec["vs_baseline"] is not None
+        assert rec["vs_baseline"] is not None
     conf = rec["extras"]["conformance"]
     assert conf["all_ok"] is True, conf
     assert not conf["skipped"] and conf["passed"] >= 30
@@ -53,6 +54,82 @@ def test_bench_self_launch_prints_one_line(n):
     # the stock-RCCL comparator and the RCCL environment pre-sweep leave a skip record here
     assert "skipped" in rec["extras"]["torch_nccl"], rec["extras"]["torch_nccl"]
     assert "skipped" in rec["extras"]["rccl_env_sweep"], rec["extras"]["rccl_env_sweep"]
+
+
+def test_bench_plain_run_is_lean_and_dumps_outputs(tmp_path):
+    # without --full: warm-up, the timed steps and the line -- no p50 steps, checks, conformance or extras;
+    # --dump-outputs writes each rank's result of the last timed step, the same from run to run
+    import numpy as np
+    import torch
+
+    world, numel, steps = 2, 1024, 3
+    outs = []
+    for d in ("a", "b"):
+        r = _run(["--gpus", str(world), "--bytes", str(numel * 4), "--steps", str(steps), "--warmup", "1",
+                  "--dump-outputs", str(tmp_path / d)])
+        assert r.returncode == 0, r.stderr[-3000:]
+        lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
+        assert len(lines) == 1, r.stdout
+        rec = json.loads(lines[0])
+        assert rec["steps"] == steps and rec["ms_per_step"] > 0 and rec["value"] > 0
+        assert rec["unit"] == "GB/s" and rec["higher_is_better"] is True and rec["dtype"] == "fp32"
+        assert rec["p50_ms"] is None and rec["correct"] is None and rec["data_finite"] is None
+        assert "conformance" not in rec["extras"] and "skipped" in rec["extras"]["rccl_env_sweep"]
+        assert "p50_steps" not in rec["extras"]["timing"] and "correctness" not in rec["extras"]["timing"]
+        files = sorted(os.listdir(tmp_path / d))
+        assert files == [f"all_reduce_rank{k}.npy" for k in range(world)]
+        outs.append([np.load(tmp_path / d / f) for f in files])
+    # the seeded inputs (bench.py: torch.rand * 1e-3, seed 1234 + rank), summed over the ranks, times W per
+    # further step; fp32 sums of two values, then exact doublings
+    xs = [torch.rand(numel, generator=torch.Generator().manual_seed(1234 + k)).mul_(1e-3) for k in range(world)]
+    want = ((xs[0] + xs[1]) * float(world ** (steps - 1))).numpy()
+    for a, b in zip(*outs):
+        assert a.dtype == np.float32 and a.shape == (numel,)
+        np.testing.assert_array_equal(a, b)
+        np.testing.assert_array_equal(a, want)
+
+
+def test_dump_outputs_samples_large_tensors(tmp_path):
+    # a tensor past the file budget is written as a fixed, seeded sample of its elements
+    import importlib.util
+
+    import numpy as np
+    import torch
+
+    spec = importlib.util.spec_from_file_location("bench_mod3", os.path.join(ROOT, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    x = torch.arange((4 << 20) + 3, dtype=torch.float32)  # (every index exact in fp32)
+    bench.dump_outputs(str(tmp_path), 1, 4, x)
+    a = np.load(tmp_path / "all_reduce_rank1.npy")
+    assert a.dtype == np.float32 and a.shape == (1 << 20,)
+    bench.dump_outputs(str(tmp_path), 2, 4, x * 2)
+    np.testing.assert_array_equal(np.load(tmp_path / "all_reduce_rank2.npy"), a * 2)  # same positions
+    assert a.min() >= 0 and a.max() < x.numel() and len(np.unique(a)) > (1 << 19)
+
+
+@pytest.mark.gpu
+def test_bench_plain_run_dumps_outputs_on_the_gpu(tmp_path):
+    # the plain run on the device, one size past the dump's file budget (20 MiB + 12 B > 16 MiB): the device
+    # generator's inputs and the sample gathered on the device. At world 1 all_reduce leaves the data as it is,
+    # so the dump is the seeded input at the seeded positions, bit for bit.
+    import numpy as np
+    import torch
+
+    numel = (5 << 20) + 3
+    r = _run(["--gpus", "1", "--bytes", str(numel * 4), "--steps", "3", "--warmup", "1",
+              "--dump-outputs", str(tmp_path)], {"PDCC_BENCH_DEVICE": "cuda"}, timeout=120)
+    assert r.returncode == 0, r.stderr[-3000:]
+    rec = json.loads([ln for ln in r.stdout.splitlines() if ln.strip()][-1])
+    assert rec["config"]["device"] == "cuda" and rec["steps"] == 3 and rec["ms_per_step"] > 0
+    assert rec["p50_ms"] is None and "conformance" not in rec["extras"]
+    assert os.listdir(tmp_path) == ["all_reduce_rank0.npy"]
+    got = np.load(tmp_path / "all_reduce_rank0.npy")
+    assert got.dtype == np.float32 and got.shape == (1 << 22,)
+    dev = torch.device("cuda", 0)
+    x = torch.rand(numel, device=dev, generator=torch.Generator(device=dev).manual_seed(1234)).mul_(1e-3)
+    idx = torch.randint(numel, (1 << 22,), generator=torch.Generator().manual_seed(20240611))  # bench.dump_outputs
+    np.testing.assert_array_equal(got, x[idx.to(dev)].cpu().numpy())
 
 
 def test_bench_failing_rank_propagates():
@@ -111,7 +188,7 @@ def test_bench_rccl_rehearsal_on_one_gpu():
     # GPU (1-rank communicators) before the driver's multi-GPU node runs them for the first time
     env = {"PDCC_BENCH_DEVICE": "cuda", "PDCC_BENCH_RCCL_REHEARSAL": "1", "PDCC_BENCH_SMALL": "1",
            "PDCC_BENCH_TIMEOUT_S": "380", "PDCC_BENCH_EXTRAS_S": "300", "PDCC_BENCH_RCCL_ENV_SWEEP_S": "150"}
-    r = _run(["--gpus", "1", "--bytes", str(64 << 20), "--steps", "3", "--warmup", "1"], env, timeout=400)
+    r = _run(["--gpus", "1", "--full", "--bytes", str(64 << 20), "--steps", "3", "--warmup", "1"], env, timeout=400)
     assert r.returncode == 0, r.stderr[-3000:]
     rec = json.loads([ln for ln in r.stdout.splitlines() if ln.strip()][-1])
     ex = rec["extras"]

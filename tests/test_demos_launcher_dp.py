@@ -1,4 +1,4 @@
-"""The tutorial workloads, the launcher (reference main.py unmodified) and
+"""The tutorial workloads, the launcher (a self-spawning script in the tutorial's style) and
 data-parallel training on the mi355x backend (CPU, multi-process)."""
 import os
 import subprocess
@@ -12,7 +12,6 @@ from pytorch_distributed_collective_communication_amd.parallel.spawn import laun
 from tests import _workers as W
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-REF_MAIN = "/root/reference/main.py"
 
 
 @pytest.mark.parametrize("name", sorted(DEMOS))
@@ -21,15 +20,40 @@ def test_demo_golden_world4(name):
     assert res == [golden(name, r, 4) for r in range(4)]
 
 
-@pytest.mark.skipif(not os.path.exists(REF_MAIN), reason="reference main.py not mounted on this machine")
-def test_reference_main_py_runs_unmodified():
-    """main.py requests backend 'gloo' (main.py:90); the launcher serves it with mi355x."""
+def test_launcher_serves_self_spawning_script(tmp_path):
+    """The launcher's takeover mode, with a script of this test's own in the style of the tutorial's: it
+    starts its 4 ranks itself with torch.multiprocessing, each asks for backend 'gloo' and makes a group of
+    all ranks, rank 0 scatters 1..4 and all ranks all_reduce; mi355x (not Gloo) must have served them."""
+    script = tmp_path / "selfspawn.py"
+    script.write_text(
+        "import os, sys, torch, torch.distributed as dist, torch.multiprocessing as mp\n"
+        "def work(rank, world, port):\n"
+        "    os.environ['MASTER_ADDR'] = '127.0.0.1'\n"
+        "    os.environ['MASTER_PORT'] = port\n"
+        "    dist.init_process_group('gloo', rank=rank, world_size=world)\n"
+        "    g = dist.new_group(list(range(world)))\n"
+        "    got = torch.empty(1)\n"
+        "    parts = [torch.tensor([float(i + 1)]) for i in range(world)] if rank == 0 else []\n"
+        "    dist.scatter(got, scatter_list=parts, src=0, group=g)\n"
+        "    t = got.clone()\n"
+        "    dist.all_reduce(t, op=dist.ReduceOp.SUM, group=g)\n"
+        "    b = g._get_backend(torch.device('cpu'))\n"
+        "    print('RESULT', rank, got.item(), t.item(), type(b).__name__, flush=True)\n"
+        "    dist.destroy_process_group()\n"
+        "if __name__ == '__main__':\n"
+        "    mp.set_start_method('spawn')\n"
+        "    ps = [mp.Process(target=work, args=(r, 4, sys.argv[1])) for r in range(4)]\n"
+        "    [p.start() for p in ps]\n"
+        "    [p.join() for p in ps]\n"
+        "    sys.exit(max(abs(p.exitcode) for p in ps))\n")
+    from pytorch_distributed_collective_communication_amd.parallel.spawn import free_port
+
     env = dict(os.environ, PDCC_LOG_LEVEL="1")
-    r = subprocess.run([sys.executable, "-m", "pytorch_distributed_collective_communication_amd.run", REF_MAIN],
-                       cwd=ROOT, env=env, capture_output=True, text=True, timeout=180)
+    r = subprocess.run([sys.executable, "-m", "pytorch_distributed_collective_communication_amd.run", str(script),
+                        str(free_port())], cwd=ROOT, env=env, capture_output=True, text=True, timeout=180)
     assert r.returncode == 0, r.stderr[-2000:]
-    lines = sorted(l for l in r.stdout.splitlines() if l.startswith("["))
-    assert lines == [f"[{i}] data = {i + 1}.0" for i in range(4)]  # do_scatter (main.py:103)
+    res = sorted(l for l in r.stdout.splitlines() if l.startswith("RESULT"))
+    assert res == [f"RESULT {i} {i + 1}.0 10.0 ProcessGroupMI355X" for i in range(4)]
     assert "[pdcc] group" in r.stderr  # proof the mi355x backend (not Gloo) served it
 
 

@@ -13,8 +13,8 @@ sanitizers go where host-side pointer arithmetic and threads live:
   same way (``_build.py --sanitize``; the gfx950 kernels are shared), loaded into
   every Python rank (``PDCC_NATIVE_SO``, ASan runtime and libstdc++ preloaded)
   while the CPU multi-process suites run: every collective x op x world, p2p,
-  peer death, coalescing, the demos, the launcher, DDP / ZeRO and the
-  reference's main.py unmodified (verdict r5 Next #5).
+  peer death, coalescing, the demos, the launcher (a self-spawning script
+  included) and DDP / ZeRO (verdict r5 Next #5).
 
 Any ASan/UBSan report fails the test.
 """
