@@ -22,7 +22,7 @@ using namespace gpu;
 // a call whose IPC engine is an LL kernel (whatever engine the autotuner then picks, every one of them
 // takes buffers at any alignment: LL, RCCL, the host path)
 bool ProcessGroupMI355X::ll_call(const DeviceState& ds, size_t bytes) const {
-  return ds.ipc_ok && ds.ll_ok && bytes_in_ll_range(bytes);
+  return ds.ipc_ok && ll_size(ds, bytes);
 }
 
 bool ProcessGroupMI355X::bytes_in_ll_range(size_t bytes) const {
@@ -261,8 +261,6 @@ bool ProcessGroupMI355X::sdma_run(
   }
   ic.launch(bar, s);  // departure
   ic.zc_note_launch(ic.new_launch_event(s));  // (the mappings stay open until the pulls are done)
-  std::lock_guard<std::mutex> lk(stats_mu_);
-  sdma_ran_ = true;
   return true;
 }
 
@@ -412,7 +410,6 @@ c10::intrusive_ptr<c10d::Work> ProcessGroupMI355X::gpu_issue(Coll c, DeviceState
   {  // (zero-copy attempts of the autotuner's scratch runs do not label this call)
     std::lock_guard<std::mutex> lk(stats_mu_);
     zc_parts_.clear();
-    sdma_ran_ = false;
   }
   auto w = gpu_run(c, ds, keep_alive, std::move(outputs), timeout, [&](hipStream_t s) {
     hp_.lap(HostStage::PRE);
@@ -424,26 +421,33 @@ c10::intrusive_ptr<c10d::Work> ProcessGroupMI355X::gpu_issue(Coll c, DeviceState
 }
 
 // =================================================================== engines
-void ProcessGroupMI355X::enqueue_allreduce(Algo a, const at::Tensor& w, kern::DType kd, kern::RedOp ko,
-                                           ncclDataType_t nd, ncclRedOp_t no, bool nok, RedOpType op, int root,
-                                           bool rooted, DeviceState& ds, hipStream_t s, std::chrono::milliseconds to) {
+const char* ProcessGroupMI355X::enqueue_allreduce(Algo a, const at::Tensor& w, const RedSpec& red, int root,
+                                                  bool rooted, DeviceState& ds, hipStream_t s,
+                                                  std::chrono::milliseconds to) {
   const StagedOnly staged_only(staged_only_, a == Algo::IPC_STAGED);  // (read by ipc_run)
   if (is_ipc(a)) {
     IpcComm& ic = ipc(ds);
     kern::IpcCall c{};
     const bool one_shot = w.nbytes() <= cfg_.ipc_1shot_max;
+    const char* label = one_shot ? "ipc_1shot" : a == Algo::IPC_WIDE ? "ipc_2shot_wide" : "ipc_2shot";
     c.coll = rooted ? (one_shot ? kern::IpcColl::REDUCE_1SHOT : kern::IpcColl::REDUCE_2SHOT)
                     : (one_shot ? kern::IpcColl::ALLREDUCE_1SHOT : kern::IpcColl::ALLREDUCE_2SHOT);
-    if (a == Algo::IPC_PUSH && c.coll == kern::IpcColl::ALLREDUCE_2SHOT) c.coll = kern::IpcColl::ALLREDUCE_PUSH;
     if (a == Algo::IPC_WIDE) c.grid_cap = cfg_.ipc_wide_grid;  // (shared devices: capped in launch_view)
-    if (a == Algo::IPC_DYN && c.coll == kern::IpcColl::ALLREDUCE_2SHOT)  // (zero-copy runs only)
+    if (a == Algo::IPC_PUSH && c.coll == kern::IpcColl::ALLREDUCE_2SHOT) {
+      c.coll = kern::IpcColl::ALLREDUCE_PUSH;
+      label = "ipc_push";
+    }
+    if (a == Algo::IPC_DYN && c.coll == kern::IpcColl::ALLREDUCE_2SHOT) {  // (zero-copy runs only)
       c.dyn = std::max(1, cfg_.ipc_dyn);  // chunks per workgroup
+      label = "ipc_2shot_dyn";
+    }
     c.dyn_min_rows = cfg_.ipc_dyn_min_rows;
-    // small (all-)reduce: flag-tagged pushes, no staging copy, no barrier
-    if (ds.ll_ok && bytes_in_ll_range(w.nbytes()))
+    if (ll_size(ds, w.nbytes())) {  // small (all-)reduce: flag-tagged pushes, no staging copy, no barrier
       c.coll = rooted ? kern::IpcColl::REDUCE_LL : kern::IpcColl::ALLREDUCE_LL;
-    c.dtype = kd;
-    c.op = ko;
+      label = "ipc_ll";
+    }
+    c.dtype = red.kd;
+    c.op = red.ko;
     c.root = root;
     c.avg_div = size_;
     c.bytes = w.nbytes();
@@ -456,23 +460,28 @@ void ProcessGroupMI355X::enqueue_allreduce(Algo a, const at::Tensor& w, kern::DT
       ipc_run(ds, c, w.data_ptr(), w.nbytes(), (size_t)size_ * kern::kTileBytes, ic.chunk_cap(), s);
     else
       ipc_chunked(ic, c, ic.chunk_cap(), s);
+    return label;
   } else if (is_rccl(a)) {
-    TORCH_CHECK(nok, "pdcc: RCCL has no reduction for ", op_name(op), " on ", w.scalar_type());
+    TORCH_CHECK(red.nok, "pdcc: RCCL has no reduction for ", op_name(red.op), " on ", w.scalar_type());
     RcclComm& rc = a == Algo::RCCL_WIDE ? rccl_wide(ds) : rccl(ds);
     RcclComm::Issue og(rc, s, capturing(s));
-    if (rooted) PDCC_NCCLC(rc.get(), ncclReduce(w.data_ptr(), w.data_ptr(), w.numel(), nd, no, root, rc.get(), s));
-    else PDCC_NCCLC(rc.get(), ncclAllReduce(w.data_ptr(), w.data_ptr(), w.numel(), nd, no, rc.get(), s));
+    if (rooted)
+      PDCC_NCCLC(rc.get(), ncclReduce(w.data_ptr(), w.data_ptr(), w.numel(), red.nd, red.no, root, rc.get(), s));
+    else
+      PDCC_NCCLC(rc.get(), ncclAllReduce(w.data_ptr(), w.data_ptr(), w.numel(), red.nd, red.no, rc.get(), s));
+    return a == Algo::RCCL_WIDE ? "rccl_wide" : "rccl";
   } else {  // HOST, synchronous
     PDCC_HIP(hipStreamSynchronize(s));
     at::Tensor h = w.cpu();
-    if (rooted) shm().reduce(h.data_ptr(), h.numel(), h.scalar_type(), op, root, to);
-    else shm().allreduce(h.data_ptr(), h.numel(), h.scalar_type(), op, to);
+    if (rooted) shm().reduce(h.data_ptr(), h.numel(), h.scalar_type(), red.op, root, to);
+    else shm().allreduce(h.data_ptr(), h.numel(), h.scalar_type(), red.op, to);
     if (!rooted || rank_ == root) const_cast<at::Tensor&>(w).copy_(h);
+    return "host";
   }
 }
 
-void ProcessGroupMI355X::enqueue_broadcast(Algo a, const at::Tensor& w, int root, DeviceState& ds, hipStream_t s,
-                                           std::chrono::milliseconds to) {
+const char* ProcessGroupMI355X::enqueue_broadcast(Algo a, const at::Tensor& w, int root, DeviceState& ds,
+                                                  hipStream_t s, std::chrono::milliseconds to) {
   const StagedOnly staged_only(staged_only_, a == Algo::IPC_STAGED);  // (read by ipc_run)
   const size_t bytes = w.nbytes();
   if (a == Algo::IPC_SDMA && bytes >= cfg_.ipc_zc_min) {  // every non-root pulls the root's tensor
@@ -481,7 +490,7 @@ void ProcessGroupMI355X::enqueue_broadcast(Algo a, const at::Tensor& w, int root
                  [&](const std::vector<char*>& p, std::vector<kern::CopyDesc>& d) {
                    if (!is_root) d.push_back({p[root], w.data_ptr(), bytes});
                  }))
-      return;
+      return "ipc_sdma";
   }
   if (is_ipc(a)) {
     IpcComm& ic = ipc(ds);
@@ -493,30 +502,33 @@ void ProcessGroupMI355X::enqueue_broadcast(Algo a, const at::Tensor& w, int root
     c.bytes = bytes;
     c.in[0] = w.data_ptr();
     c.out[0] = w.data_ptr();
-    if (ds.ll_ok && bytes_in_ll_range(bytes)) {  // small: the root pushes flag-tagged words
+    if (ll_size(ds, bytes)) {  // small: the root pushes flag-tagged words
       c.coll = kern::IpcColl::BROADCAST_LL;
       ic.launch(c, s);
-      return;
+      return "ipc_ll";
     }
     if (c.coll == kern::IpcColl::BROADCAST_2SHOT)
       ipc_run(ds, c, w.data_ptr(), bytes, (size_t)size_ * kern::kTileBytes, ic.chunk_cap(), s);
     else
       ipc_chunked(ic, c, ic.chunk_cap(), s);
+    return c.coll == kern::IpcColl::BROADCAST_2SHOT ? "ipc_2shot" : "ipc_1shot";
   } else if (a == Algo::RCCL) {
     RcclComm& rc = rccl(ds);
     RcclComm::Issue og(rc, s, capturing(s));
     PDCC_NCCLC(rc.get(), ncclBroadcast(w.data_ptr(), w.data_ptr(), bytes, ncclUint8, root, rc.get(), s));
+    return "rccl";
   } else {
     PDCC_HIP(hipStreamSynchronize(s));
     at::Tensor h = w.cpu();
     shm().broadcast(h.data_ptr(), bytes, root, to);
     if (rank_ != root) const_cast<at::Tensor&>(w).copy_(h);
+    return "host";
   }
 }
 
-void ProcessGroupMI355X::enqueue_allgather(Algo a, const at::Tensor& wi, const std::vector<at::Tensor>& wo, int root,
-                                           bool rooted, DeviceState& ds, hipStream_t s,
-                                           std::chrono::milliseconds to) {
+const char* ProcessGroupMI355X::enqueue_allgather(Algo a, const at::Tensor& wi, const std::vector<at::Tensor>& wo,
+                                                  int root, bool rooted, DeviceState& ds, hipStream_t s,
+                                                  std::chrono::milliseconds to) {
   const StagedOnly staged_only(staged_only_, a == Algo::IPC_STAGED);  // (read by ipc_run)
   const size_t bytes = wi.nbytes();
   const bool receiver = !rooted || rank_ == root;
@@ -528,7 +540,7 @@ void ProcessGroupMI355X::enqueue_allgather(Algo a, const at::Tensor& wi, const s
             d.push_back({r == rank_ ? wi.data_ptr() : p[r], wo[r].data_ptr(), bytes});
           }
         }))
-      return;
+      return "ipc_sdma";
   }
   if (is_ipc(a)) {
     IpcComm& ic = ipc(ds);
@@ -541,19 +553,21 @@ void ProcessGroupMI355X::enqueue_allgather(Algo a, const at::Tensor& wi, const s
     c.in[0] = wi.data_ptr();
     if (receiver)
       for (int r = 0; r < size_; ++r) c.out[r] = wo[r].data_ptr();
-    if (ds.ll_ok && bytes_in_ll_range(bytes)) {  // small: flag-tagged pushes, no staging copy, no barrier
+    if (ll_size(ds, bytes)) {  // small: flag-tagged pushes, no staging copy, no barrier
       c.coll = rooted ? kern::IpcColl::GATHER_LL : kern::IpcColl::ALLGATHER_LL;
       ic.launch(c, s);
-      return;
+      return "ipc_ll";
     }
     if (a == Algo::IPC_DYN && !rooted) c.dyn = std::max(1, cfg_.ipc_dyn);  // (zero-copy runs only)
     c.dyn_min_rows = cfg_.ipc_dyn_min_rows;
     ipc_run(ds, c, wi.data_ptr(), bytes, kern::kTileBytes, ic.chunk_cap(), s);
+    return c.dyn ? "ipc_dyn" : "ipc";
   } else if (a == Algo::RCCL) {
     RcclComm& rc = rccl(ds);
     RcclComm::Issue og(rc, s, capturing(s));
     if (!rooted && is_flat(wo, bytes)) {
       PDCC_NCCLC(rc.get(), ncclAllGather(wi.data_ptr(), wo[0].data_ptr(), bytes, ncclUint8, rc.get(), s));
+      return "rccl";
     } else if (!rooted && !cfg_.list_gather_p2p) {
       // staged: one ring all-gather into a staging buffer, then K2 unpacks into the list
       at::Tensor stg = at::empty({(int64_t)(bytes * size_)}, wi.options().dtype(at::kByte));
@@ -562,6 +576,7 @@ void ProcessGroupMI355X::enqueue_allgather(Algo a, const at::Tensor& wi, const s
       for (int r = 0; r < size_; ++r)
         d.push_back({static_cast<char*>(stg.data_ptr()) + r * bytes, wo[r].data_ptr(), bytes});
       multi_copy_or_memcpy(d, s);
+      return "rccl_staged";
     } else {
       // zero copy: every receiver posts one recv per peer straight into its list entry;
       // over a fully connected xGMI node the W-1 transfers of a rank use W-1 links at once
@@ -574,6 +589,7 @@ void ProcessGroupMI355X::enqueue_allgather(Algo a, const at::Tensor& wi, const s
       PDCC_NCCLC(rc.get(), ncclGroupEnd());
       if (receiver && bytes)
         PDCC_HIP(hipMemcpyAsync(wo[rank_].data_ptr(), wi.data_ptr(), bytes, hipMemcpyDeviceToDevice, s));
+      return rooted ? "rccl" : "rccl_p2p";
     }
   } else {
     PDCC_HIP(hipStreamSynchronize(s));
@@ -589,11 +605,13 @@ void ProcessGroupMI355X::enqueue_allgather(Algo a, const at::Tensor& wi, const s
     else shm().allgather(h.data_ptr(), ptrs, bytes, to);
     if (receiver)
       for (int r = 0; r < size_; ++r) const_cast<at::Tensor&>(wo[r]).copy_(ho[r]);
+    return "host";
   }
 }
 
-void ProcessGroupMI355X::enqueue_scatter(Algo a, const std::vector<at::Tensor>& wi, const at::Tensor& wo, int root,
-                                         DeviceState& ds, hipStream_t s, std::chrono::milliseconds to) {
+const char* ProcessGroupMI355X::enqueue_scatter(Algo a, const std::vector<at::Tensor>& wi, const at::Tensor& wo,
+                                                int root, DeviceState& ds, hipStream_t s,
+                                                std::chrono::milliseconds to) {
   const StagedOnly staged_only(staged_only_, a == Algo::IPC_STAGED);  // (read by ipc_run)
   const size_t bytes = wo.nbytes();
   if (a == Algo::IPC_SDMA && bytes >= cfg_.ipc_zc_min) {
@@ -604,7 +622,7 @@ void ProcessGroupMI355X::enqueue_scatter(Algo a, const std::vector<at::Tensor>& 
     if (sdma_run(ds, z, is_root ? bytes * size_ : 0, s, [&](const std::vector<char*>& p, std::vector<kern::CopyDesc>& d) {
           d.push_back({is_root ? wi[root].data_ptr() : p[root] + (size_t)rank_ * bytes, wo.data_ptr(), bytes});
         }))
-      return;
+      return "ipc_sdma";
   }
   if (is_ipc(a)) {
     IpcComm& ic = ipc(ds);
@@ -618,14 +636,15 @@ void ProcessGroupMI355X::enqueue_scatter(Algo a, const std::vector<at::Tensor>& 
     if (rank_ == root)
       for (int r = 0; r < size_; ++r) c.in[r] = wi[r].data_ptr();
     c.out[0] = wo.data_ptr();
-    if (ds.ll_ok && bytes_in_ll_range(bytes)) {  // small: the root pushes chunk q to rank q
+    if (ll_size(ds, bytes)) {  // small: the root pushes chunk q to rank q
       c.coll = kern::IpcColl::SCATTER_LL;
       ic.launch(c, s);
-      return;
+      return "ipc_ll";
     }
     // a flat root list (e.g. x.chunk(W)) is read in place; the other ranks share nothing
     const void* z = rank_ == root ? (is_flat(wi, bytes) ? wi[0].data_ptr() : nullptr) : nullptr;
     ipc_run(ds, c, z, rank_ == root ? bytes * size_ : 0, kern::kTileBytes, ic.chunk_cap() / size_, s);
+    return "ipc";
   } else if (a == Algo::RCCL) {
     RcclComm& rc = rccl(ds);
     RcclComm::Issue og(rc, s, capturing(s));
@@ -639,6 +658,7 @@ void ProcessGroupMI355X::enqueue_scatter(Algo a, const std::vector<at::Tensor>& 
     PDCC_NCCLC(rc.get(), ncclGroupEnd());
     if (rank_ == root && bytes)
       PDCC_HIP(hipMemcpyAsync(wo.data_ptr(), wi[root].data_ptr(), bytes, hipMemcpyDeviceToDevice, s));
+    return "rccl";
   } else {
     PDCC_HIP(hipStreamSynchronize(s));
     std::vector<at::Tensor> hi;
@@ -651,38 +671,39 @@ void ProcessGroupMI355X::enqueue_scatter(Algo a, const std::vector<at::Tensor>& 
     at::Tensor h = at::empty(wo.sizes(), wo.options().device(at::kCPU));
     shm().scatter(ptrs, h.data_ptr(), bytes, root, to);
     const_cast<at::Tensor&>(wo).copy_(h);
+    return "host";
   }
 }
 
-void ProcessGroupMI355X::enqueue_reduce_scatter(Algo a, const std::vector<at::Tensor>& wi, const at::Tensor& wo,
-                                                kern::DType kd, kern::RedOp ko, ncclDataType_t nd, ncclRedOp_t no,
-                                                bool nok, RedOpType op, DeviceState& ds, hipStream_t s,
-                                                std::chrono::milliseconds to) {
+const char* ProcessGroupMI355X::enqueue_reduce_scatter(Algo a, const std::vector<at::Tensor>& wi,
+                                                       const at::Tensor& wo, const RedSpec& red, DeviceState& ds,
+                                                       hipStream_t s, std::chrono::milliseconds to) {
   const StagedOnly staged_only(staged_only_, a == Algo::IPC_STAGED);  // (read by ipc_run)
   const size_t bytes = wo.nbytes();
   if (is_ipc(a)) {
     IpcComm& ic = ipc(ds);
     kern::IpcCall c{};
     c.coll = kern::IpcColl::REDUCE_SCATTER;
-    c.dtype = kd;
-    c.op = ko;
+    c.dtype = red.kd;
+    c.op = red.ko;
     c.avg_div = size_;
     c.bytes = bytes;
     c.zstride = bytes;
     for (int r = 0; r < size_; ++r) c.in[r] = wi[r].data_ptr();
     c.out[0] = wo.data_ptr();
-    if (ds.ll_ok && bytes_in_ll_range(bytes)) {  // small: chunk q pushed to rank q, reduced there
+    if (ll_size(ds, bytes)) {  // small: chunk q pushed to rank q, reduced there
       c.coll = kern::IpcColl::REDUCE_SCATTER_LL;
       ic.launch(c, s);
-      return;
+      return "ipc_ll";
     }
     if (a == Algo::IPC_DYN) c.dyn = std::max(1, cfg_.ipc_dyn);  // (zero-copy runs only)
     c.dyn_min_rows = cfg_.ipc_dyn_min_rows;
     // a flat input (reduce_scatter_tensor) is read in place by every peer
     ipc_run(ds, c, is_flat(wi, bytes) ? wi[0].data_ptr() : nullptr, bytes * size_, kern::kTileBytes,
             ic.chunk_cap() / size_, s);
+    return c.dyn ? "ipc_dyn" : "ipc";
   } else if (a == Algo::RCCL) {
-    TORCH_CHECK(nok, "pdcc: RCCL has no reduction for ", op_name(op), " on ", wo.scalar_type());
+    TORCH_CHECK(red.nok, "pdcc: RCCL has no reduction for ", op_name(red.op), " on ", wo.scalar_type());
     RcclComm& rc = rccl(ds);
     const void* src;
     at::Tensor stg;
@@ -697,7 +718,8 @@ void ProcessGroupMI355X::enqueue_reduce_scatter(Algo a, const std::vector<at::Te
       src = stg.data_ptr();
     }
     RcclComm::Issue og(rc, s, capturing(s));
-    PDCC_NCCLC(rc.get(), ncclReduceScatter(src, wo.data_ptr(), wo.numel(), nd, no, rc.get(), s));
+    PDCC_NCCLC(rc.get(), ncclReduceScatter(src, wo.data_ptr(), wo.numel(), red.nd, red.no, rc.get(), s));
+    return "rccl";
   } else {
     PDCC_HIP(hipStreamSynchronize(s));
     std::vector<at::Tensor> hi;
@@ -707,13 +729,15 @@ void ProcessGroupMI355X::enqueue_reduce_scatter(Algo a, const std::vector<at::Te
       ptrs.push_back(hi.back().data_ptr());
     }
     at::Tensor h = at::empty(wo.sizes(), wo.options().device(at::kCPU));
-    shm().reduce_scatter(ptrs, h.data_ptr(), wo.numel(), wo.scalar_type(), op, to);
+    shm().reduce_scatter(ptrs, h.data_ptr(), wo.numel(), wo.scalar_type(), red.op, to);
     const_cast<at::Tensor&>(wo).copy_(h);
+    return "host";
   }
 }
 
-void ProcessGroupMI355X::enqueue_alltoall(Algo a, const std::vector<at::Tensor>& wi, const std::vector<at::Tensor>& wo,
-                                          bool equal, DeviceState& ds, hipStream_t s, std::chrono::milliseconds to) {
+const char* ProcessGroupMI355X::enqueue_alltoall(Algo a, const std::vector<at::Tensor>& wi,
+                                                 const std::vector<at::Tensor>& wo, bool equal, DeviceState& ds,
+                                                 hipStream_t s, std::chrono::milliseconds to) {
   const StagedOnly staged_only(staged_only_, a == Algo::IPC_STAGED);  // (read by ipc_run)
   if (a == Algo::IPC_SDMA && equal && wi[0].nbytes() >= cfg_.ipc_zc_min) {
     // rank r pulls block r of every rank's flat input into its out[q] (a non-flat input: the IPC kernels)
@@ -725,7 +749,7 @@ void ProcessGroupMI355X::enqueue_alltoall(Algo a, const std::vector<at::Tensor>&
             d.push_back({q == rank_ ? wi[rank_].data_ptr() : p[q] + (size_t)rank_ * chunk, wo[q].data_ptr(), chunk});
           }
         }))
-      return;
+      return "ipc_sdma";
   }
   if (is_ipc(a)) {
     TORCH_CHECK(equal, "pdcc: the IPC all-to-all needs equal splits");
@@ -740,13 +764,14 @@ void ProcessGroupMI355X::enqueue_alltoall(Algo a, const std::vector<at::Tensor>&
       c.in[r] = wi[r].data_ptr();
       c.out[r] = wo[r].data_ptr();
     }
-    if (ds.ll_ok && bytes_in_ll_range(c.bytes)) {  // small: chunk q pushed straight to rank q
+    if (ll_size(ds, c.bytes)) {  // small: chunk q pushed straight to rank q
       c.coll = kern::IpcColl::ALLTOALL_LL;
       ic.launch(c, s);
-      return;
+      return "ipc_ll";
     }
     ipc_run(ds, c, is_flat(wi, c.bytes) ? wi[0].data_ptr() : nullptr, c.bytes * size_, kern::kTileBytes,
             ic.chunk_cap() / size_, s);
+    return "ipc";
   } else if (a == Algo::RCCL) {
     RcclComm& rc = rccl(ds);
     RcclComm::Issue og(rc, s, capturing(s));
@@ -765,6 +790,7 @@ void ProcessGroupMI355X::enqueue_alltoall(Algo a, const std::vector<at::Tensor>&
         PDCC_HIP(hipMemcpyAsync(wo[rank_].data_ptr(), wi[rank_].data_ptr(), wi[rank_].nbytes(),
                                 hipMemcpyDeviceToDevice, s));
     }
+    return "rccl";
   } else {
     PDCC_HIP(hipStreamSynchronize(s));
     std::vector<at::Tensor> hi, ho;
@@ -783,7 +809,48 @@ void ProcessGroupMI355X::enqueue_alltoall(Algo a, const std::vector<at::Tensor>&
     }
     shm().alltoall(ip, sb, op, rb, to);
     for (size_t i = 0; i < wo.size(); ++i) const_cast<at::Tensor&>(wo[i]).copy_(ho[i]);
+    return "host";
   }
+}
+
+// =================================================================== one issue path
+// What every GPU collective does once its front-end (below) has taken the local shortcut and prepared
+// the buffers. The front-end hands over what differs: the tune-key slots (`c`), the race on scratch
+// buffers (`tune`), its engine (`enqueue(algo, stream)`: returns the label of the protocol it ran), the
+// copy from prepared temporaries back into the caller's tensors, what to keep alive and what the Work
+// holds. A coalesced call (`co`) unpacks its members behind the collective, on the same stream.
+template <class Tune, class Enqueue, class CopyBack>
+c10::intrusive_ptr<c10d::Work> ProcessGroupMI355X::issue_collective(const Issue& c, DeviceState& ds, Tune&& tune,
+                                                                    Enqueue&& enqueue, CopyBack&& copy_back,
+                                                                    std::vector<at::Tensor> keep_alive,
+                                                                    std::vector<at::Tensor> outputs,
+                                                                    const std::shared_ptr<const Coalesced>& co) {
+  const Algo a = decide(c.coll, c.key_dtype, c.key_op, c.bytes, ds, c.a0, c.rccl_can, c.ipc_can, tune);
+  if (co) {
+    keep_alive.insert(keep_alive.end(), co->members.begin(), co->members.end());
+    outputs = co->members;
+  }
+  const char* label = nullptr;
+  auto job = [&](hipStream_t s) {
+    label = enqueue(a, s);
+    copy_back();
+    if (co) co->run(s);
+  };
+  c10::intrusive_ptr<c10d::Work> work;
+  if (a == Algo::HOST) {  // synchronous, on the caller's stream
+    job(current_stream(ds.device));
+    work = cpu_done(c.coll, std::move(outputs));
+  } else {  // (gpu_issue runs the job before it returns)
+    std::shared_ptr<IpcComm> icp;
+    if (is_ipc(a)) {
+      ipc(ds);
+      icp = ds.ipc;
+    }
+    work = gpu_issue(c.coll, ds, a, keep_alive, std::move(outputs), c.to, job, std::move(icp));
+  }
+  record(c.coll, label, c.stat_bytes, c.t0);
+  if (a != Algo::HOST) hp_.lap(HostStage::RECORD);  // (the stage profile follows GPU engines only)
+  return work;
 }
 
 // =================================================================== all-reduce / reduce
@@ -800,67 +867,37 @@ c10::intrusive_ptr<c10d::Work> ProcessGroupMI355X::gpu_allreduce(at::Tensor& t, 
   }
   DeviceState& ds = dev_state(t);
   hp_.lap(HostStage::DEV_STATE);
-  kern::DType kd;
-  kern::RedOp ko;
-  const bool kok = kern_dtype(t.scalar_type(), kd) && kern_op(op, ko) && kern::supports(kd, ko);
-  ncclDataType_t nd = ncclFloat32;
-  ncclRedOp_t no = ncclSum;
-  const bool nok = nccl_dtype(t.scalar_type(), nd) && nccl_op(op, t.scalar_type(), no);
-  const bool rccl_can = ds.rccl_ok && nok, ipc_can = ds.ipc_ok && kok;
+  const RedSpec red = red_spec(t.scalar_type(), op);
+  const bool rccl_can = ds.rccl_ok && red.nok, ipc_can = ds.ipc_ok && red.kok;
   const Algo a0 = choose(cname, bytes, ds, rccl_can, ipc_can);
   at::Tensor w = prep_in(t, ipc_can && ll_call(ds, bytes));  // (an LL call: any alignment, see prep_in)
-  const Algo a = decide(cname, (int)t.scalar_type(), (int)op, bytes, ds, a0, rccl_can, ipc_can,
-                        [&](const TuneKey& key, const std::vector<Algo>& cands) {
+  auto enqueue = [&](Algo a, const at::Tensor& x, hipStream_t s) {
+    return enqueue_allreduce(a, x, red, root, rooted, ds, s, to);
+  };
+  auto tune = [&](const TuneKey& key, const std::vector<Algo>& cands) {
     const int64_t n = sample_numel(w.numel(), w.element_size(), cfg_.autotune_sample);
     std::vector<at::Tensor> sc;
     for (size_t k = 0; k < cands.size(); ++k) sc.push_back(w.reshape({-1}).narrow(0, 0, n).clone());
     const hipStream_t cs = current_stream(ds.device);
     return autotune(
-        key, bytes, ds, cands,
-        [&](size_t k) { enqueue_allreduce(cands[k], sc[k], kd, ko, nd, no, nok, op, root, rooted, ds, cs, to); },
+        key, bytes, ds, cands, [&](size_t k) { enqueue(cands[k], sc[k], cs); },
         [&](size_t r, size_t k) { return results_match(sc[r], sc[k], op, size_); },
         [&] {  // IPC as the reference: itself vs the host transport on a prefix
           const int64_t m = sample_numel(w.numel(), w.element_size(), kHostTuneMax);
           at::Tensor h = w.reshape({-1}).narrow(0, 0, m).clone(), g = h.clone();
-          enqueue_allreduce(Algo::HOST, h, kd, ko, nd, no, nok, op, root, rooted, ds, cs, to);
-          enqueue_allreduce(cands[0], g, kd, ko, nd, no, nok, op, root, rooted, ds, cs, to);
+          enqueue(Algo::HOST, h, cs);
+          enqueue(cands[0], g, cs);
           PDCC_HIP(hipStreamSynchronize(cs));
           // (a partial sanity check: the prefix runs the protocol of its own size, not the key's -- the
           // raced variants are then checked against the full-size reference run, results_match above)
           return results_match(h, g, op, size_);
         });
-  });
-  if (a == Algo::HOST) {
-    enqueue_allreduce(Algo::HOST, w, kd, ko, nd, no, nok, op, root, rooted, ds, current_stream(ds.device), to);
-    if (!w.is_same(t) && (!rooted || rank_ == root)) t.copy_(w);
-    if (co) co->run(current_stream(ds.device));
-    record(cname, "host", bytes, t0);
-    return cpu_done(cname, co ? co->members : std::vector<at::Tensor>{t});
-  }
-  std::shared_ptr<IpcComm> icp;
-  if (is_ipc(a)) {
-    ipc(ds);
-    icp = ds.ipc;
-  }
-  const bool one_shot = bytes <= cfg_.ipc_1shot_max;
-  std::vector<at::Tensor> keep{t, w};
-  if (co) keep.insert(keep.end(), co->members.begin(), co->members.end());
-  auto work = gpu_issue(cname, ds, a, keep, co ? co->members : std::vector<at::Tensor>{t}, to,
-                        [=, dsp = &ds, t = t](hipStream_t x) mutable {
-    enqueue_allreduce(a, w, kd, ko, nd, no, nok, op, root, rooted, *dsp, x, to);
-    if (!w.is_same(t) && (!rooted || rank_ == root)) t.copy_(w);
-    if (co) co->run(x);
-  }, icp);
-  const bool ll = ds.ll_ok && bytes_in_ll_range(bytes);
-  record(cname, is_ipc(a) ? (ll                                 ? "ipc_ll"
-                             : one_shot                         ? "ipc_1shot"
-                             : a == Algo::IPC_PUSH && !rooted ? "ipc_push"
-                             : a == Algo::IPC_WIDE            ? "ipc_2shot_wide"
-                             : a == Algo::IPC_DYN && !rooted  ? "ipc_2shot_dyn"
-                                                              : "ipc_2shot")
-                          : a == Algo::RCCL_WIDE ? "rccl_wide" : "rccl", bytes, t0);
-  hp_.lap(HostStage::RECORD);
-  return work;
+  };
+  return issue_collective(
+      {cname, (int)t.scalar_type(), (int)op, bytes, bytes, a0, rccl_can, ipc_can, t0, to}, ds, tune,
+      [&](Algo a, hipStream_t s) { return enqueue(a, w, s); },
+      [&] { if (!w.is_same(t) && (!rooted || rank_ == root)) t.copy_(w); },
+      {t, w}, {t}, co);
 }
 
 // =================================================================== broadcast
@@ -875,8 +912,7 @@ c10::intrusive_ptr<c10d::Work> ProcessGroupMI355X::gpu_broadcast(at::Tensor& t, 
   DeviceState& ds = dev_state(t);
   const Algo a0 = choose(Coll::BROADCAST, bytes, ds, ds.rccl_ok, ds.ipc_ok);
   at::Tensor w = prep_in(t, ll_call(ds, bytes));  // (an LL call: any alignment, see prep_in)
-  const Algo a = decide(Coll::BROADCAST, -1, -1, bytes, ds, a0, ds.rccl_ok, ds.ipc_ok,
-                        [&](const TuneKey& key, const std::vector<Algo>& cands) {
+  auto tune = [&](const TuneKey& key, const std::vector<Algo>& cands) {
     const int64_t n = sample_numel(w.numel(), w.element_size(), cfg_.autotune_sample);
     std::vector<at::Tensor> sc;
     for (size_t k = 0; k < cands.size(); ++k) sc.push_back(w.reshape({-1}).narrow(0, 0, n).clone());
@@ -893,26 +929,12 @@ c10::intrusive_ptr<c10d::Work> ProcessGroupMI355X::gpu_broadcast(at::Tensor& t, 
           PDCC_HIP(hipStreamSynchronize(cs));
           return at::equal(h, g);
         });
-  });
-  if (a == Algo::HOST) {
-    enqueue_broadcast(Algo::HOST, w, root, ds, current_stream(ds.device), to);
-    if (!w.is_same(t) && rank_ != root) t.copy_(w);
-    record(Coll::BROADCAST, "host", bytes, t0);
-    return cpu_done(Coll::BROADCAST, {t});
-  }
-  std::shared_ptr<IpcComm> icp;
-  if (is_ipc(a)) {
-    ipc(ds);
-    icp = ds.ipc;
-  }
-  const bool one_shot = bytes <= cfg_.ipc_1shot_max;
-  auto work = gpu_issue(Coll::BROADCAST, ds, a, {t, w}, {t}, to, [=, dsp = &ds, t = t](hipStream_t x) mutable {
-    enqueue_broadcast(a, w, root, *dsp, x, to);
-    if (!w.is_same(t) && rank_ != root) t.copy_(w);
-  }, icp);
-  const bool ll = ds.ll_ok && bytes_in_ll_range(bytes);
-  record(Coll::BROADCAST, is_ipc(a) ? (ll ? "ipc_ll" : one_shot ? "ipc_1shot" : "ipc_2shot") : "rccl", bytes, t0);
-  return work;
+  };
+  return issue_collective(
+      {Coll::BROADCAST, -1, -1, bytes, bytes, a0, ds.rccl_ok, ds.ipc_ok, t0, to}, ds, tune,
+      [&](Algo a, hipStream_t s) { return enqueue_broadcast(a, w, root, ds, s, to); },
+      [&] { if (!w.is_same(t) && rank_ != root) t.copy_(w); },
+      {t, w}, {t});
 }
 
 // =================================================================== all-gather / gather
@@ -939,8 +961,7 @@ c10::intrusive_ptr<c10d::Work> ProcessGroupMI355X::gpu_allgather(std::vector<at:
   // the layout is part of the key (RCCL takes a different path for a flat output);
   // on gather only the root has outputs, so the key cannot depend on them there
   const bool flat = !rooted && is_flat(wo, bytes);
-  const Algo a = decide(cname, -1, rooted ? -1 : (flat ? kLayoutFlat : kLayoutList), bytes, ds, a0, ds.rccl_ok,
-                        ds.ipc_ok, [&](const TuneKey& key, const std::vector<Algo>& cands) {
+  auto tune = [&](const TuneKey& key, const std::vector<Algo>& cands) {
     const int64_t n = sample_numel(wi.numel(), wi.element_size(), cfg_.autotune_sample, size_);
     const at::Tensor si = wi.reshape({-1}).narrow(0, 0, n);
     std::vector<std::vector<at::Tensor>> sc(cands.size());
@@ -963,37 +984,18 @@ c10::intrusive_ptr<c10d::Work> ProcessGroupMI355X::gpu_allgather(std::vector<at:
           PDCC_HIP(hipStreamSynchronize(cs));
           return lists_equal(h, g);
         });
-  });
-  if (a == Algo::HOST) {
-    enqueue_allgather(Algo::HOST, wi, wo, root, rooted, ds, current_stream(ds.device), to);
-    if (receiver)
-      for (int r = 0; r < size_; ++r)
-        if (!wo[r].is_same(outs[r])) outs[r].copy_(wo[r]);
-    if (co) co->run(current_stream(ds.device));
-    record(cname, "host", bytes, t0);
-    return cpu_done(cname, co ? co->members : outs);
-  }
+  };
   std::vector<at::Tensor> keep{in, wi};
-  for (auto& o : wo) keep.push_back(o);
-  if (co) keep.insert(keep.end(), co->members.begin(), co->members.end());
-  std::shared_ptr<IpcComm> icp;
-  if (is_ipc(a)) {
-    ipc(ds);
-    icp = ds.ipc;
-  }
-  const bool ll = ds.ll_ok && bytes_in_ll_range(wi.nbytes());
-  const char* algo = is_ipc(a) ? (ll ? "ipc_ll" : a == Algo::IPC_DYN && !rooted ? "ipc_dyn" : "ipc")
-                                    : (flat || rooted ? "rccl" : (cfg_.list_gather_p2p ? "rccl_p2p" : "rccl_staged"));
-  auto work = gpu_issue(cname, ds, a, keep, co ? co->members : outs, to,
-                        [=, dsp = &ds, outs = outs](hipStream_t x) mutable {
-    enqueue_allgather(a, wi, wo, root, rooted, *dsp, x, to);
-    if (receiver)
-      for (int r = 0; r < size_; ++r)
-        if (!wo[r].is_same(outs[r])) outs[r].copy_(wo[r]);
-    if (co) co->run(x);
-  }, icp);
-  record(cname, algo, bytes, t0);
-  return work;
+  keep.insert(keep.end(), wo.begin(), wo.end());
+  return issue_collective(
+      {cname, -1, rooted ? -1 : (flat ? kLayoutFlat : kLayoutList), bytes, bytes, a0, ds.rccl_ok, ds.ipc_ok, t0, to},
+      ds, tune, [&](Algo a, hipStream_t s) { return enqueue_allgather(a, wi, wo, root, rooted, ds, s, to); },
+      [&] {
+        if (receiver)
+          for (int r = 0; r < size_; ++r)
+            if (!wo[r].is_same(outs[r])) outs[r].copy_(wo[r]);
+      },
+      std::move(keep), outs, co);
 }
 
 // =================================================================== scatter
@@ -1013,8 +1015,7 @@ c10::intrusive_ptr<c10d::Work> ProcessGroupMI355X::gpu_scatter(at::Tensor& out, 
   if (rank_ == root)
     for (auto& i : ins) wi.push_back(prep_in(i, any_align));
   at::Tensor wo = prep_out(out, any_align);
-  const Algo a = decide(Coll::SCATTER, -1, -1, bytes, ds, a0, ds.rccl_ok, ds.ipc_ok,
-                        [&](const TuneKey& key, const std::vector<Algo>& cands) {
+  auto tune = [&](const TuneKey& key, const std::vector<Algo>& cands) {
     const int64_t n = sample_numel(wo.numel(), wo.element_size(), cfg_.autotune_sample, size_);
     const std::vector<at::Tensor> si = sample_inputs(wi, n, false);
     std::vector<at::Tensor> sc;
@@ -1023,26 +1024,14 @@ c10::intrusive_ptr<c10d::Work> ProcessGroupMI355X::gpu_scatter(at::Tensor& out, 
     return autotune(
         key, bytes, ds, cands, [&](size_t k) { enqueue_scatter(cands[k], si, sc[k], root, ds, cs, to); },
         [&](size_t r, size_t k) { return at::equal(sc[r], sc[k]); });
-  });
-  if (a == Algo::HOST) {
-    enqueue_scatter(Algo::HOST, wi, wo, root, ds, current_stream(ds.device), to);
-    if (!wo.is_same(out)) out.copy_(wo);
-    record(Coll::SCATTER, "host", bytes, t0);
-    return cpu_done(Coll::SCATTER, {out});
-  }
+  };
   std::vector<at::Tensor> keep{out, wo};
-  for (auto& i : wi) keep.push_back(i);
-  std::shared_ptr<IpcComm> icp;
-  if (is_ipc(a)) {
-    ipc(ds);
-    icp = ds.ipc;
-  }
-  auto work = gpu_issue(Coll::SCATTER, ds, a, keep, {out}, to, [=, dsp = &ds, out = out](hipStream_t x) mutable {
-    enqueue_scatter(a, wi, wo, root, *dsp, x, to);
-    if (!wo.is_same(out)) out.copy_(wo);
-  }, icp);
-  record(Coll::SCATTER, is_ipc(a) ? (ds.ll_ok && bytes_in_ll_range(bytes) ? "ipc_ll" : "ipc") : "rccl", bytes, t0);
-  return work;
+  keep.insert(keep.end(), wi.begin(), wi.end());
+  return issue_collective(
+      {Coll::SCATTER, -1, -1, bytes, bytes, a0, ds.rccl_ok, ds.ipc_ok, t0, to}, ds, tune,
+      [&](Algo a, hipStream_t s) { return enqueue_scatter(a, wi, wo, root, ds, s, to); },
+      [&] { if (!wo.is_same(out)) out.copy_(wo); },
+      std::move(keep), {out});
 }
 
 // =================================================================== reduce-scatter
@@ -1058,64 +1047,39 @@ c10::intrusive_ptr<c10d::Work> ProcessGroupMI355X::gpu_reduce_scatter(at::Tensor
     return cpu_done(Coll::REDUCE_SCATTER, {out});
   }
   DeviceState& ds = dev_state(out);
-  kern::DType kd;
-  kern::RedOp ko;
-  const bool kok = kern_dtype(out.scalar_type(), kd) && kern_op(op, ko) && kern::supports(kd, ko);
-  ncclDataType_t nd = ncclFloat32;
-  ncclRedOp_t no = ncclSum;
-  const bool nok = nccl_dtype(out.scalar_type(), nd) && nccl_op(op, out.scalar_type(), no);
-  const bool rccl_can = ds.rccl_ok && nok, ipc_can = ds.ipc_ok && kok;
+  const RedSpec red = red_spec(out.scalar_type(), op);
+  const bool rccl_can = ds.rccl_ok && red.nok, ipc_can = ds.ipc_ok && red.kok;
   const Algo a0 = choose(Coll::REDUCE_SCATTER, bytes, ds, rccl_can, ipc_can);
   const bool any_align = ll_call(ds, bytes);  // (see prep_in)
   std::vector<at::Tensor> wi;
   for (auto& i : ins) wi.push_back(prep_in(i, any_align));
   at::Tensor wo = prep_out(out, any_align);
-  const Algo a = decide(Coll::REDUCE_SCATTER, (int)out.scalar_type(), (int)op, bytes, ds, a0, rccl_can, ipc_can,
-                        [&](const TuneKey& key, const std::vector<Algo>& cands) {
+  auto tune = [&](const TuneKey& key, const std::vector<Algo>& cands) {
     const int64_t n = sample_numel(wo.numel(), wo.element_size(), cfg_.autotune_sample, size_);
     const std::vector<at::Tensor> si = sample_inputs(wi, n, is_flat(wi, bytes));
     std::vector<at::Tensor> sc;
     for (size_t k = 0; k < cands.size(); ++k) sc.push_back(at::empty({n}, wo.options()));
     const hipStream_t cs = current_stream(ds.device);
     return autotune(
-        key, bytes, ds, cands,
-        [&](size_t k) { enqueue_reduce_scatter(cands[k], si, sc[k], kd, ko, nd, no, nok, op, ds, cs, to); },
+        key, bytes, ds, cands, [&](size_t k) { enqueue_reduce_scatter(cands[k], si, sc[k], red, ds, cs, to); },
         [&](size_t r, size_t k) { return results_match(sc[r], sc[k], op, size_); },
         [&] {  // IPC as the reference: itself vs the host transport on a prefix of every chunk
           const int64_t m = sample_numel(wo.numel(), wo.element_size(), kHostTuneMax, size_);
           const std::vector<at::Tensor> pi = sample_inputs(wi, m, false);
           at::Tensor h = at::empty({m}, wo.options()), g = at::empty({m}, wo.options());
-          enqueue_reduce_scatter(Algo::HOST, pi, h, kd, ko, nd, no, nok, op, ds, cs, to);
-          enqueue_reduce_scatter(cands[0], pi, g, kd, ko, nd, no, nok, op, ds, cs, to);
+          enqueue_reduce_scatter(Algo::HOST, pi, h, red, ds, cs, to);
+          enqueue_reduce_scatter(cands[0], pi, g, red, ds, cs, to);
           PDCC_HIP(hipStreamSynchronize(cs));
           return results_match(h, g, op, size_);
         });
-  });
-  if (a == Algo::HOST) {
-    enqueue_reduce_scatter(Algo::HOST, wi, wo, kd, ko, nd, no, nok, op, ds, current_stream(ds.device), to);
-    if (!wo.is_same(out)) out.copy_(wo);
-    if (co) co->run(current_stream(ds.device));
-    record(Coll::REDUCE_SCATTER, "host", bytes, t0);
-    return cpu_done(Coll::REDUCE_SCATTER, co ? co->members : std::vector<at::Tensor>{out});
-  }
+  };
   std::vector<at::Tensor> keep{out, wo};
-  for (auto& i : wi) keep.push_back(i);
-  if (co) keep.insert(keep.end(), co->members.begin(), co->members.end());
-  std::shared_ptr<IpcComm> icp;
-  if (is_ipc(a)) {
-    ipc(ds);
-    icp = ds.ipc;
-  }
-  auto work = gpu_issue(Coll::REDUCE_SCATTER, ds, a, keep, co ? co->members : std::vector<at::Tensor>{out}, to,
-                        [=, dsp = &ds, out = out](hipStream_t x) mutable {
-    enqueue_reduce_scatter(a, wi, wo, kd, ko, nd, no, nok, op, *dsp, x, to);
-    if (!wo.is_same(out)) out.copy_(wo);
-    if (co) co->run(x);
-  }, icp);
-  record(Coll::REDUCE_SCATTER,
-         is_ipc(a) ? (ds.ll_ok && bytes_in_ll_range(bytes) ? "ipc_ll" : a == Algo::IPC_DYN ? "ipc_dyn" : "ipc") : "rccl",
-         bytes, t0);
-  return work;
+  keep.insert(keep.end(), wi.begin(), wi.end());
+  return issue_collective(
+      {Coll::REDUCE_SCATTER, (int)out.scalar_type(), (int)op, bytes, bytes, a0, rccl_can, ipc_can, t0, to}, ds, tune,
+      [&](Algo a, hipStream_t s) { return enqueue_reduce_scatter(a, wi, wo, red, ds, s, to); },
+      [&] { if (!wo.is_same(out)) out.copy_(wo); },
+      std::move(keep), {out}, co);
 }
 
 // =================================================================== all-to-all
@@ -1132,6 +1096,8 @@ c10::intrusive_ptr<c10d::Work> ProcessGroupMI355X::gpu_alltoall(std::vector<at::
   }
   DeviceState& ds = dev_state(ins[0]);
   const size_t chunk = ins[0].nbytes();
+  // uneven splits take the same path: without the IPC engine (`ipc_can`) decide() has no candidates to
+  // race and keeps the static choice, RCCL's grouped send/recv or the host transport
   const bool ipc_can = ds.ipc_ok && equal;
   const Algo a0 = choose(Coll::ALLTOALL, equal ? chunk : SIZE_MAX, ds, ds.rccl_ok, ipc_can);
   const bool any_align = equal && ll_call(ds, chunk);  // (see prep_in)
@@ -1139,8 +1105,7 @@ c10::intrusive_ptr<c10d::Work> ProcessGroupMI355X::gpu_alltoall(std::vector<at::
   for (auto& i : ins) wi.push_back(prep_in(i, any_align));
   for (auto& o : outs) wo.push_back(prep_out(o, any_align));
   const bool flat = equal && is_flat(wi, chunk) && is_flat(wo, chunk);
-  const Algo a = !equal ? a0 : decide(Coll::ALLTOALL, -1, flat ? kLayoutFlat : kLayoutList, chunk, ds, a0,
-                                      ds.rccl_ok, ipc_can, [&](const TuneKey& key, const std::vector<Algo>& cands) {
+  auto tune = [&](const TuneKey& key, const std::vector<Algo>& cands) {
     const int64_t n = sample_numel(wi[0].numel(), wi[0].element_size(), cfg_.autotune_sample, size_);
     const std::vector<at::Tensor> si = sample_inputs(wi, n, flat);
     std::vector<std::vector<at::Tensor>> sc;
@@ -1149,237 +1114,17 @@ c10::intrusive_ptr<c10d::Work> ProcessGroupMI355X::gpu_alltoall(std::vector<at::
     return autotune(
         key, chunk, ds, cands, [&](size_t k) { enqueue_alltoall(cands[k], si, sc[k], true, ds, cs, to); },
         [&](size_t r, size_t k) { return lists_equal(sc[r], sc[k]); });
-  });
-  if (a == Algo::HOST) {
-    enqueue_alltoall(Algo::HOST, wi, wo, equal, ds, current_stream(ds.device), to);
-    for (size_t i = 0; i < outs.size(); ++i)
-      if (!wo[i].is_same(outs[i])) outs[i].copy_(wo[i]);
-    record(Coll::ALLTOALL, "host", total, t0);
-    return cpu_done(Coll::ALLTOALL, outs);
-  }
-  std::vector<at::Tensor> keep;
-  for (auto& x : wi) keep.push_back(x);
-  for (auto& x : wo) keep.push_back(x);
-  std::shared_ptr<IpcComm> icp;
-  if (is_ipc(a)) {
-    ipc(ds);
-    icp = ds.ipc;
-  }
-  auto work = gpu_issue(Coll::ALLTOALL, ds, a, keep, outs, to, [=, dsp = &ds, outs = outs](hipStream_t x) mutable {
-    enqueue_alltoall(a, wi, wo, equal, *dsp, x, to);
-    for (size_t i = 0; i < outs.size(); ++i)
-      if (!wo[i].is_same(outs[i])) outs[i].copy_(wo[i]);
-  }, icp);
-  record(Coll::ALLTOALL, is_ipc(a) ? (ds.ll_ok && bytes_in_ll_range(chunk) ? "ipc_ll" : "ipc") : "rccl", total,
-         t0);
-  return work;
-}
-
-// =================================================================== p2p + coalescing
-// Host-staged point-to-point (ranks sharing a GPU, or PDCC_ALGO=host): the copy to
-// the host happens now, on the caller's stream; the transfer runs on the backend's
-// send/recv threads over the pair's shared-memory channel, so isend/irecv pairs
-// and rings never deadlock; the copy back to the GPU happens on the recv thread.
-c10::intrusive_ptr<c10d::Work> ProcessGroupMI355X::host_p2p(at::Tensor& t, int peer, bool is_send,
-                                                            std::chrono::milliseconds to) {
-  TORCH_CHECK(!capturing_on(t.device().index()), "pdcc: ", is_send ? "send" : "recv",
-              " runs on the host transport here, which cannot be captured into a graph");
-  const auto t0 = std::chrono::steady_clock::now();
-  const Coll cname = is_send ? Coll::SEND : Coll::RECV;
-  auto work = c10::make_intrusive<WorkMI355X>(rank_, is_send ? c10d::OpType::SEND : c10d::OpType::RECV,
-                                              op_seq_.load(), std::vector<at::Tensor>{t});
-  const int pi = peer < rank_ ? 0 : 1;  // the peer's rank inside the pair channel
-  if (is_send) {
-    at::Tensor h = t.cpu().contiguous();
-    p2p_submit(true, Job{[this, h, peer, pi, to] { shm_pair(peer).send(h.data_ptr(), h.nbytes(), pi, to); }, work});
-  } else {
-    p2p_submit(false, Job{[this, t, peer, pi, to]() mutable {
-                            at::Tensor h = at::empty(t.sizes(), t.options().device(at::kCPU));
-                            shm_pair(peer).recv(h.data_ptr(), h.nbytes(), pi, to);
-                            c10::hip::HIPGuardMasqueradingAsCUDA g(t.device());
-                            t.copy_(h);
-                            PDCC_HIP(hipStreamSynchronize(current_stream(t.device().index())));
-                          },
-                          work});
-  }
-  if (coalescing_) coalesced_cpu_.push_back(work);
-  record(cname, "host", t.nbytes(), t0);
-  return work;
-}
-
-c10::intrusive_ptr<c10d::Work> ProcessGroupMI355X::gpu_p2p(at::Tensor& t, int peer, bool is_send,
-                                                           std::chrono::milliseconds to) {
-  const auto t0 = std::chrono::steady_clock::now();
-  const Coll cname = is_send ? Coll::SEND : Coll::RECV;
-  if (coalescing_) {
-    // batch_isend_irecv: one group call on the group's communicator (like ProcessGroupNCCL,
-    // every rank of the group takes part in the batch that first uses it)
-    DeviceState& ds = dev_state(t);
-    if (!ds.rccl_ok || cfg_.force_algo == Algo::HOST) return host_p2p(t, peer, is_send, to);
-    RcclComm& rc = rccl(ds);
-    at::Tensor w = is_send ? prep_in(t) : prep_out(t);
-    coalesced_.push_back([w, peer, is_send, comm = rc.get()](hipStream_t s) mutable {
-      if (is_send) PDCC_NCCL(ncclSend(w.data_ptr(), w.nbytes(), ncclUint8, peer, comm, s));
-      else PDCC_NCCL(ncclRecv(w.data_ptr(), w.nbytes(), ncclUint8, peer, comm, s));
-    });
-    coalesced_tensors_.push_back(t);
-    coalesced_tensors_.push_back(w);
-    coalesced_ds_ = &ds;
-    record(cname, "rccl_coalesced", t.nbytes(), t0);
-    return cpu_done(cname, {t});
-  }
-  // single send/recv: only this pair of ranks takes part
-  DeviceState& ds = dev_local(t);
-  if (cfg_.force_algo == Algo::HOST || !pair_on_distinct_devices(ds, peer)) return host_p2p(t, peer, is_send, to);
-  auto pc = pair_chan(ds, peer);
-  const int pi = peer < rank_ ? 0 : 1;  // the peer's rank in the pair communicator
-  at::Tensor w = is_send ? prep_in(t) : prep_out(t);
-  {
-    std::unique_lock<std::mutex> lk(pc->mu);
-    if (!pc->error.empty()) throw std::runtime_error("pdcc: point-to-point channel to rank " + std::to_string(peer) +
-                                                     " failed: " + pc->error);
-    if (!(pc->ready && pc->q.empty())) {
-      // the channel's communicator is still being built: queue behind it, in order
-      TORCH_CHECK(!capturing_on(ds.device), "pdcc: the first send/recv between two ranks cannot be captured into a "
-                  "graph (it builds their communicator): run one exchange before capturing");
-      c10::hip::HIPGuardMasqueradingAsCUDA g((c10::DeviceIndex)ds.device);
-      auto gate = std::make_shared<Gate>();
-      PDCC_HIP(hipEventCreateWithFlags(&gate->ev, hipEventDisableTiming));
-      hipEvent_t after = nullptr;
-      PDCC_HIP(hipEventCreateWithFlags(&after, hipEventDisableTiming));
-      PDCC_HIP(hipEventRecord(after, current_stream(ds.device)));
-      pc->q.push_back({is_send, t, w, after, gate});
-      auto work = c10::make_intrusive<WorkMI355X>(
-          rank_, is_send ? c10d::OpType::SEND : c10d::OpType::RECV, op_seq_.load(), std::vector<at::Tensor>{t},
-          c10::Device(c10::kCUDA, (c10::DeviceIndex)ds.device), gate->ev, pc->stream, health_, cfg_.blocking_wait,
-          to, nullptr, nullptr);
-      work->set_gate(gate);
-      if (!pc->started) {
-        pc->started = true;
-        // self-contained (copies only): the thread may outlive a group destroyed meanwhile
-        const int lo = std::min(rank_, peer), hi = std::max(rank_, peer);
-        std::thread([pc, store = store_, key = "pdcc/p2p/" + std::to_string(lo) + ":" + std::to_string(hi),
-                     prank = rank_ == lo ? 0 : 1, dev = ds.device, pi,
-                     init_ms = cfg_.rccl_nonblocking ? rccl_opts().init_timeout_ms : int64_t{0}] {
-          pair_builder(pc, store, key, prank, dev, pi, init_ms);
-        }).detach();
-      }
-      if (cfg_.watchdog_ms > 0) {
-        std::lock_guard<std::mutex> wl(wd_mu_);
-        inflight_.emplace_back(work);
-      }
-      record(cname, "rccl_pair_deferred", t.nbytes(), t0);
-      return work;
-    }
-  }
-  auto work = gpu_run(cname, ds, {t, w}, {t}, to, [&](hipStream_t s) {
-    if (is_send) PDCC_NCCLC(pc->comm->get(), ncclSend(w.data_ptr(), w.nbytes(), ncclUint8, pi, pc->comm->get(), s));
-    else PDCC_NCCLC(pc->comm->get(), ncclRecv(w.data_ptr(), w.nbytes(), ncclUint8, pi, pc->comm->get(), s));
-    if (!is_send && !w.is_same(t)) t.copy_(w);
-  }, nullptr, &pc->stream);
-  record(cname, "rccl_pair", t.nbytes(), t0);
-  return work;
-}
-
-// Builder thread of a PairChan: create the 2-rank communicator (blocking on the peer),
-// then enqueue the ops that queued up meanwhile, in order, each after its caller's
-// stream point, and open their gates; then mark the channel ready.
-void ProcessGroupMI355X::pair_builder(std::shared_ptr<PairChan> pc, c10::intrusive_ptr<c10d::Store> store,
-                                      std::string key, int prank, int dev, int pi, int64_t init_ms) {
-  std::string err;
-  try {
-    PDCC_HIP(hipSetDevice(dev));
-    const auto t0 = std::chrono::steady_clock::now();
-    RcclOpts o;
-    o.init_timeout_ms = init_ms;  // the peer may never post its side: bounded
-    o.nonblocking = init_ms > 0;
-    auto c = std::make_shared<RcclComm>(store, key, prank, 2, dev, o);
-    std::lock_guard<std::mutex> lk(pc->mu);
-    pc->comm = c;
-    pc->init_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-  } catch (const std::exception& e) {
-    err = e.what();
-  }
-  for (;;) {
-    PairChan::Op op;
-    {
-      std::lock_guard<std::mutex> lk(pc->mu);
-      if (!err.empty()) pc->error = err;
-      if (pc->q.empty()) {
-        pc->ready = pc->error.empty();
-        return;
-      }
-      op = std::move(pc->q.front());
-      pc->q.pop_front();
-    }
-    try {
-      if (!err.empty()) throw std::runtime_error(err);
-      c10::hip::HIPStreamGuardMasqueradingAsCUDA sg(pc->stream);
-      const hipStream_t s = pc->stream.stream();
-      PDCC_HIP(hipStreamWaitEvent(s, op.after, 0));
-      if (op.is_send) PDCC_NCCLC(pc->comm->get(), ncclSend(op.w.data_ptr(), op.w.nbytes(), ncclUint8, pi, pc->comm->get(), s));
-      else PDCC_NCCLC(pc->comm->get(), ncclRecv(op.w.data_ptr(), op.w.nbytes(), ncclUint8, pi, pc->comm->get(), s));
-      if (!op.is_send && !op.w.is_same(op.t)) op.t.copy_(op.w);
-      for (const at::Tensor* x : {&op.t, &op.w})
-        c10::hip::HIPCachingAllocatorMasqueradingAsCUDA::recordStreamMasqueradingAsCUDA(x->storage().data_ptr(),
-                                                                                         pc->stream);
-      PDCC_HIP(hipEventRecord(op.gate->ev, s));
-      op.gate->state.store(1, std::memory_order_release);
-    } catch (const std::exception& e) {
-      if (err.empty()) err = e.what();
-      std::lock_guard<std::mutex> lk(op.gate->mu);
-      op.gate->error = std::string("send/recv channel setup failed: ") + e.what();
-      op.gate->state.store(-1, std::memory_order_release);
-    }
-    (void)hipEventDestroy(op.after);
-  }
-}
-
-void ProcessGroupMI355X::startCoalescing() {
-  coalescing_ = true;
-  coalesced_cpu_.clear();
-  coalesced_.clear();
-  coalesced_tensors_.clear();
-  coalesced_ds_ = nullptr;
-}
-
-c10::intrusive_ptr<c10d::Work> ProcessGroupMI355X::endCoalescing() {
-  coalescing_ = false;
-  DeviceState* ds = coalesced_ds_;
-  if (!ds) {
-    std::lock_guard<std::mutex> lk(init_mu_);
-    if (devs_.size() == 1) ds = devs_.begin()->second.get();
-  }
-  // CPU p2p posted inside the batch runs on the worker threads: wait for all of
-  // it so the returned work really covers the batch (all ops are already posted,
-  // so this cannot deadlock the exchange)
-  auto cpu_works = std::move(coalesced_cpu_);
-  coalesced_cpu_.clear();
-  for (auto& w : cpu_works) w->wait();
-  if (!ds) return cpu_done(Coll::SEND, {});
-  // nothing was batched (torch's fast path issued one coalesced collective instead): a synchronous
-  // one already ran on the caller's stream, so there is nothing to order -- an async one ran on the
-  // comm stream and the returned work must cover it (below)
-  if (coalesced_.empty() && !op_async_) {
-    coalesced_tensors_.clear();
-    coalesced_ds_ = nullptr;
-    return cpu_done(Coll::SEND, {});
-  }
-  auto fns = std::move(coalesced_);
-  auto keep = std::move(coalesced_tensors_);
-  coalesced_.clear();
-  coalesced_tensors_.clear();
-  coalesced_ds_ = nullptr;
-  return gpu_run(Coll::SEND, *ds, keep, {}, timeout_, [&](hipStream_t s) {
-    if (fns.empty()) return;
-    // the batch runs on the group's communicator (rccl() made it when the first op was posted)
-    RcclComm::Issue og(*ds->rccl, s, capturing(s));
-    PDCC_NCCL(ncclGroupStart());
-    for (auto& f : fns) f(s);
-    PDCC_NCCLC(ds->rccl->get(), ncclGroupEnd());
-    for (size_t i = 0; i + 1 < keep.size(); i += 2)
-      if (!keep[i].is_same(keep[i + 1])) keep[i].copy_(keep[i + 1]);
-  });
+  };
+  std::vector<at::Tensor> keep = wi;
+  keep.insert(keep.end(), wo.begin(), wo.end());
+  return issue_collective(
+      {Coll::ALLTOALL, -1, flat ? kLayoutFlat : kLayoutList, chunk, total, a0, ds.rccl_ok, ipc_can, t0, to}, ds, tune,
+      [&](Algo a, hipStream_t s) { return enqueue_alltoall(a, wi, wo, equal, ds, s, to); },
+      [&] {
+        for (size_t i = 0; i < outs.size(); ++i)
+          if (!wo[i].is_same(outs[i])) outs[i].copy_(wo[i]);
+      },
+      std::move(keep), outs);
 }
 
 }  // namespace pdcc

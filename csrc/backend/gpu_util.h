@@ -2,6 +2,7 @@
 //   gpu_setup.cpp   device state, topology, communicators, IPC self-test
 //   autotune.cpp    the online engine race and its persisted decisions
 //   gpu_ops.cpp     the engines and the collectives built on them
+//   gpu_p2p.cpp     point-to-point (pair channels, host-staged) and batch coalescing
 #pragma once
 #include <ATen/hip/HIPContext.h>
 #include <ATen/hip/impl/HIPCachingAllocatorMasqueradingAsCUDA.h>
@@ -79,6 +80,25 @@ inline bool nccl_op(RedOpType op, at::ScalarType t, ncclRedOp_t& o) {
     case RedOpType::AVG: o = ncclAvg; return !b;
     default: return false;  // BAND/BOR/BXOR: no RCCL op (IPC kernels or the host path)
   }
+}
+
+// One reduction as each engine needs it described: the IPC kernels' dtype / op (`kok`: they have
+// it), RCCL's (`nok`), and the c10d op for the host transport and the messages
+struct RedSpec {
+  RedOpType op = RedOpType::SUM;
+  kern::DType kd{};
+  kern::RedOp ko{};
+  ncclDataType_t nd = ncclFloat32;
+  ncclRedOp_t no = ncclSum;
+  bool kok = false, nok = false;
+};
+
+inline RedSpec red_spec(at::ScalarType t, RedOpType op) {
+  RedSpec r;
+  r.op = op;
+  r.kok = kern_dtype(t, r.kd) && kern_op(op, r.ko) && kern::supports(r.kd, r.ko);
+  r.nok = nccl_dtype(t, r.nd) && nccl_op(op, t, r.no);
+  return r;
 }
 
 inline const char* op_name(int op) {

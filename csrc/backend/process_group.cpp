@@ -568,8 +568,6 @@ void ProcessGroupMI355X::record_setup(const std::string& key, std::chrono::stead
 void ProcessGroupMI355X::record(Coll c, const char* algo, size_t bytes, std::chrono::steady_clock::time_point t0) {
   const double ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
   std::lock_guard<std::mutex> lk(stats_mu_);
-  if (sdma_ran_) algo = "ipc_sdma";  // (the engine job ran on the copy engines: sdma_run)
-  sdma_ran_ = false;
   PendingRec p{++rec_id_, c, algo, bytes, ms, {}};
   // an IPC op whose zero-copy attempts all ran zero-copy is counted as "<algo>_zc" -- decided from
   // the outcome (a gated attempt's exchange may still be running: the record waits in pending_)

@@ -326,6 +326,10 @@ struct OpStats {
   double host_ms = 0.0;
 };
 
+namespace gpu {
+struct RedSpec;  // one reduction as each engine describes it (gpu_util.h)
+}
+
 class ProcessGroupMI355X : public c10d::Backend {
  public:
   ProcessGroupMI355X(const c10::intrusive_ptr<c10d::Store>& store, int rank, int size,
@@ -480,9 +484,23 @@ class ProcessGroupMI355X : public c10d::Backend {
                                            std::vector<at::Tensor> outputs, std::chrono::milliseconds timeout,
                                            std::function<void(hipStream_t)> job, std::shared_ptr<IpcComm> ipcp);
   c10::intrusive_ptr<c10d::Work> cpu_done(Coll c, std::vector<at::Tensor> outputs);
-  // GPU tensors through the host transport (D2H, shm, H2D); synchronous
-  c10::intrusive_ptr<c10d::Work> host_staged(Coll c, std::vector<at::Tensor> outputs,
-                                             const std::function<void()>& fn);
+  struct Issue {  // one call's tune-key slots and static choice, as its front-end hands them on
+    Coll coll;
+    int key_dtype, key_op;     // (-1: none; copies: the list layout)
+    size_t bytes, stat_bytes;  // per-rank payload (the key's size); what stats() counts
+    Algo a0;                   // choose()'s static engine
+    bool rccl_can, ipc_can;
+    std::chrono::steady_clock::time_point t0;
+    std::chrono::milliseconds to;
+  };
+  // The life of one GPU collective after its front-end has prepared the buffers (gpu_ops.cpp):
+  // decide() the engine (a new key races through `tune`), `enqueue(algo, stream)` + `copy_back()`
+  // (+ the coalesced unpack) as one job, record() under the label `enqueue` returned
+  template <class Tune, class Enqueue, class CopyBack>
+  c10::intrusive_ptr<c10d::Work> issue_collective(const Issue& c, DeviceState& ds, Tune&& tune, Enqueue&& enqueue,
+                                                  CopyBack&& copy_back, std::vector<at::Tensor> keep_alive,
+                                                  std::vector<at::Tensor> outputs,
+                                                  const std::shared_ptr<const Coalesced>& co = nullptr);
   void ipc_chunked(IpcComm& ic, kern::IpcCall call, size_t per_call_max, hipStream_t s);
   // Zero-copy IPC call (PDCC_IPC_ZC): every rank's `zbuf` (`zlen` readable bytes) is
   // mapped into its peers and read in place. Runs the leading whole `unit`s of
@@ -545,6 +563,7 @@ class ProcessGroupMI355X : public c10d::Backend {
                                                     std::shared_ptr<const Coalesced> co = nullptr);
   c10::intrusive_ptr<c10d::Work> gpu_alltoall(std::vector<at::Tensor>& outs, std::vector<at::Tensor>& ins,
                                               bool equal_split, std::chrono::milliseconds to);
+  // point-to-point and batch coalescing (gpu_p2p.cpp)
   c10::intrusive_ptr<c10d::Work> gpu_p2p(at::Tensor& t, int peer, bool is_send, std::chrono::milliseconds to);
   c10::intrusive_ptr<c10d::Work> host_p2p(at::Tensor& t, int peer, bool is_send, std::chrono::milliseconds to);
 
@@ -624,6 +643,8 @@ class ProcessGroupMI355X : public c10d::Backend {
  private:
   // payload size the LL protocol takes (PDCC_IPC_LL_MAX, at most kern::kLLMaxBytes)
   bool bytes_in_ll_range(size_t bytes) const;
+  // the IPC engine serves this payload with an LL kernel (what every enqueue_* asks)
+  bool ll_size(const DeviceState& ds, size_t bytes) const { return ds.ll_ok && bytes_in_ll_range(bytes); }
   bool ll_call(const DeviceState& ds, size_t bytes) const;
 
  private:
@@ -631,7 +652,7 @@ class ProcessGroupMI355X : public c10d::Backend {
   int (*roctx_push_)(const char*) = nullptr;
   int (*roctx_pop_)() = nullptr;
 
-  // online autotuner (gpu_ops.cpp)
+  // online autotuner (autotune.cpp)
   struct TuneEntry {
     Algo ref = Algo::RCCL;
     double rccl_us = 0, ipc_us = 0, push_us = 0, wide_us = 0, ipc_wide_us = 0, staged_us = 0, dyn_us = 0, sdma_us = 0;
@@ -682,28 +703,28 @@ class ProcessGroupMI355X : public c10d::Backend {
                 const std::function<void(size_t)>& run, const std::function<bool(size_t, size_t)>& same,
                 const std::function<bool()>& ref_check = nullptr);
 
-  // one engine's enqueue of each collective on stream `s` (HOST: synchronous)
-  void enqueue_allreduce(Algo a, const at::Tensor& w, kern::DType kd, kern::RedOp ko, ncclDataType_t nd,
-                         ncclRedOp_t no, bool nok, c10d::ReduceOp::RedOpType op, int root, bool rooted,
-                         DeviceState& ds, hipStream_t s, std::chrono::milliseconds to);
-  void enqueue_broadcast(Algo a, const at::Tensor& w, int root, DeviceState& ds, hipStream_t s,
-                         std::chrono::milliseconds to);
-  void enqueue_allgather(Algo a, const at::Tensor& wi, const std::vector<at::Tensor>& wo, int root, bool rooted,
-                         DeviceState& ds, hipStream_t s, std::chrono::milliseconds to);
-  void enqueue_scatter(Algo a, const std::vector<at::Tensor>& wi, const at::Tensor& wo, int root, DeviceState& ds,
-                       hipStream_t s, std::chrono::milliseconds to);
-  void enqueue_reduce_scatter(Algo a, const std::vector<at::Tensor>& wi, const at::Tensor& wo, kern::DType kd,
-                              kern::RedOp ko, ncclDataType_t nd, ncclRedOp_t no, bool nok,
-                              c10d::ReduceOp::RedOpType op, DeviceState& ds, hipStream_t s,
-                              std::chrono::milliseconds to);
-  void enqueue_alltoall(Algo a, const std::vector<at::Tensor>& wi, const std::vector<at::Tensor>& wo, bool equal,
-                        DeviceState& ds, hipStream_t s, std::chrono::milliseconds to);
+  // one engine's enqueue of each collective on stream `s` (HOST: synchronous); returns the label
+  // of the protocol it enqueued, named where it is picked (what record() counts the call under)
+  const char* enqueue_allreduce(Algo a, const at::Tensor& w, const gpu::RedSpec& red, int root, bool rooted,
+                                DeviceState& ds, hipStream_t s, std::chrono::milliseconds to);
+  const char* enqueue_broadcast(Algo a, const at::Tensor& w, int root, DeviceState& ds, hipStream_t s,
+                                std::chrono::milliseconds to);
+  const char* enqueue_allgather(Algo a, const at::Tensor& wi, const std::vector<at::Tensor>& wo, int root,
+                                bool rooted, DeviceState& ds, hipStream_t s, std::chrono::milliseconds to);
+  const char* enqueue_scatter(Algo a, const std::vector<at::Tensor>& wi, const at::Tensor& wo, int root,
+                              DeviceState& ds, hipStream_t s, std::chrono::milliseconds to);
+  const char* enqueue_reduce_scatter(Algo a, const std::vector<at::Tensor>& wi, const at::Tensor& wo,
+                                     const gpu::RedSpec& red, DeviceState& ds, hipStream_t s,
+                                     std::chrono::milliseconds to);
+  const char* enqueue_alltoall(Algo a, const std::vector<at::Tensor>& wi, const std::vector<at::Tensor>& wo,
+                               bool equal, DeviceState& ds, hipStream_t s, std::chrono::milliseconds to);
 
   HostProf hp_;  // caller thread only
   std::mutex stats_mu_;
   std::map<std::string, OpStats> stats_;
   std::string last_algo_;
-  // Engine labels record what ran, not what was intended. The zero-copy attempts of the op being
+  // Engine labels record what ran, not what was intended: the protocol name comes from the enqueue_*
+  // that picked it. The zero-copy attempts of the op being
   // issued (ipc_run appends, gpu_issue starts a fresh list, record() takes it) and the records
   // whose gated attempts are still pending: a record is counted under "<coll>/<algo>_zc" or
   // "<coll>/<algo>" once every attempt's outcome is in (non-blocking at each record(), blocking
@@ -717,7 +738,6 @@ class ProcessGroupMI355X : public c10d::Backend {
     std::vector<ZcPart> parts;
   };
   std::vector<ZcPart> zc_parts_;
-  bool sdma_ran_ = false;  // the op being issued ran on the copy engines (record() labels it ipc_sdma)
   std::deque<PendingRec> pending_;
   uint64_t rec_id_ = 0;
   uint64_t zc_ran_calls_ = 0, zc_staged_calls_ = 0;

@@ -2224,3 +2224,123 @@ def ll_unaligned_probe(rank, size, device="cuda"):
         ok[f"bcast_offset/{n}"] = bool(torch.equal(v, torch.arange(n, device=d, dtype=torch.float32) * 3)) and \
             float(buf[0]) == -5.0
     return {"ok": ok, "algos": sorted(algos)}
+
+
+def engine_label_matrix(rank, size, device="cuda", algos=("ipc",), payloads=(8 << 10,), wide=False):
+    """Every GPU collective x engine (set_algo, identically on every rank) x payload: the engine label
+    the call recorded (last_algo) and whether its result is exact against closed-form fills. `payloads`
+    are the bytes the engine keys on (the tensor of all_reduce / reduce / broadcast, one rank's chunk of
+    the others); rooted collectives use the last rank as root. Returns {case: [label, ok]}."""
+    import torch
+    import torch.distributed as dist
+
+    from pytorch_distributed_collective_communication_amd.parallel import backend as be
+
+    d = _dev(device)
+    b = be.native_backend(None, "cuda")
+    b.set_ipc_thresholds(16 << 10, -1, -1)  # 1-shot up to 16 KiB
+    root = size - 1
+    tri = size * (size + 1) // 2
+    out = {}
+
+    def full(n, v):
+        return torch.full((n,), float(v), device=d)
+
+    def sep(n, v=None):  # a tensor that is never adjacent to the next one (a list of them is never flat)
+        t = torch.empty(n + 64, device=d)[:n]
+        return t if v is None else t.fill_(float(v))
+
+    def eq(t, v):
+        return bool(torch.all(t == float(v)))
+
+    def cases(n):
+        def all_reduce(**kw):
+            x = full(n, rank + 1)
+            w = dist.all_reduce(x, **kw)
+            if w is not None:
+                w.wait()
+            return eq(x, tri)
+
+        def reduce():
+            x = full(n, rank + 1)
+            dist.reduce(x, dst=root)
+            return eq(x, tri if rank == root else rank + 1)
+
+        def broadcast():
+            ramp = torch.arange(n, device=d, dtype=torch.float32) % 251
+            x = ramp.clone() if rank == root else full(n, -1)
+            dist.broadcast(x, src=root)
+            return bool(torch.equal(x, ramp))
+
+        def all_gather_list():
+            lst = [sep(n) for _ in range(size)]
+            dist.all_gather(lst, full(n, rank + 1))
+            return all(eq(t, q + 1) for q, t in enumerate(lst))
+
+        def all_gather_into_tensor():
+            o = full(n * size, -1)
+            dist.all_gather_into_tensor(o, full(n, rank + 1))
+            return all(eq(t, q + 1) for q, t in enumerate(o.chunk(size)))
+
+        def gather():
+            lst = [sep(n, -1) for _ in range(size)]
+            dist.gather(full(n, rank + 1), gather_list=lst if rank == root else None, dst=root)
+            return all(eq(t, q + 1 if rank == root else -1) for q, t in enumerate(lst))
+
+        def scatter(flat):
+            x = torch.arange(size, device=d, dtype=torch.float32).repeat_interleave(n) + 10
+            lst = list(x.chunk(size)) if flat else [sep(n, q + 10) for q in range(size)]
+            o = full(n, -1)
+            dist.scatter(o, scatter_list=lst if rank == root else None, src=root)
+            return eq(o, rank + 10)
+
+        def reduce_scatter_list():
+            o = full(n, -1)
+            dist.reduce_scatter(o, [sep(n, 10 * q + rank) for q in range(size)])
+            return eq(o, 10 * rank * size + size * (size - 1) // 2)
+
+        def reduce_scatter_tensor():
+            x = torch.arange(size, device=d, dtype=torch.float32).repeat_interleave(n) * 10 + rank
+            o = full(n, -1)
+            dist.reduce_scatter_tensor(o, x)
+            return eq(o, 10 * rank * size + size * (size - 1) // 2)
+
+        def all_to_all_single():
+            x = torch.arange(size, device=d, dtype=torch.float32).repeat_interleave(n) + 100 * rank
+            o = full(n * size, -1)
+            dist.all_to_all_single(o, x)
+            return all(eq(t, 100 * q + rank) for q, t in enumerate(o.chunk(size)))
+
+        def all_to_all_list():
+            outs = [sep(n, -1) for _ in range(size)]
+            dist.all_to_all(outs, [sep(n, 100 * rank + q) for q in range(size)])
+            return all(eq(t, 100 * q + rank) for q, t in enumerate(outs))
+
+        def all_reduce_coalesced():
+            xs = [full(n, rank + 1), full(n, 2 * (rank + 1))]
+            with dist._coalescing_manager(device=d, async_ops=False):
+                for x in xs:
+                    dist.all_reduce(x)
+            return eq(xs[0], tri) and eq(xs[1], 2 * tri)
+
+        return (("all_reduce", all_reduce), ("reduce", reduce), ("broadcast", broadcast),
+                ("all_gather_list", all_gather_list), ("all_gather_into_tensor", all_gather_into_tensor),
+                ("gather", gather), ("scatter_chunks", lambda: scatter(True)),
+                ("scatter_separate", lambda: scatter(False)), ("reduce_scatter_list", reduce_scatter_list),
+                ("reduce_scatter_tensor", reduce_scatter_tensor), ("all_to_all_single", all_to_all_single),
+                ("all_to_all_list", all_to_all_list), ("all_reduce_async", lambda: all_reduce(async_op=True)),
+                ("all_reduce_coalesced", all_reduce_coalesced))
+
+    for algo in algos:
+        b.set_algo(algo)
+        for nbytes in payloads:
+            for name, fn in cases(nbytes // 4):
+                ok = fn()
+                out[f"{algo}/{nbytes}/{name}"] = [b.last_algo(), ok]
+    if wide:
+        b.set_algo("rccl_wide")
+        ok = cases(payloads[0] // 4)[0][1]()
+        out[f"rccl_wide/{payloads[0]}/all_reduce"] = [b.last_algo(), ok]
+    b.set_algo("auto")
+    dist.barrier()
+    return out

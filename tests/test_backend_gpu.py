@@ -7,6 +7,9 @@
   2-shot protocols, chunking, parity double-buffering) and the host-staged
   fallback, with the reference's golden outputs as the oracle.
 """
+import json
+import os
+
 import pytest
 import torch
 
@@ -773,3 +776,41 @@ def test_ll_collectives_on_views_at_4_byte_offsets(world):
         assert all(r["ok"].values()), r
         assert r["algos"] == ["ipc_ll"], r
 
+
+
+_LABEL_ALGOS = ("ipc", "ipc_push", "ipc_dyn", "ipc_wide", "ipc_staged", "ipc_sdma", "host")
+# one payload per protocol class under the thresholds below: LL, 1-shot / copy, 2-shot / zero-copy in whole
+# rows of W x 4096 B, and a zero-copy body plus a staged rest
+_LABEL_PAYLOADS = (256, 8 << 10, 128 << 10, (128 << 10) + (4 << 10))
+_LABEL_GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "engine_labels.json")
+
+
+def engine_label_runs():
+    """{launch: [per-rank {case: [label, exact]}]}: two ranks sharing the GPU with every engine forced in
+    turn, and a world of 1 on RCCL under both PDCC_LIST_GATHER modes."""
+    shared = {"PDCC_AUTOTUNE": "0", "PDCC_IPC_ZC_ASYNC": "0", "PDCC_IPC_ZC_MIN": "64K", "PDCC_IPC_LL_MAX": "1K"}
+    runs = {"shared_w2": _gpu_launch(W.engine_label_matrix, 2, args=("cuda", _LABEL_ALGOS, _LABEL_PAYLOADS),
+                                     env=shared, timeout_s=120)}
+    for mode in ("p2p", "staged"):
+        env = {"PDCC_WORLD1_LOCAL": "0", "PDCC_ALGO": "rccl", "PDCC_LIST_GATHER": mode}
+        runs[f"world1_{mode}"] = _gpu_launch(W.engine_label_matrix, 1, args=("cuda", ("rccl",), (8 << 10,), True),
+                                             env=env)
+    return json.loads(json.dumps(runs))
+
+
+def test_engine_label_matrix():
+    # the engine label of every collective x engine x protocol class, as recorded by the code that picks
+    # the protocol, equals what the hand-written per-collective label code gave before the front-ends were
+    # folded onto one issue path (tests/golden/engine_labels.json) -- and every result is exact
+    with open(_LABEL_GOLDEN) as f:
+        golden = json.load(f)
+    runs = engine_label_runs()
+    assert sorted(runs) == sorted(golden)
+    for launch_name, ranks in runs.items():
+        assert len(ranks) == len(golden[launch_name])
+        for r, got in enumerate(ranks):
+            bad = {k: v for k, v in got.items() if not v[1]}
+            assert not bad, (launch_name, r, bad)
+            diff = {k: (got.get(k), golden[launch_name][r].get(k))
+                    for k in set(got) | set(golden[launch_name][r]) if got.get(k) != golden[launch_name][r].get(k)}
+            assert not diff, (launch_name, r, diff)
