@@ -137,7 +137,7 @@ size_t ProcessGroupMI355X::ipc_zero_copy(DeviceState& ds, kern::IpcCall call, co
   IpcComm& ic = ds.ipc ? *ds.ipc : ipc(ds);
   std::vector<char*> ptrs;
   if (!zc_map(ds, zbuf, zlen, capturing(s), selftest, ptrs)) return 0;
-  if (call.coll == kern::IpcColl::REDUCE_2SHOT || call.coll == kern::IpcColl::ALLREDUCE_PUSH) {
+  if (kern::coll_traits(call.coll).zc_stages) {
     // the rooted reduce stages its reduced tiles, the push all-reduce receives its owned
     // tiles in staging: chunks of at most the staging cap
     const size_t chunk = std::max(unit, ic.chunk_cap() / unit * unit);
@@ -180,18 +180,16 @@ void ProcessGroupMI355X::ipc_run(DeviceState& ds, kern::IpcCall call, const void
   }
   if (body == call.bytes) return;
   kern::IpcCall rest = call;
-  if (rest.coll == kern::IpcColl::ALLREDUCE_PUSH) rest.coll = kern::IpcColl::ALLREDUCE_2SHOT;  // zero-copy only
-  rest.dyn = 0;                                                                                 // (likewise)
+  rest.coll = kern::staged_twin(rest.coll);  // (a zero-copy-only protocol)
+  rest.dyn = 0;                              // (likewise)
   rest.bytes = call.bytes - body;
   for (int k = 0; k < kern::kMaxRanks; ++k) {
     if (call.in[k]) rest.in[k] = static_cast<const char*>(call.in[k]) + body;
     if (call.out[k]) rest.out[k] = static_cast<char*>(call.out[k]) + body;
   }
-  if (body && rest.bytes <= cfg_.ipc_1shot_max) {  // the rest of a zero-copy 2-shot is short
-    if (rest.coll == kern::IpcColl::ALLREDUCE_2SHOT) rest.coll = kern::IpcColl::ALLREDUCE_1SHOT;
-    if (rest.coll == kern::IpcColl::REDUCE_2SHOT) rest.coll = kern::IpcColl::REDUCE_1SHOT;
-    if (rest.coll == kern::IpcColl::BROADCAST_2SHOT) rest.coll = kern::IpcColl::BROADCAST_1SHOT;
-  }
+  const kern::IpcColl one_shot = kern::coll_traits(rest.coll).one_shot;
+  if (body && rest.bytes <= cfg_.ipc_1shot_max && one_shot != kern::IpcColl::kCount)
+    rest.coll = one_shot;  // the rest of a zero-copy 2-shot is short
   ipc_chunked(ipc(ds), rest, per_call_max, s);
 }
 
@@ -229,10 +227,7 @@ bool ProcessGroupMI355X::sdma_run(
                copies.end());
   // (one pull stays one copy: splitting a 64 MiB broadcast pull over three streams took 296 us against
   // 129 us whole, ranks sharing one MI355X -- profiles/r6/sdma/)
-  kern::IpcCall bar{};
-  bar.coll = kern::IpcColl::BARRIER;
-  bar.dtype = kern::DType::U8;
-  bar.op = kern::RedOp::COPY;
+  const kern::IpcCall bar = copy_call(kern::IpcColl::BARRIER, 0);
   ic.launch(bar, s);  // arrival
   const int nside = std::min<int>(cfg_.sdma_streams, (int)copies.size() - 1);
   if (nside <= 0) {
@@ -427,11 +422,13 @@ const char* ProcessGroupMI355X::enqueue_allreduce(Algo a, const at::Tensor& w, c
   const StagedOnly staged_only(staged_only_, a == Algo::IPC_STAGED);  // (read by ipc_run)
   if (is_ipc(a)) {
     IpcComm& ic = ipc(ds);
-    kern::IpcCall c{};
     const bool one_shot = w.nbytes() <= cfg_.ipc_1shot_max;
     const char* label = one_shot ? "ipc_1shot" : a == Algo::IPC_WIDE ? "ipc_2shot_wide" : "ipc_2shot";
-    c.coll = rooted ? (one_shot ? kern::IpcColl::REDUCE_1SHOT : kern::IpcColl::REDUCE_2SHOT)
-                    : (one_shot ? kern::IpcColl::ALLREDUCE_1SHOT : kern::IpcColl::ALLREDUCE_2SHOT);
+    kern::IpcCall c = reduce_call(
+        rooted ? (one_shot ? kern::IpcColl::REDUCE_1SHOT : kern::IpcColl::REDUCE_2SHOT)
+               : (one_shot ? kern::IpcColl::ALLREDUCE_1SHOT : kern::IpcColl::ALLREDUCE_2SHOT),
+        red.kd, red.ko, size_, w.nbytes());
+    c.root = root;
     if (a == Algo::IPC_WIDE) c.grid_cap = cfg_.ipc_wide_grid;  // (shared devices: capped in launch_view)
     if (a == Algo::IPC_PUSH && c.coll == kern::IpcColl::ALLREDUCE_2SHOT) {
       c.coll = kern::IpcColl::ALLREDUCE_PUSH;
@@ -443,20 +440,14 @@ const char* ProcessGroupMI355X::enqueue_allreduce(Algo a, const at::Tensor& w, c
     }
     c.dyn_min_rows = cfg_.ipc_dyn_min_rows;
     if (ll_size(ds, w.nbytes())) {  // small (all-)reduce: flag-tagged pushes, no staging copy, no barrier
-      c.coll = rooted ? kern::IpcColl::REDUCE_LL : kern::IpcColl::ALLREDUCE_LL;
+      c.coll = kern::coll_traits(c.coll).ll_twin;
       label = "ipc_ll";
     }
-    c.dtype = red.kd;
-    c.op = red.ko;
-    c.root = root;
-    c.avg_div = size_;
-    c.bytes = w.nbytes();
     c.in[0] = w.data_ptr();
     c.out[0] = w.data_ptr();
     // 2-shot reads the peers' tensors in place (all-reduce: reduced in place too;
     // rooted reduce: into staging, so non-root tensors stay untouched)
-    if (c.coll == kern::IpcColl::ALLREDUCE_2SHOT || c.coll == kern::IpcColl::REDUCE_2SHOT ||
-        c.coll == kern::IpcColl::ALLREDUCE_PUSH)
+    if (kern::coll_traits(c.coll).zc_unit == kern::ZcUnit::ROW)
       ipc_run(ds, c, w.data_ptr(), w.nbytes(), (size_t)size_ * kern::kTileBytes, ic.chunk_cap(), s);
     else
       ipc_chunked(ic, c, ic.chunk_cap(), s);
@@ -494,16 +485,12 @@ const char* ProcessGroupMI355X::enqueue_broadcast(Algo a, const at::Tensor& w, i
   }
   if (is_ipc(a)) {
     IpcComm& ic = ipc(ds);
-    kern::IpcCall c{};
-    c.coll = bytes <= cfg_.ipc_1shot_max ? kern::IpcColl::BROADCAST_1SHOT : kern::IpcColl::BROADCAST_2SHOT;
-    c.dtype = kern::DType::U8;
-    c.op = kern::RedOp::COPY;
-    c.root = root;
-    c.bytes = bytes;
+    kern::IpcCall c = copy_call(
+        bytes <= cfg_.ipc_1shot_max ? kern::IpcColl::BROADCAST_1SHOT : kern::IpcColl::BROADCAST_2SHOT, bytes, root);
     c.in[0] = w.data_ptr();
     c.out[0] = w.data_ptr();
     if (ll_size(ds, bytes)) {  // small: the root pushes flag-tagged words
-      c.coll = kern::IpcColl::BROADCAST_LL;
+      c.coll = kern::coll_traits(c.coll).ll_twin;
       ic.launch(c, s);
       return "ipc_ll";
     }
@@ -544,17 +531,12 @@ const char* ProcessGroupMI355X::enqueue_allgather(Algo a, const at::Tensor& wi, 
   }
   if (is_ipc(a)) {
     IpcComm& ic = ipc(ds);
-    kern::IpcCall c{};
-    c.coll = rooted ? kern::IpcColl::GATHER : kern::IpcColl::ALLGATHER;
-    c.dtype = kern::DType::U8;
-    c.op = kern::RedOp::COPY;
-    c.root = root;
-    c.bytes = bytes;
+    kern::IpcCall c = copy_call(rooted ? kern::IpcColl::GATHER : kern::IpcColl::ALLGATHER, bytes, root);
     c.in[0] = wi.data_ptr();
     if (receiver)
       for (int r = 0; r < size_; ++r) c.out[r] = wo[r].data_ptr();
     if (ll_size(ds, bytes)) {  // small: flag-tagged pushes, no staging copy, no barrier
-      c.coll = rooted ? kern::IpcColl::GATHER_LL : kern::IpcColl::ALLGATHER_LL;
+      c.coll = kern::coll_traits(c.coll).ll_twin;
       ic.launch(c, s);
       return "ipc_ll";
     }
@@ -626,18 +608,13 @@ const char* ProcessGroupMI355X::enqueue_scatter(Algo a, const std::vector<at::Te
   }
   if (is_ipc(a)) {
     IpcComm& ic = ipc(ds);
-    kern::IpcCall c{};
-    c.coll = kern::IpcColl::SCATTER;
-    c.dtype = kern::DType::U8;
-    c.op = kern::RedOp::COPY;
-    c.root = root;
-    c.bytes = bytes;
+    kern::IpcCall c = copy_call(kern::IpcColl::SCATTER, bytes, root);
     c.zstride = bytes;
     if (rank_ == root)
       for (int r = 0; r < size_; ++r) c.in[r] = wi[r].data_ptr();
     c.out[0] = wo.data_ptr();
     if (ll_size(ds, bytes)) {  // small: the root pushes chunk q to rank q
-      c.coll = kern::IpcColl::SCATTER_LL;
+      c.coll = kern::coll_traits(c.coll).ll_twin;
       ic.launch(c, s);
       return "ipc_ll";
     }
@@ -682,17 +659,12 @@ const char* ProcessGroupMI355X::enqueue_reduce_scatter(Algo a, const std::vector
   const size_t bytes = wo.nbytes();
   if (is_ipc(a)) {
     IpcComm& ic = ipc(ds);
-    kern::IpcCall c{};
-    c.coll = kern::IpcColl::REDUCE_SCATTER;
-    c.dtype = red.kd;
-    c.op = red.ko;
-    c.avg_div = size_;
-    c.bytes = bytes;
+    kern::IpcCall c = reduce_call(kern::IpcColl::REDUCE_SCATTER, red.kd, red.ko, size_, bytes);
     c.zstride = bytes;
     for (int r = 0; r < size_; ++r) c.in[r] = wi[r].data_ptr();
     c.out[0] = wo.data_ptr();
     if (ll_size(ds, bytes)) {  // small: chunk q pushed to rank q, reduced there
-      c.coll = kern::IpcColl::REDUCE_SCATTER_LL;
+      c.coll = kern::coll_traits(c.coll).ll_twin;
       ic.launch(c, s);
       return "ipc_ll";
     }
@@ -754,18 +726,14 @@ const char* ProcessGroupMI355X::enqueue_alltoall(Algo a, const std::vector<at::T
   if (is_ipc(a)) {
     TORCH_CHECK(equal, "pdcc: the IPC all-to-all needs equal splits");
     IpcComm& ic = ipc(ds);
-    kern::IpcCall c{};
-    c.coll = kern::IpcColl::ALLTOALL;
-    c.dtype = kern::DType::U8;
-    c.op = kern::RedOp::COPY;
-    c.bytes = wi[0].nbytes();
+    kern::IpcCall c = copy_call(kern::IpcColl::ALLTOALL, wi[0].nbytes());
     c.zstride = c.bytes;
     for (int r = 0; r < size_; ++r) {
       c.in[r] = wi[r].data_ptr();
       c.out[r] = wo[r].data_ptr();
     }
     if (ll_size(ds, c.bytes)) {  // small: chunk q pushed straight to rank q
-      c.coll = kern::IpcColl::ALLTOALL_LL;
+      c.coll = kern::coll_traits(c.coll).ll_twin;
       ic.launch(c, s);
       return "ipc_ll";
     }

@@ -353,9 +353,65 @@ bool ProcessGroupMI355X::ipc_selftest(DeviceState& ds) {
     for (const auto& x : v) all = all && !x.empty() && x[0] == 1;
     return all;
   };
+  auto say = [&](const char* what, bool mine, const std::string& why, const char* then) {
+    fprintf(stderr, "[pdcc r%d] %s self-test failed (%s): group '%s' %s\n", rank_, what,
+            mine ? "on another rank" : why.c_str(), group_name_.c_str(), then);
+  };
+  // One stage: `body` issues the stage's calls on the comm stream and returns whether their data came
+  // out right (it may give a reason of its own, or throw). Then the error word (`timeout_why`), the
+  // stage's test hook (`fail_env` naming this rank: report a failure), the store vote under `key`, and
+  // where the vote fails one sentence on stderr: "<what> self-test failed (...): group '...' <then>".
+  auto stage = [&](const char* key, const char* fail_env, const char* timeout_why, const char* what,
+                   const char* then, const std::function<bool(hipStream_t, std::string&)>& body) {
+    bool ok = false;
+    std::string why;
+    try {
+      c10::hip::HIPStreamGuardMasqueradingAsCUDA sg(ds.stream);
+      const hipStream_t s = ds.stream.stream();
+      ok = body(s, why);
+      PDCC_HIP(hipStreamSynchronize(s));
+      if (ds.ipc->error_word() != 0) {
+        ok = false;
+        why = timeout_why;
+        ds.ipc->clear_error();
+      } else if (!ok && why.empty()) {
+        why = "wrong data";
+      }
+    } catch (const std::exception& e) {
+      ok = false;
+      why = e.what();
+    }
+    if (const char* f = std::getenv(fail_env))
+      if (*f && std::atoi(f) == rank_) {
+        ok = false;
+        why = fail_env;
+      }
+    const bool all = vote(key, ok);
+    if (!all) say(what, ok, why, then);
+    return all;
+  };
   const int64_t spin_ms = std::max<int64_t>(1, std::min<int64_t>(cfg_.ipc_selftest_ms, timeout_.count()));
+  const auto opt = at::TensorOptions().device(at::kCUDA, ds.device).dtype(at::kFloat);
+  const double tri = size_ * (size_ + 1) / 2.0;
+  const size_t row_bytes = (size_t)size_ * kern::kTileBytes;
+  // an all-gather of `in` into consecutive slices of `out`
+  auto gather_call = [&](kern::IpcColl coll, const at::Tensor& in, at::Tensor& out) {
+    kern::IpcCall c = copy_call(coll, in.nbytes());
+    c.in[0] = in.data_ptr();
+    for (int r = 0; r < size_; ++r) c.out[r] = static_cast<char*>(out.data_ptr()) + r * in.nbytes();
+    return c;
+  };
+  // an in-place f32 / bf16 sum of `x`
+  auto sum_call = [&](kern::IpcColl coll, at::Tensor& x) {
+    kern::IpcCall c = reduce_call(coll, x.scalar_type() == at::kFloat ? kern::DType::F32 : kern::DType::BF16,
+                                  kern::RedOp::SUM, size_, x.nbytes());
+    c.in[0] = x.data_ptr();
+    c.out[0] = x.data_ptr();
+    return c;
+  };
+
   std::string why;
-  bool ok = true;
+  bool built = true;
   try {
     ds.ipc = std::make_shared<IpcComm>(store_, "pdcc/ipc", rank_, size_, ds.device, cfg_.ipc_max_staging,
                                        (uint64_t)spin_ms, ds.shared_device, cfg_.ipc_zc_cache);
@@ -363,151 +419,70 @@ bool ProcessGroupMI355X::ipc_selftest(DeviceState& ds) {
     ds.ipc->set_async_grid(cfg_.ipc_async_grid);
     ds.ipc->set_zc_size_guard(cfg_.ipc_zc_size_guard);
   } catch (const std::exception& e) {
-    ok = false;
+    built = false;
     why = e.what();
   }
-  bool all = vote("pdcc/ipc_selftest/built", ok);
-  if (all) {
-    try {
-      IpcComm& ic = *ds.ipc;
-      c10::hip::HIPStreamGuardMasqueradingAsCUDA sg(ds.stream);
-      const hipStream_t s = ds.stream.stream();
-      const auto opt = at::TensorOptions().device(at::kCUDA, ds.device).dtype(at::kFloat);
-      const double tri = size_ * (size_ + 1) / 2.0;
-      for (const int64_t n : {int64_t{1000}, int64_t{3} * size_ * 1024 + 257}) {
-        const at::Tensor base = at::arange(n, opt).remainder(7);
-        at::Tensor x = base + (double)(rank_ + 1);
-        kern::IpcCall c{};
-        c.coll = n == 1000 ? kern::IpcColl::ALLREDUCE_1SHOT : kern::IpcColl::ALLREDUCE_2SHOT;
-        c.dtype = kern::DType::F32;
-        c.op = kern::RedOp::SUM;
-        c.avg_div = size_;
-        c.bytes = x.nbytes();
-        c.in[0] = x.data_ptr();
-        c.out[0] = x.data_ptr();
-        ic.launch(c, s);
-        ok = at::equal(x, base * (double)size_ + tri) && ok;
-      }
-      const int64_t m = 780;  // 3120 B per rank: whole 16-B vectors, one partial tile
-      const at::Tensor in = at::full({m}, (double)rank_, opt);
-      at::Tensor out = at::full({m * size_}, -1.0, opt);
-      kern::IpcCall c{};
-      c.coll = kern::IpcColl::ALLGATHER;
-      c.dtype = kern::DType::U8;
-      c.op = kern::RedOp::COPY;
-      c.bytes = in.nbytes();
-      c.in[0] = in.data_ptr();
-      for (int r = 0; r < size_; ++r) c.out[r] = static_cast<char*>(out.data_ptr()) + r * in.nbytes();
-      ic.launch(c, s);
-      ok = at::equal(out, at::arange(size_, opt).repeat_interleave(m)) && ok;
-      if (ic.error_word() != 0) {
-        ok = false;
-        why = "a cross-GPU barrier timed out";
-      } else if (!ok) {
-        why = "wrong data";
-      }
-    } catch (const std::exception& e) {
-      ok = false;
-      why = e.what();
+  const char* const no_ipc = "runs without the peer-memory path";
+  bool all = vote("pdcc/ipc_selftest/built", built);
+  if (!all) say("IPC", built, why, no_ipc);
+  // the staged protocols: 1-shot, 2-shot with a partial last row and a ragged tail, an all-gather
+  all = all && stage("pdcc/ipc_selftest/result", "PDCC_IPC_SELFTEST_FAIL", "a cross-GPU barrier timed out", "IPC",
+                     no_ipc, [&](hipStream_t s, std::string&) {
+    IpcComm& ic = *ds.ipc;
+    bool ok = true;
+    for (const int64_t n : {int64_t{1000}, int64_t{3} * size_ * 1024 + 257}) {
+      const at::Tensor base = at::arange(n, opt).remainder(7);
+      at::Tensor x = base + (double)(rank_ + 1);
+      ic.launch(sum_call(n == 1000 ? kern::IpcColl::ALLREDUCE_1SHOT : kern::IpcColl::ALLREDUCE_2SHOT, x), s);
+      ok = at::equal(x, base * (double)size_ + tri) && ok;
     }
-    if (const char* f = std::getenv("PDCC_IPC_SELFTEST_FAIL"))  // test hook: this rank reports a failure
-      if (*f && std::atoi(f) == rank_) {
-        ok = false;
-        why = "PDCC_IPC_SELFTEST_FAIL";
-      }
-    all = vote("pdcc/ipc_selftest/result", ok);
-  }
+    const int64_t m = 780;  // 3120 B per rank: whole 16-B vectors, one partial tile
+    const at::Tensor in = at::full({m}, (double)rank_, opt);
+    at::Tensor out = at::full({m * size_}, -1.0, opt);
+    ic.launch(gather_call(kern::IpcColl::ALLGATHER, in, out), s);
+    return at::equal(out, at::arange(size_, opt).repeat_interleave(m)) && ok;
+  });
   if (!all) {
-    fprintf(stderr, "[pdcc r%d] IPC self-test failed (%s): group '%s' runs without the peer-memory path\n", rank_,
-            ok ? "on another rank" : why.c_str(), group_name_.c_str());
     // every rank voted after its own kernels finished: nothing touches these buffers any more
     if (ds.ipc) ds.ipc->release(std::chrono::milliseconds(std::max<int64_t>(1, std::min<int64_t>(timeout_.count(), 30000))));
     ds.ipc.reset();
     return false;
   }
+  IpcComm& ic = *ds.ipc;
   // zero-copy IPC (user buffers mapped per call and read in place): whole rows /
   // tiles zero-copy plus a staged rest, twice on one buffer (first and cached
   // mapping), all-gather with a ragged tail, reduce-scatter of a flat input
-  ds.zc_ok = false;
-  if (cfg_.ipc_zc) {
-    bool zok = true;
-    std::string zwhy;
-    IpcComm& ic = *ds.ipc;
-    try {
-      c10::hip::HIPStreamGuardMasqueradingAsCUDA sg(ds.stream);
-      const hipStream_t s = ds.stream.stream();
-      const auto opt = at::TensorOptions().device(at::kCUDA, ds.device).dtype(at::kFloat);
-      const int64_t tile_f = kern::kTileBytes / 4;
-      const int64_t n = 3 * size_ * tile_f + 257;
-      const at::Tensor base = at::arange(n, opt).remainder(5);
-      at::Tensor x = base + (double)(rank_ + 1);
-      const double tri = size_ * (size_ + 1) / 2.0;
-      for (int k = 0; k < 2; ++k) {
-        kern::IpcCall c{};
-        c.coll = kern::IpcColl::ALLREDUCE_2SHOT;
-        c.dtype = kern::DType::F32;
-        c.op = kern::RedOp::SUM;
-        c.avg_div = size_;
-        c.bytes = x.nbytes();
-        c.in[0] = x.data_ptr();
-        c.out[0] = x.data_ptr();
-        ipc_run(ds, c, x.data_ptr(), x.nbytes(), (size_t)size_ * kern::kTileBytes, ic.max_staging(), s,
-                k == 0 ? "pdcc/ipc_selftest/zc_ar0" : "pdcc/ipc_selftest/zc_ar1");
-        const at::Tensor want = k == 0 ? base * (double)size_ + tri : (base * (double)size_ + tri) * (double)size_;
-        zok = at::equal(x, want) && zok;
-      }
-      const int64_t m = 2 * tile_f + 5;
-      const at::Tensor in = at::full({m}, (double)rank_, opt);
-      at::Tensor out = at::full({m * size_}, -1.0, opt);
-      {
-        kern::IpcCall c{};
-        c.coll = kern::IpcColl::ALLGATHER;
-        c.dtype = kern::DType::U8;
-        c.op = kern::RedOp::COPY;
-        c.bytes = in.nbytes();
-        c.in[0] = in.data_ptr();
-        for (int r = 0; r < size_; ++r) c.out[r] = static_cast<char*>(out.data_ptr()) + r * in.nbytes();
-        ipc_run(ds, c, in.data_ptr(), in.nbytes(), kern::kTileBytes, ic.max_staging(), s, "pdcc/ipc_selftest/zc_ag");
-        zok = at::equal(out, at::arange(size_, opt).repeat_interleave(m)) && zok;
-      }
-      {
-        const at::Tensor rin = at::arange(size_ * 2 * tile_f, opt).remainder(3) + (double)rank_;
-        at::Tensor rout = at::full({2 * tile_f}, -1.0, opt);
-        kern::IpcCall c{};
-        c.coll = kern::IpcColl::REDUCE_SCATTER;
-        c.dtype = kern::DType::F32;
-        c.op = kern::RedOp::SUM;
-        c.avg_div = size_;
-        c.bytes = rout.nbytes();
-        c.zstride = rout.nbytes();
-        for (int r = 0; r < size_; ++r) c.in[r] = static_cast<const char*>(rin.data_ptr()) + r * rout.nbytes();
-        c.out[0] = rout.data_ptr();
-        ipc_run(ds, c, rin.data_ptr(), rin.nbytes(), kern::kTileBytes, ic.max_staging(), s, "pdcc/ipc_selftest/zc_rs");
-        const at::Tensor mine = rin.narrow(0, rank_ * 2 * tile_f, 2 * tile_f) - (double)rank_;
-        zok = at::equal(rout, mine * (double)size_ + (size_ - 1) * size_ / 2.0) && zok;
-      }
-      PDCC_HIP(hipStreamSynchronize(s));
-      if (ic.error_word() != 0) {
-        zok = false;
-        zwhy = "a cross-GPU barrier timed out";
-        ic.clear_error();
-      } else if (!zok) {
-        zwhy = "wrong data";
-      }
-    } catch (const std::exception& e) {
-      zok = false;
-      zwhy = e.what();
+  ds.zc_ok = cfg_.ipc_zc &&
+             stage("pdcc/ipc_selftest/zc", "PDCC_IPC_ZC_SELFTEST_FAIL", "a cross-GPU barrier timed out",
+                   "zero-copy IPC", "stages every IPC call", [&](hipStream_t s, std::string&) {
+    bool ok = true;
+    const int64_t tile_f = kern::kTileBytes / 4;
+    const int64_t n = 3 * size_ * tile_f + 257;
+    const at::Tensor base = at::arange(n, opt).remainder(5);
+    at::Tensor x = base + (double)(rank_ + 1);
+    for (int k = 0; k < 2; ++k) {
+      ipc_run(ds, sum_call(kern::IpcColl::ALLREDUCE_2SHOT, x), x.data_ptr(), x.nbytes(), row_bytes, ic.max_staging(),
+              s, k == 0 ? "pdcc/ipc_selftest/zc_ar0" : "pdcc/ipc_selftest/zc_ar1");
+      const at::Tensor want = k == 0 ? base * (double)size_ + tri : (base * (double)size_ + tri) * (double)size_;
+      ok = at::equal(x, want) && ok;
     }
-    if (const char* f = std::getenv("PDCC_IPC_ZC_SELFTEST_FAIL"))  // test hook: this rank reports a failure
-      if (*f && std::atoi(f) == rank_) {
-        zok = false;
-        zwhy = "PDCC_IPC_ZC_SELFTEST_FAIL";
-      }
-    ds.zc_ok = vote("pdcc/ipc_selftest/zc", zok);
-    if (!ds.zc_ok)
-      fprintf(stderr, "[pdcc r%d] zero-copy IPC self-test failed (%s): group '%s' stages every IPC call\n", rank_,
-              zok ? "on another rank" : zwhy.c_str(), group_name_.c_str());
-  }
+    const int64_t m = 2 * tile_f + 5;
+    const at::Tensor in = at::full({m}, (double)rank_, opt);
+    at::Tensor out = at::full({m * size_}, -1.0, opt);
+    ipc_run(ds, gather_call(kern::IpcColl::ALLGATHER, in, out), in.data_ptr(), in.nbytes(), kern::kTileBytes,
+            ic.max_staging(), s, "pdcc/ipc_selftest/zc_ag");
+    ok = at::equal(out, at::arange(size_, opt).repeat_interleave(m)) && ok;
+    const at::Tensor rin = at::arange(size_ * 2 * tile_f, opt).remainder(3) + (double)rank_;
+    at::Tensor rout = at::full({2 * tile_f}, -1.0, opt);
+    kern::IpcCall c =
+        reduce_call(kern::IpcColl::REDUCE_SCATTER, kern::DType::F32, kern::RedOp::SUM, size_, rout.nbytes());
+    c.zstride = rout.nbytes();
+    for (int r = 0; r < size_; ++r) c.in[r] = static_cast<const char*>(rin.data_ptr()) + r * rout.nbytes();
+    c.out[0] = rout.data_ptr();
+    ipc_run(ds, c, rin.data_ptr(), rin.nbytes(), kern::kTileBytes, ic.max_staging(), s, "pdcc/ipc_selftest/zc_rs");
+    const at::Tensor mine = rin.narrow(0, rank_ * 2 * tile_f, 2 * tile_f) - (double)rank_;
+    return at::equal(rout, mine * (double)size_ + (size_ - 1) * size_ / 2.0) && ok;
+  });
   // Device-side record exchange of gated zero-copy launches (design.md §3): a gated all-reduce
   // on a buffer every rank has mapped now must resolve on the device -- its host gate is not
   // opened unless the kernel is still running after a grace period (then: staged fallback,
@@ -516,28 +491,17 @@ bool ProcessGroupMI355X::ipc_selftest(DeviceState& ds) {
   // depending on the environment being the same everywhere)
   ds.zx_ok = false;
   if (ds.zc_ok) {
-    bool xok = cfg_.ipc_zx;
-    std::string xwhy = xok ? "" : "PDCC_IPC_ZX=0";
-    IpcComm& ic = *ds.ipc;
     ic.set_zx(cfg_.ipc_zx);
-    if (xok) try {
-      c10::hip::HIPStreamGuardMasqueradingAsCUDA sg(ds.stream);
-      const hipStream_t s = ds.stream.stream();
-      const auto opt = at::TensorOptions().device(at::kCUDA, ds.device).dtype(at::kFloat);
+    ds.zx_ok = !cfg_.ipc_zx ? vote("pdcc/ipc_selftest/zx", false) :
+               stage("pdcc/ipc_selftest/zx", "PDCC_IPC_ZX_SELFTEST_FAIL", "the device exchange or a barrier timed out",
+                     "device-side zero-copy exchange", "gates zero-copy calls on the host",
+                     [&](hipStream_t s, std::string& xwhy) {
       const int64_t row = (int64_t)size_ * (kern::kTileBytes / 4);
       const at::Tensor base = at::arange(4 * row, opt).remainder(7);
       at::Tensor x = base + (double)rank_;
       // map x everywhere first (inline exchange through the store, like the zc self-test)
-      kern::IpcCall c{};
-      c.coll = kern::IpcColl::ALLREDUCE_2SHOT;
-      c.dtype = kern::DType::F32;
-      c.op = kern::RedOp::SUM;
-      c.avg_div = size_;
-      c.bytes = x.nbytes();
-      c.in[0] = x.data_ptr();
-      c.out[0] = x.data_ptr();
-      ipc_run(ds, c, x.data_ptr(), x.nbytes(), (size_t)size_ * kern::kTileBytes, ic.max_staging(), s,
-              "pdcc/ipc_selftest/zx_map");
+      const kern::IpcCall c = sum_call(kern::IpcColl::ALLREDUCE_2SHOT, x);
+      ipc_run(ds, c, x.data_ptr(), x.nbytes(), row_bytes, ic.max_staging(), s, "pdcc/ipc_selftest/zx_map");
       const IpcComm::ZcRec mine = ic.zc_export(x.data_ptr(), x.nbytes(), false);
       const uint64_t t = ic.gate_reserve();
       ic.launch_gated(c, t, 0, mine, x.data_ptr(), s);
@@ -553,167 +517,90 @@ bool ProcessGroupMI355X::ipc_selftest(DeviceState& ds) {
       const at::Tensor once = base * (double)size_ + size_ * (size_ - 1) / 2.0;  // after the mapping call
       const bool data_ok = at::equal(x, once * (double)size_);
       const uint32_t verdict = ic.zx_verdict(tag);
-      if (ic.error_word() != 0) {
-        xok = false;
-        xwhy = "the device exchange or a barrier timed out";
-        ic.clear_error();
-      } else if (verdict != 1u) {
-        xok = false;
-        xwhy = "the kernel did not resolve the buffers on the device (verdict " + std::to_string(verdict) + ")";
-      } else if (!data_ok) {
-        xok = false;
-        xwhy = "wrong data";
-      }
-    } catch (const std::exception& e) {
-      xok = false;
-      xwhy = e.what();
-    }
-    if (const char* f = std::getenv("PDCC_IPC_ZX_SELFTEST_FAIL"))  // test hook: this rank reports a failure
-      if (*f && std::atoi(f) == rank_) {
-        xok = false;
-        xwhy = "PDCC_IPC_ZX_SELFTEST_FAIL";
-      }
-    const bool zx = vote("pdcc/ipc_selftest/zx", xok);
-    ic.set_zx(zx);
-    ds.zx_ok = zx;
-    if (!zx && cfg_.ipc_zx)
-      fprintf(stderr, "[pdcc r%d] device-side zero-copy exchange self-test failed (%s): group '%s' gates zero-copy "
-              "calls on the host\n", rank_, xok ? "on another rank" : xwhy.c_str(), group_name_.c_str());
+      if (verdict == 1u) return data_ok;
+      xwhy = "the kernel did not resolve the buffers on the device (verdict " + std::to_string(verdict) + ")";
+      return false;
+    });
+    ic.set_zx(ds.zx_ok);
   }
-  // LL all-reduce: payloads with a partial last line and the largest one, each twice
-  // (both slot parities), bf16 and f32
-  ds.ll_ok = false;
-  if (cfg_.ipc_ll_max > 0) {
-    bool lok = true;
-    std::string lwhy;
-    IpcComm& ic = *ds.ipc;
-    try {
-      c10::hip::HIPStreamGuardMasqueradingAsCUDA sg(ds.stream);
-      const hipStream_t s = ds.stream.stream();
-      const double tri = size_ * (size_ + 1) / 2.0;
-      const int64_t full = (int64_t)(kern::kLLMaxBytes / 4);
-      for (const int64_t n : {int64_t{1}, int64_t{1001}, full, full}) {
-        for (const auto dt : {at::kFloat, at::kBFloat16}) {
-          const auto opt = at::TensorOptions().device(at::kCUDA, ds.device).dtype(dt);
-          const int64_t ne = dt == at::kFloat ? n : std::max<int64_t>(1, n / 2 - 1);  // bf16: odd byte counts too
-          const at::Tensor base = at::arange(ne, opt).remainder(3);
-          at::Tensor x = base + (double)(rank_ + 1);
-          kern::IpcCall c{};
-          c.coll = kern::IpcColl::ALLREDUCE_LL;
-          c.dtype = dt == at::kFloat ? kern::DType::F32 : kern::DType::BF16;
-          c.op = kern::RedOp::SUM;
-          c.avg_div = size_;
-          c.bytes = x.nbytes();
-          c.in[0] = x.data_ptr();
-          c.out[0] = x.data_ptr();
-          ic.launch(c, s);
-          lok = at::equal(x, base * (double)size_ + tri) && lok;
-        }
+  // LL: payloads with a partial last line and the largest one, each twice (both slot parities),
+  // bf16 and f32
+  ds.ll_ok = cfg_.ipc_ll_max > 0 &&
+             stage("pdcc/ipc_selftest/ll", "PDCC_IPC_LL_SELFTEST_FAIL", "an LL poll timed out", "LL all-reduce",
+                   "uses the 1-shot protocol", [&](hipStream_t s, std::string&) {
+    bool ok = true;
+    const int64_t full = (int64_t)(kern::kLLMaxBytes / 4);
+    for (const int64_t n : {int64_t{1}, int64_t{1001}, full, full}) {
+      for (const auto dt : {at::kFloat, at::kBFloat16}) {
+        const int64_t ne = dt == at::kFloat ? n : std::max<int64_t>(1, n / 2 - 1);  // bf16: odd byte counts too
+        const at::Tensor base = at::arange(ne, opt.dtype(dt)).remainder(3);
+        at::Tensor x = base + (double)(rank_ + 1);
+        ic.launch(sum_call(kern::IpcColl::ALLREDUCE_LL, x), s);
+        ok = at::equal(x, base * (double)size_ + tri) && ok;
       }
-      for (const int64_t m : {int64_t{3}, full}) {  // all-gather: a partial line, the maximum
-        const auto opt = at::TensorOptions().device(at::kCUDA, ds.device).dtype(at::kFloat);
-        const at::Tensor in = at::full({m}, (double)rank_, opt);
-        at::Tensor out = at::full({m * size_}, -1.0, opt);
-        kern::IpcCall c{};
-        c.coll = kern::IpcColl::ALLGATHER_LL;
-        c.dtype = kern::DType::U8;
-        c.op = kern::RedOp::COPY;
-        c.bytes = in.nbytes();
-        c.in[0] = in.data_ptr();
-        for (int r = 0; r < size_; ++r) c.out[r] = static_cast<char*>(out.data_ptr()) + r * in.nbytes();
-        ic.launch(c, s);
-        lok = at::equal(out, at::arange(size_, opt).repeat_interleave(m)) && lok;
-      }
-      // rooted kinds (tokens on the pairs without data), first and last rank as root, a partial line
-      for (const int root : {0, size_ - 1}) {
-        const auto opt = at::TensorOptions().device(at::kCUDA, ds.device).dtype(at::kFloat);
-        const int64_t m = 1001;
-        const bool am_root = rank_ == root;
-        kern::IpcCall c{};
-        c.dtype = kern::DType::U8;
-        c.op = kern::RedOp::COPY;
-        c.root = root;
-        c.bytes = (size_t)m * 4;
-        at::Tensor b = at::full({m}, am_root ? 7.0 : -1.0, opt);  // broadcast
-        c.coll = kern::IpcColl::BROADCAST_LL;
-        c.in[0] = b.data_ptr();
-        c.out[0] = b.data_ptr();
-        ic.launch(c, s);
-        lok = at::equal(b, at::full({m}, 7.0, opt)) && lok;
-        const at::Tensor src = at::arange(size_ * m, opt).view({size_, m}).add((double)rank_);  // scatter
-        at::Tensor sc = at::full({m}, -1.0, opt);
-        c.coll = kern::IpcColl::SCATTER_LL;
-        for (int r = 0; r < size_; ++r) c.in[r] = am_root ? src[r].data_ptr() : nullptr;
-        c.out[0] = sc.data_ptr();
-        ic.launch(c, s);
-        lok = at::equal(sc, at::arange(m, opt).add((double)(rank_ * m + root))) && lok;
-        const at::Tensor gi = at::full({m}, (double)rank_, opt);  // gather
-        at::Tensor go = at::full({size_, m}, -1.0, opt);
-        c.coll = kern::IpcColl::GATHER_LL;
-        c.in[0] = gi.data_ptr();
-        for (int r = 0; r < size_; ++r) c.out[r] = am_root ? go[r].data_ptr() : nullptr;
-        ic.launch(c, s);
-        lok = (am_root ? at::equal(go, at::arange(size_, opt).view({size_, 1}).expand({size_, m}))
-                       : at::equal(go, at::full({size_, m}, -1.0, opt))) && lok;
-        const at::Tensor rb = at::arange(m, opt).remainder(5);  // reduce (non-root tensors untouched)
-        at::Tensor rx = rb + (double)(rank_ + 1);
-        c.coll = kern::IpcColl::REDUCE_LL;
-        c.dtype = kern::DType::F32;
-        c.op = kern::RedOp::SUM;
-        c.avg_div = size_;
-        c.in[0] = rx.data_ptr();
-        c.out[0] = rx.data_ptr();
-        ic.launch(c, s);
-        const double tri = size_ * (size_ + 1) / 2.0;
-        lok = at::equal(rx, am_root ? rb * (double)size_ + tri : rb + (double)(rank_ + 1)) && lok;
-      }
-      {  // reduce-scatter and all-to-all: chunk q to rank q (a partial line per chunk)
-        const auto opt = at::TensorOptions().device(at::kCUDA, ds.device).dtype(at::kFloat);
-        const int64_t m = 333;
-        const at::Tensor src = at::arange(size_, opt).view({size_, 1}).add((double)(100 * rank_)).expand({size_, m})
-                                   .contiguous();  // chunk q = 100 * rank + q
-        at::Tensor rs = at::full({m}, -1.0, opt);
-        at::Tensor a2a = at::full({size_, m}, -1.0, opt);
-        kern::IpcCall c{};
-        c.coll = kern::IpcColl::REDUCE_SCATTER_LL;
-        c.dtype = kern::DType::F32;
-        c.op = kern::RedOp::SUM;
-        c.avg_div = size_;
-        c.bytes = (size_t)m * 4;
-        for (int r = 0; r < size_; ++r) c.in[r] = src[r].data_ptr();
-        c.out[0] = rs.data_ptr();
-        ic.launch(c, s);
-        lok = at::equal(rs, at::full({m}, 100.0 * (tri - size_) + (double)(size_ * rank_), opt)) && lok;
-        c.coll = kern::IpcColl::ALLTOALL_LL;
-        c.dtype = kern::DType::U8;
-        c.op = kern::RedOp::COPY;
-        for (int r = 0; r < size_; ++r) c.out[r] = a2a[r].data_ptr();
-        ic.launch(c, s);
-        lok = at::equal(a2a, at::arange(size_, opt).mul(100.0).add((double)rank_).view({size_, 1}).expand({size_, m}))
-              && lok;
-      }
-      PDCC_HIP(hipStreamSynchronize(s));
-      if (ic.error_word() != 0) {
-        lok = false;
-        lwhy = "an LL poll timed out";
-        ic.clear_error();
-      } else if (!lok) {
-        lwhy = "wrong data";
-      }
-    } catch (const std::exception& e) {
-      lok = false;
-      lwhy = e.what();
     }
-    if (const char* f = std::getenv("PDCC_IPC_LL_SELFTEST_FAIL"))  // test hook: this rank reports a failure
-      if (*f && std::atoi(f) == rank_) {
-        lok = false;
-        lwhy = "PDCC_IPC_LL_SELFTEST_FAIL";
-      }
-    ds.ll_ok = vote("pdcc/ipc_selftest/ll", lok);
-    if (!ds.ll_ok)
-      fprintf(stderr, "[pdcc r%d] LL all-reduce self-test failed (%s): group '%s' uses the 1-shot protocol\n", rank_,
-              lok ? "on another rank" : lwhy.c_str(), group_name_.c_str());
-  }
+    for (const int64_t m : {int64_t{3}, full}) {  // all-gather: a partial line, the maximum
+      const at::Tensor in = at::full({m}, (double)rank_, opt);
+      at::Tensor out = at::full({m * size_}, -1.0, opt);
+      ic.launch(gather_call(kern::IpcColl::ALLGATHER_LL, in, out), s);
+      ok = at::equal(out, at::arange(size_, opt).repeat_interleave(m)) && ok;
+    }
+    // rooted kinds (tokens on the pairs without data), first and last rank as root, a partial line
+    for (const int root : {0, size_ - 1}) {
+      const int64_t m = 1001;
+      const bool am_root = rank_ == root;
+      at::Tensor b = at::full({m}, am_root ? 7.0 : -1.0, opt);  // broadcast
+      kern::IpcCall c = copy_call(kern::IpcColl::BROADCAST_LL, (size_t)m * 4, root);
+      c.in[0] = b.data_ptr();
+      c.out[0] = b.data_ptr();
+      ic.launch(c, s);
+      ok = at::equal(b, at::full({m}, 7.0, opt)) && ok;
+      const at::Tensor src = at::arange(size_ * m, opt).view({size_, m}).add((double)rank_);  // scatter
+      at::Tensor sc = at::full({m}, -1.0, opt);
+      c.coll = kern::IpcColl::SCATTER_LL;
+      for (int r = 0; r < size_; ++r) c.in[r] = am_root ? src[r].data_ptr() : nullptr;
+      c.out[0] = sc.data_ptr();
+      ic.launch(c, s);
+      ok = at::equal(sc, at::arange(m, opt).add((double)(rank_ * m + root))) && ok;
+      const at::Tensor gi = at::full({m}, (double)rank_, opt);  // gather
+      at::Tensor go = at::full({size_, m}, -1.0, opt);
+      c.coll = kern::IpcColl::GATHER_LL;
+      c.in[0] = gi.data_ptr();
+      for (int r = 0; r < size_; ++r) c.out[r] = am_root ? go[r].data_ptr() : nullptr;
+      ic.launch(c, s);
+      ok = (am_root ? at::equal(go, at::arange(size_, opt).view({size_, 1}).expand({size_, m}))
+                    : at::equal(go, at::full({size_, m}, -1.0, opt))) && ok;
+      const at::Tensor rb = at::arange(m, opt).remainder(5);  // reduce (non-root tensors untouched)
+      at::Tensor rx = rb + (double)(rank_ + 1);
+      c.coll = kern::IpcColl::REDUCE_LL;
+      c.dtype = kern::DType::F32;
+      c.op = kern::RedOp::SUM;
+      c.avg_div = size_;
+      c.in[0] = rx.data_ptr();
+      c.out[0] = rx.data_ptr();
+      ic.launch(c, s);
+      ok = at::equal(rx, am_root ? rb * (double)size_ + tri : rb + (double)(rank_ + 1)) && ok;
+    }
+    // reduce-scatter and all-to-all: chunk q to rank q (a partial line per chunk)
+    const int64_t m = 333;
+    const at::Tensor src = at::arange(size_, opt).view({size_, 1}).add((double)(100 * rank_)).expand({size_, m})
+                               .contiguous();  // chunk q = 100 * rank + q
+    at::Tensor rs = at::full({m}, -1.0, opt);
+    at::Tensor a2a = at::full({size_, m}, -1.0, opt);
+    kern::IpcCall c =
+        reduce_call(kern::IpcColl::REDUCE_SCATTER_LL, kern::DType::F32, kern::RedOp::SUM, size_, (size_t)m * 4);
+    for (int r = 0; r < size_; ++r) c.in[r] = src[r].data_ptr();
+    c.out[0] = rs.data_ptr();
+    ic.launch(c, s);
+    ok = at::equal(rs, at::full({m}, 100.0 * (tri - size_) + (double)(size_ * rank_), opt)) && ok;
+    c.coll = kern::IpcColl::ALLTOALL_LL;
+    c.dtype = kern::DType::U8;
+    c.op = kern::RedOp::COPY;
+    for (int r = 0; r < size_; ++r) c.out[r] = a2a[r].data_ptr();
+    ic.launch(c, s);
+    return at::equal(a2a, at::arange(size_, opt).mul(100.0).add((double)rank_).view({size_, 1}).expand({size_, m})) &&
+           ok;
+  });
   ds.ipc->set_timeout_ms((uint64_t)std::max<int64_t>(1, std::min<int64_t>(cfg_.ipc_spin_ms, timeout_.count())));
   return true;
 }

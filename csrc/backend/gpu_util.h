@@ -101,6 +101,22 @@ inline RedSpec red_spec(at::ScalarType t, RedOpType op) {
   return r;
 }
 
+// One IPC call's fixed fields: a reducing one, a copying one. Callers fill in[], out[] (and zstride).
+inline kern::IpcCall reduce_call(kern::IpcColl coll, kern::DType dt, kern::RedOp op, int avg_div, size_t bytes) {
+  kern::IpcCall c{};
+  c.coll = coll;
+  c.dtype = dt;
+  c.op = op;
+  c.avg_div = avg_div;
+  c.bytes = bytes;
+  return c;
+}
+inline kern::IpcCall copy_call(kern::IpcColl coll, size_t bytes, int root = 0) {
+  kern::IpcCall c = reduce_call(coll, kern::DType::U8, kern::RedOp::COPY, 0, bytes);
+  c.root = root;
+  return c;
+}
+
 inline const char* op_name(int op) {
   switch (op) {
     case RedOpType::SUM: return "SUM";

@@ -28,7 +28,7 @@
 #include <string>
 #include <vector>
 
-#include "../kernels/kernel_api.h"
+#include "../kernels/ipc_plan.h"
 
 namespace pdcc {
 

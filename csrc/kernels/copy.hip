@@ -249,26 +249,6 @@ __global__ void __launch_bounds__(256) k_ipc_copy(IpcView v, IpcCall c) {
 // =============================================================== host entry points
 namespace kern {
 
-bool supports(DType t, RedOp op) {
-  if (op == RedOp::COPY) return true;
-  const bool is_float = t == DType::F32 || t == DType::F16 || t == DType::BF16 || t == DType::F64;
-  const bool is_int = t == DType::I8 || t == DType::U8 || t == DType::I32 || t == DType::I64;
-  if (t == DType::BOOL) return op == RedOp::MAX || op == RedOp::MIN || op == RedOp::BAND || op == RedOp::BOR ||
-                               op == RedOp::BXOR || op == RedOp::SUM || op == RedOp::PROD;
-  if (is_float) return op == RedOp::SUM || op == RedOp::AVG || op == RedOp::PROD || op == RedOp::MIN ||
-                       op == RedOp::MAX;
-  return is_int;
-}
-
-// bool: SUM == logical OR == MAX, PROD == logical AND == MIN (ProcessGroupNCCL semantics)
-static void canon(DType& t, RedOp& op) {
-  if (t == DType::BOOL) {
-    t = DType::U8;
-    if (op == RedOp::SUM) op = RedOp::MAX;
-    if (op == RedOp::PROD) op = RedOp::MIN;
-  }
-}
-
 static hipError_t k1_dispatch(const void* const* srcs, int nsrc, void* out, size_t count, DType t, RedOp op,
                               int avg_div, hipStream_t stream, int max_blocks, int lds) {
   if (nsrc < 1 || nsrc > kMaxRanks || op == RedOp::COPY || !supports(t, op)) return hipErrorInvalidValue;
@@ -280,14 +260,10 @@ static hipError_t k1_dispatch(const void* const* srcs, int nsrc, void* out, size
   int grid = (int)std::min<size_t>(std::max<size_t>(tiles, 1), max_blocks > 0 ? (size_t)max_blocks : 256);
   using namespace dev;
   switch (t) {
-    case DType::F32: return k1_dispatch_F32(srcs, nsrc, out, nbytes, op, avg_div, stream, grid, lds);
-    case DType::F16: return k1_dispatch_F16(srcs, nsrc, out, nbytes, op, avg_div, stream, grid, lds);
-    case DType::BF16: return k1_dispatch_BF16(srcs, nsrc, out, nbytes, op, avg_div, stream, grid, lds);
-    case DType::F64: return k1_dispatch_F64(srcs, nsrc, out, nbytes, op, avg_div, stream, grid, lds);
-    case DType::I8: return k1_dispatch_I8(srcs, nsrc, out, nbytes, op, avg_div, stream, grid, lds);
-    case DType::U8: return k1_dispatch_U8(srcs, nsrc, out, nbytes, op, avg_div, stream, grid, lds);
-    case DType::I32: return k1_dispatch_I32(srcs, nsrc, out, nbytes, op, avg_div, stream, grid, lds);
-    case DType::I64: return k1_dispatch_I64(srcs, nsrc, out, nbytes, op, avg_div, stream, grid, lds);
+#define PDCC_DT(DT) \
+  case DType::DT: return k1_dispatch_##DT(srcs, nsrc, out, nbytes, op, avg_div, stream, grid, lds);
+    PDCC_FOR_DTYPES(PDCC_DT)
+#undef PDCC_DT
     default: return hipErrorInvalidValue;
   }
 }
@@ -369,154 +345,31 @@ hipError_t multi_copy(const CopyDesc* descs, int n, hipStream_t stream, int max_
 // block-pairwise flags, the per-block call counters, the LL control words and LL slots
 size_t ipc_signal_bytes() { return kDynOffset + kDynBytes; }
 
-size_t ipc_staging_bytes(const IpcCall& c, int world) {
-  if (c.gate) {  // either protocol may run: the larger need
-    IpcCall z = c, st = c;
-    z.gate = st.gate = nullptr;
-    z.ztab = st.ztab = nullptr;
-    z.zc = 1;
-    st.zc = 0;
-    if (st.coll == IpcColl::ALLREDUCE_PUSH) st.coll = IpcColl::ALLREDUCE_2SHOT;
-    return std::max(ipc_staging_bytes(z, world), ipc_staging_bytes(st, world));
-  }
-  if (c.zc)  // peers read the user buffers in place; a rooted reduce stages its reduced tiles,
-             // the push all-reduce receives W slots of bytes / W
-    return c.coll == IpcColl::REDUCE_2SHOT || c.coll == IpcColl::ALLREDUCE_PUSH
-               ? (c.bytes + kTileBytes - 1) / kTileBytes * kTileBytes : 0;
-  if (c.coll == IpcColl::ALLREDUCE_PUSH) return 0;  // (zero-copy only; rejected by ipc_launch)
-  if (is_ll(c.coll)) return 0;  // straight into LL slots
-  const size_t cpad = (c.bytes + kTileBytes - 1) / kTileBytes * kTileBytes;
-  switch (c.coll) {
-    case IpcColl::SCATTER:
-    case IpcColl::REDUCE_SCATTER:
-    case IpcColl::ALLTOALL:
-      return cpad * world;
-    case IpcColl::BARRIER:
-      return 0;
-    case IpcColl::ALLREDUCE_2SHOT:
-    case IpcColl::REDUCE_2SHOT:
-    case IpcColl::BROADCAST_2SHOT: {
-      // whole rows of W tiles: phase 2 (dev::OwnerRowMap) reads a partial last row's padding
-      const size_t row = (size_t)world * kTileBytes;
-      return (cpad + row - 1) / row * row;
-    }
-    default:
-      return cpad;
-  }
-}
-
+// plan (ipc_plan.h: every rejection, the grid, the canonical dtype and op), then one dispatch on
+// (family, world[, dtype, op])
 hipError_t ipc_launch(const IpcView& v, const IpcCall& call, hipStream_t stream) {
+  const IpcPlan p = ipc_plan(v.world, call);
+  if (p.err != hipSuccess) return p.err;
   IpcCall c = call;
-  if (v.world < 2 || v.world > kMaxRanks) return hipErrorInvalidValue;
-  if (c.gate && (c.zc || is_ll(c.coll))) return hipErrorInvalidValue;  // the kernel picks zc for a gated call
-  if (c.zc || c.gate) {  // in-place reads of user buffers: whole tiles (2-shot: whole rows of W tiles), no over-read
-    const bool rows = c.coll == IpcColl::ALLREDUCE_2SHOT || c.coll == IpcColl::BROADCAST_2SHOT ||
-                      c.coll == IpcColl::REDUCE_2SHOT || c.coll == IpcColl::ALLREDUCE_PUSH;
-    const bool known = rows || c.coll == IpcColl::ALLGATHER || c.coll == IpcColl::GATHER ||
-                       c.coll == IpcColl::SCATTER || c.coll == IpcColl::REDUCE_SCATTER ||
-                       c.coll == IpcColl::ALLTOALL;
-    const size_t unit = (size_t)kTileBytes * (rows ? v.world : 1);
-    if (!known || c.bytes == 0 || c.bytes % unit != 0) return hipErrorInvalidValue;
-  }
-  const size_t nt = (c.bytes + kTileBytes - 1) / kTileBytes;
-  int grid = c.grid;
-  if (grid <= 0) {
-    size_t g;
-    switch (c.coll) {
-      case IpcColl::ALLREDUCE_2SHOT:
-      case IpcColl::ALLREDUCE_PUSH:
-      case IpcColl::REDUCE_2SHOT:
-      case IpcColl::BROADCAST_2SHOT:
-        g = (nt + v.world - 1) / v.world;  // rows
-        break;
-      case IpcColl::BARRIER:
-        g = 1;
-        break;
-      case IpcColl::ALLREDUCE_LL:
-      case IpcColl::ALLGATHER_LL:
-      case IpcColl::REDUCE_LL:
-      case IpcColl::BROADCAST_LL:
-      case IpcColl::GATHER_LL:
-      case IpcColl::SCATTER_LL:
-      case IpcColl::REDUCE_SCATTER_LL:
-      case IpcColl::ALLTOALL_LL:
-        g = ((c.bytes + 7) / 8 + kBlockThreads - 1) / kBlockThreads;  // one 8-byte line per thread
-        break;
-      default:
-        g = nt;
-    }
-    grid = (int)std::max<size_t>(1, std::min<size_t>(g, c.grid_cap > 0 ? (size_t)c.grid_cap : 512));
-  }
-  if (c.grid_cap > 0) grid = std::min(grid, c.grid_cap);
-  grid = std::min(grid, kMaxBlocks);
-  // a gated zero-copy launch with the device-side exchange: one more workgroup, block 0, does only
-  // the exchange (dev::xchg_blocks); the data blocks keep the grid every rank computes the same way
-  if (c.gate && c.ztab && !is_ll(c.coll)) grid = std::min(grid, kMaxBlocks - 1) + 1;
-  if (c.coll == IpcColl::ALLREDUCE_PUSH && !c.zc && !c.gate) return hipErrorInvalidValue;
-  if (is_ll(c.coll) && (c.zc || c.bytes == 0 || c.bytes > kLLMaxBytes))
-    return hipErrorInvalidValue;
-  const bool ll_rooted = c.coll == IpcColl::REDUCE_LL || c.coll == IpcColl::BROADCAST_LL ||
-                         c.coll == IpcColl::GATHER_LL || c.coll == IpcColl::SCATTER_LL;
-  if (ll_rooted && (c.root < 0 || c.root >= v.world)) return hipErrorInvalidValue;
-  const bool reducing = c.coll == IpcColl::ALLREDUCE_1SHOT || c.coll == IpcColl::ALLREDUCE_2SHOT ||
-                        c.coll == IpcColl::ALLREDUCE_PUSH || c.coll == IpcColl::ALLREDUCE_LL ||
-                        c.coll == IpcColl::REDUCE_LL || c.coll == IpcColl::REDUCE_SCATTER_LL ||
-                        c.coll == IpcColl::REDUCE_1SHOT || c.coll == IpcColl::REDUCE_2SHOT ||
-                        c.coll == IpcColl::REDUCE_SCATTER;
-  if (c.coll == IpcColl::ALLGATHER_LL) {
-    switch (v.world) {
-#define PDCC_W(WW) \
-  case WW: hipLaunchKernelGGL(dev::k_ll_allgather<WW>, dim3(grid), dim3(256), 0, stream, v, c); break;
-      PDCC_W(2) PDCC_W(3) PDCC_W(4) PDCC_W(5) PDCC_W(6) PDCC_W(7) PDCC_W(8)
-#undef PDCC_W
-      default: return hipErrorInvalidValue;
-    }
-    return hipGetLastError();
-  }
-  if (c.coll == IpcColl::ALLTOALL_LL) {
-    switch (v.world) {
-#define PDCC_W(WW) \
-  case WW: hipLaunchKernelGGL(dev::k_ll_alltoall<WW>, dim3(grid), dim3(256), 0, stream, v, c); break;
-      PDCC_W(2) PDCC_W(3) PDCC_W(4) PDCC_W(5) PDCC_W(6) PDCC_W(7) PDCC_W(8)
-#undef PDCC_W
-      default: return hipErrorInvalidValue;
-    }
-    return hipGetLastError();
-  }
-  if (c.coll == IpcColl::BROADCAST_LL || c.coll == IpcColl::GATHER_LL || c.coll == IpcColl::SCATTER_LL) {
-    switch (v.world) {
-#define PDCC_W(WW) \
-  case WW: hipLaunchKernelGGL(dev::k_ll_rooted<WW>, dim3(grid), dim3(256), 0, stream, v, c); break;
-      PDCC_W(2) PDCC_W(3) PDCC_W(4) PDCC_W(5) PDCC_W(6) PDCC_W(7) PDCC_W(8)
-#undef PDCC_W
-      default: return hipErrorInvalidValue;
-    }
-    return hipGetLastError();
-  }
-  if (!reducing) {
-    switch (v.world) {
-#define PDCC_W(WW) \
-  case WW: hipLaunchKernelGGL(dev::k_ipc_copy<WW>, dim3(grid), dim3(256), 0, stream, v, c); break;
-      PDCC_W(2) PDCC_W(3) PDCC_W(4) PDCC_W(5) PDCC_W(6) PDCC_W(7) PDCC_W(8)
-#undef PDCC_W
-      default: return hipErrorInvalidValue;
-    }
-    return hipGetLastError();
-  }
-  if (!supports(c.dtype, c.op)) return hipErrorInvalidValue;
-  canon(c.dtype, c.op);
+  c.dtype = p.dtype;
+  c.op = p.op;
   using namespace dev;
-  switch (c.dtype) {
-    case DType::F32: return ipc_dispatch_F32(v, c, stream, grid);
-    case DType::F16: return ipc_dispatch_F16(v, c, stream, grid);
-    case DType::BF16: return ipc_dispatch_BF16(v, c, stream, grid);
-    case DType::F64: return ipc_dispatch_F64(v, c, stream, grid);
-    case DType::I8: return ipc_dispatch_I8(v, c, stream, grid);
-    case DType::U8: return ipc_dispatch_U8(v, c, stream, grid);
-    case DType::I32: return ipc_dispatch_I32(v, c, stream, grid);
-    case DType::I64: return ipc_dispatch_I64(v, c, stream, grid);
-    default: return hipErrorInvalidValue;
-  }
+  if (coll_traits(c.coll).reducing) switch (p.dtype) {
+#define PDCC_DT(DT) \
+  case DType::DT: return ipc_dispatch_##DT(v, c, stream, p);
+      PDCC_FOR_DTYPES(PDCC_DT)
+#undef PDCC_DT
+      default: return hipErrorInvalidValue;
+    }
+  return by_world(v.world, [&](auto w) {
+    constexpr int W = decltype(w)::value;
+    switch (p.family) {
+      case Family::LL_ALLGATHER: return ipc_go(k_ll_allgather<W>, p.grid, stream, v, c);
+      case Family::LL_ALLTOALL: return ipc_go(k_ll_alltoall<W>, p.grid, stream, v, c);
+      case Family::LL_ROOTED: return ipc_go(k_ll_rooted<W>, p.grid, stream, v, c);
+      default: return ipc_go(k_ipc_copy<W>, p.grid, stream, v, c);
+    }
+  });
 }
 
 }  // namespace kern

@@ -42,7 +42,16 @@ inline size_t dtype_size(DType t) {
 }
 
 // true iff the (dtype, op) pair has a device kernel
-bool supports(DType t, RedOp op);
+inline bool supports(DType t, RedOp op) {
+  if (op == RedOp::COPY) return true;
+  const bool is_float = t == DType::F32 || t == DType::F16 || t == DType::BF16 || t == DType::F64;
+  const bool is_int = t == DType::I8 || t == DType::U8 || t == DType::I32 || t == DType::I64;
+  if (t == DType::BOOL) return op == RedOp::MAX || op == RedOp::MIN || op == RedOp::BAND || op == RedOp::BOR ||
+                               op == RedOp::BXOR || op == RedOp::SUM || op == RedOp::PROD;
+  if (is_float) return op == RedOp::SUM || op == RedOp::AVG || op == RedOp::PROD || op == RedOp::MIN ||
+                       op == RedOp::MAX;
+  return is_int;
+}
 
 // ---------------------------------------------------------------- K1
 // out[i] = Op(srcs[0][i], ..., srcs[nsrc-1][i]), 1 <= nsrc <= kMaxRanks.
@@ -173,12 +182,7 @@ enum class IpcColl : int32_t {
   kCount
 };
 
-// the flag-tagged push protocols (no staging, no barrier; payload <= kLLMaxBytes)
-inline bool is_ll(IpcColl c) {
-  return c == IpcColl::ALLREDUCE_LL || c == IpcColl::ALLGATHER_LL || c == IpcColl::REDUCE_LL ||
-         c == IpcColl::BROADCAST_LL || c == IpcColl::GATHER_LL || c == IpcColl::SCATTER_LL ||
-         c == IpcColl::REDUCE_SCATTER_LL || c == IpcColl::ALLTOALL_LL;
-}
+// (what the host must know about each protocol: kern::coll_traits, ipc_plan.h)
 
 // Arguments of one IPC collective. `chunk_bytes` is the per-rank payload of one
 // chunk (all-gather/scatter/... operate on W chunks of that size).
@@ -303,8 +307,7 @@ struct IpcCallT {
 };
 using IpcCall = IpcCallT<RawPtr>;
 
-// Bytes of staging needed for `call` (padded to tiles).
-size_t ipc_staging_bytes(const IpcCall& call, int world);
+// (kern::ipc_staging_bytes and kern::ipc_plan, what a launch will do: ipc_plan.h)
 // Bytes of the signal area every rank must allocate (uncached memory).
 size_t ipc_signal_bytes();
 hipError_t ipc_launch(const IpcView& view, const IpcCall& call, hipStream_t stream);

@@ -6,6 +6,7 @@
 #include <cstdlib>
 
 #include "dev_common.h"
+#include "ipc_plan.h"
 
 namespace pdcc {
 namespace dev {
@@ -1015,15 +1016,9 @@ __global__ void __launch_bounds__(256) k_ll_alltoall(IpcView v, IpcCall c) {
 #define PDCC_DECL_DISPATCH(DTNAME)                                                                   \
   hipError_t k1_dispatch_##DTNAME(const void* const* srcs, int n, void* out, size_t nb, RedOp op,    \
                                   int avg_div, hipStream_t s, int grid, int lds);                    \
-  hipError_t ipc_dispatch_##DTNAME(const IpcView& v, const IpcCall& c, hipStream_t s, int grid);
-PDCC_DECL_DISPATCH(F32)
-PDCC_DECL_DISPATCH(F16)
-PDCC_DECL_DISPATCH(BF16)
-PDCC_DECL_DISPATCH(F64)
-PDCC_DECL_DISPATCH(I8)
-PDCC_DECL_DISPATCH(U8)
-PDCC_DECL_DISPATCH(I32)
-PDCC_DECL_DISPATCH(I64)
+  hipError_t ipc_dispatch_##DTNAME(const IpcView& v, const IpcCall& c, hipStream_t s, const kern::IpcPlan& p);
+#define PDCC_FOR_DTYPES(X) X(F32) X(F16) X(BF16) X(F64) X(I8) X(U8) X(I32) X(I64)
+PDCC_FOR_DTYPES(PDCC_DECL_DISPATCH)
 #undef PDCC_DECL_DISPATCH
 
 // `mode` (kern::K1Mode): bit 0 = LDS-DMA engine (else registers), bit 1 = non-temporal stores,
@@ -1080,46 +1075,24 @@ hipError_t k1_by_n(const void* const* srcs, int n, void* out, size_t nbytes, int
   }
 }
 
-template <DType DT, RedOp OP>
-hipError_t ipc_by_w(const IpcView& v, const IpcCall& c, hipStream_t s, int grid) {
-  if (c.coll == IpcColl::ALLREDUCE_LL) {
-    switch (v.world) {
-#define PDCC_W(WW) \
-  case WW: hipLaunchKernelGGL((k_ll_allreduce<DT, OP, WW>), dim3(grid), dim3(256), 0, s, v, c); break;
-      PDCC_W(2) PDCC_W(3) PDCC_W(4) PDCC_W(5) PDCC_W(6) PDCC_W(7) PDCC_W(8)
-#undef PDCC_W
-      default: return hipErrorInvalidValue;
-    }
-    return hipGetLastError();
-  }
-  if (c.coll == IpcColl::REDUCE_LL) {
-    switch (v.world) {
-#define PDCC_W(WW) \
-  case WW: hipLaunchKernelGGL((k_ll_reduce<DT, OP, WW>), dim3(grid), dim3(256), 0, s, v, c); break;
-      PDCC_W(2) PDCC_W(3) PDCC_W(4) PDCC_W(5) PDCC_W(6) PDCC_W(7) PDCC_W(8)
-#undef PDCC_W
-      default: return hipErrorInvalidValue;
-    }
-    return hipGetLastError();
-  }
-  if (c.coll == IpcColl::REDUCE_SCATTER_LL) {
-    switch (v.world) {
-#define PDCC_W(WW) \
-  case WW: hipLaunchKernelGGL((k_ll_reduce_scatter<DT, OP, WW>), dim3(grid), dim3(256), 0, s, v, c); break;
-      PDCC_W(2) PDCC_W(3) PDCC_W(4) PDCC_W(5) PDCC_W(6) PDCC_W(7) PDCC_W(8)
-#undef PDCC_W
-      default: return hipErrorInvalidValue;
-    }
-    return hipGetLastError();
-  }
-  switch (v.world) {
-#define PDCC_W(WW) \
-  case WW: hipLaunchKernelGGL((k_ipc_reduce<DT, OP, WW>), dim3(grid), dim3(256), 0, s, v, c); break;
-    PDCC_W(2) PDCC_W(3) PDCC_W(4) PDCC_W(5) PDCC_W(6) PDCC_W(7) PDCC_W(8)
-#undef PDCC_W
-    default: return hipErrorInvalidValue;
-  }
+// every IPC kernel takes (view, call) and runs 256 threads per workgroup
+inline hipError_t ipc_go(void (*k)(IpcView, IpcCall), int grid, hipStream_t s, const IpcView& v, const IpcCall& c) {
+  hipLaunchKernelGGL(k, dim3(grid), dim3(256), 0, s, v, c);
   return hipGetLastError();
+}
+
+// the reducing kernel families, for one (dtype, op)
+template <DType DT, RedOp OP>
+hipError_t ipc_by_w(const IpcView& v, const IpcCall& c, hipStream_t s, const kern::IpcPlan& p) {
+  return kern::by_world(v.world, [&](auto w) {
+    constexpr int W = decltype(w)::value;
+    switch (p.family) {
+      case kern::Family::LL_ALLREDUCE: return ipc_go(k_ll_allreduce<DT, OP, W>, p.grid, s, v, c);
+      case kern::Family::LL_REDUCE: return ipc_go(k_ll_reduce<DT, OP, W>, p.grid, s, v, c);
+      case kern::Family::LL_REDUCE_SCATTER: return ipc_go(k_ll_reduce_scatter<DT, OP, W>, p.grid, s, v, c);
+      default: return ipc_go(k_ipc_reduce<DT, OP, W>, p.grid, s, v, c);
+    }
+  });
 }
 
 }  // namespace dev
@@ -1147,9 +1120,10 @@ hipError_t ipc_by_w(const IpcView& v, const IpcCall& c, hipStream_t s, int grid)
     constexpr DType DT = DType::DTNAME;                                                               \
     switch (op) { OPSET(k1_by_n, srcs, n, out, nb, avg_div, s, grid, lds) default: return hipErrorInvalidValue; } \
   }                                                                                                   \
-  hipError_t ipc_dispatch_##DTNAME(const IpcView& v, const IpcCall& c, hipStream_t s, int grid) {     \
+  hipError_t ipc_dispatch_##DTNAME(const IpcView& v, const IpcCall& c, hipStream_t s,              \
+                                   const kern::IpcPlan& p) {                                         \
     constexpr DType DT = DType::DTNAME;                                                               \
-    switch (c.op) { OPSET(ipc_by_w, v, c, s, grid) default: return hipErrorInvalidValue; }            \
+    switch (p.op) { OPSET(ipc_by_w, v, c, s, p) default: return hipErrorInvalidValue; }               \
   }                                                                                                   \
   }                                                                                                   \
   }
