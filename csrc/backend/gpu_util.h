@@ -37,6 +37,8 @@ inline bool kern_dtype(at::ScalarType t, kern::DType& d) {
     case at::kInt: d = kern::DType::I32; return true;
     case at::kLong: d = kern::DType::I64; return true;
     case at::kBool: d = kern::DType::BOOL; return true;
+    case at::kFloat8_e4m3fn: d = kern::DType::F8E4M3; return true;  // (the OCP formats only: fnuz is gfx942's)
+    case at::kFloat8_e5m2: d = kern::DType::F8E5M2; return true;
     default: return false;
   }
 }
@@ -66,6 +68,8 @@ inline bool nccl_dtype(at::ScalarType t, ncclDataType_t& d) {
     case at::kBool: d = ncclUint8; return true;
     case at::kInt: d = ncclInt32; return true;
     case at::kLong: d = ncclInt64; return true;
+    // (no FP8: a ring rounds to 8 bits at every hop, so its result depends on the rank's position and
+    // cannot meet the fold-in-f32, round-once contract of the IPC kernels and the host path)
     default: return false;
   }
 }

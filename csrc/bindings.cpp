@@ -28,6 +28,8 @@ pdcc::kern::DType kdtype(at::ScalarType t) {
     case at::kInt: return pdcc::kern::DType::I32;
     case at::kLong: return pdcc::kern::DType::I64;
     case at::kBool: return pdcc::kern::DType::BOOL;
+    case at::kFloat8_e4m3fn: return pdcc::kern::DType::F8E4M3;
+    case at::kFloat8_e5m2: return pdcc::kern::DType::F8E5M2;
     default: TORCH_CHECK(false, "pdcc.ops: unsupported dtype ", t);
   }
 }

@@ -5,6 +5,8 @@
 #pragma once
 #include <c10/core/ScalarType.h>
 #include <c10/util/BFloat16.h>
+#include <c10/util/Float8_e4m3fn.h>
+#include <c10/util/Float8_e5m2.h>
 #include <c10/util/Half.h>
 #include <torch/csrc/distributed/c10d/Types.hpp>
 
@@ -95,6 +97,9 @@ inline void reduce_cpu(at::ScalarType t, void* dst, const void* const* srcs, int
     case at::kInt: return reduce_typed<int32_t, int32_t>(dst, srcs, n, count, op, avg_div);
     case at::kLong: return reduce_typed<int64_t, int64_t>(dst, srcs, n, count, op, avg_div);
     case at::kBool: return reduce_typed<bool, bool>(dst, srcs, n, count, op, avg_div);
+    // OCP FP8: c10's conversions are torch's CPU cast (nearest even, subnormals kept, no saturation)
+    case at::kFloat8_e4m3fn: return reduce_typed<c10::Float8_e4m3fn, float>(dst, srcs, n, count, op, avg_div);
+    case at::kFloat8_e5m2: return reduce_typed<c10::Float8_e5m2, float>(dst, srcs, n, count, op, avg_div);
     default:
       throw std::runtime_error(std::string("pdcc: unsupported dtype for CPU reduction: ") + c10::toString(t));
   }

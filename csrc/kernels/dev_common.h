@@ -1,7 +1,7 @@
 // Device-side building blocks shared by every gfx950 kernel in this library.
 //
 //  * element traits + reduction functors (SUM/AVG/PROD/MIN/MAX/BAND/BOR/BXOR),
-//    bf16/f16 accumulate in f32 across ALL sources and round once;
+//    bf16/f16/fp8 accumulate in f32 across ALL sources and round once;
 //  * `pipe_run`: the LDS-DMA streaming engine. Each wave64 moves 1 KiB per source
 //    per tile with `global_load_lds_dwordx4` into a DEPTH-deep ring in LDS, waits
 //    with a counted `s_waitcnt vmcnt(N)` (never 0 in steady state), reads its own
@@ -132,6 +132,28 @@ PDCC_INT_TR(DType::I32, int32_t)
 PDCC_INT_TR(DType::I64, int64_t)
 #undef PDCC_INT_TR
 
+// OCP 8-bit floats: gfx950 converts them in pairs, one dword at a time. `widen` takes the low
+// (HI = false) or high word of a dword of four elements to two floats (v_cvt_pk_f32_fp8 / _bf8);
+// `narrow` rounds two floats (nearest even, subnormals kept) into the low or high word of `old`
+// (v_cvt_pk_fp8_f32 / _bf8_f32). reduce_vec works on these pairs, never on single bytes.
+typedef float f32x2 __attribute__((ext_vector_type(2)));
+template <> struct Tr<DType::F8E4M3> {
+  using S = uint8_t; using C = float; static constexpr bool kFloat = true;
+  template <bool HI> __device__ static f32x2 widen(uint32_t w) { return __builtin_amdgcn_cvt_pk_f32_fp8((int)w, HI); }
+  template <bool HI> __device__ static uint32_t narrow(C a, C b, uint32_t old) {
+    return (uint32_t)__builtin_amdgcn_cvt_pk_fp8_f32(a, b, (int)old, HI);
+  }
+};
+template <> struct Tr<DType::F8E5M2> {
+  using S = uint8_t; using C = float; static constexpr bool kFloat = true;
+  template <bool HI> __device__ static f32x2 widen(uint32_t w) { return __builtin_amdgcn_cvt_pk_f32_bf8((int)w, HI); }
+  template <bool HI> __device__ static uint32_t narrow(C a, C b, uint32_t old) {
+    return (uint32_t)__builtin_amdgcn_cvt_pk_bf8_f32(a, b, (int)old, HI);
+  }
+};
+template <DType DT>
+constexpr bool kPackedF8 = DT == DType::F8E4M3 || DT == DType::F8E5M2;
+
 template <RedOp OP, class C>
 __device__ __forceinline__ C apply_op(C a, C b) {
   if constexpr (OP == RedOp::SUM || OP == RedOp::AVG) return a + b;
@@ -150,6 +172,37 @@ template <DType DT, RedOp OP, int NSRC>
 __device__ __forceinline__ uint4 reduce_vec(const uint4 (&v)[NSRC], int avg_div) {
   if constexpr (OP == RedOp::COPY) {
     return v[0];
+  } else if constexpr (kPackedF8<DT>) {
+    // per dword: two packed converts widen its four elements, the fold runs in f32 in source
+    // order, two packed converts round the four results once
+    using T = Tr<DT>;
+    float acc[16];
+    auto widen4 = [](const uint4& x, float (&f)[16]) {
+      const uint32_t w[4] = {x.x, x.y, x.z, x.w};
+#pragma unroll
+      for (int d = 0; d < 4; ++d) {
+        const f32x2 lo = T::template widen<false>(w[d]), hi = T::template widen<true>(w[d]);
+        f[4 * d + 0] = lo[0]; f[4 * d + 1] = lo[1]; f[4 * d + 2] = hi[0]; f[4 * d + 3] = hi[1];
+      }
+    };
+    widen4(v[0], acc);
+#pragma unroll
+    for (int k = 1; k < NSRC; ++k) {
+      float f[16];
+      widen4(v[k], f);
+#pragma unroll
+      for (int e = 0; e < 16; ++e) acc[e] = apply_op<OP, float>(acc[e], f[e]);
+    }
+    if constexpr (OP == RedOp::AVG) {
+#pragma unroll
+      for (int e = 0; e < 16; ++e) acc[e] = acc[e] / (float)avg_div;
+    }
+    uint32_t r[4];
+#pragma unroll
+    for (int d = 0; d < 4; ++d)
+      r[d] = T::template narrow<true>(acc[4 * d + 2], acc[4 * d + 3],
+                                      T::template narrow<false>(acc[4 * d + 0], acc[4 * d + 1], 0u));
+    return make_uint4(r[0], r[1], r[2], r[3]);
   } else {
     using T = Tr<DT>;
     using S = typename T::S;

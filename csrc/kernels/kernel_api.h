@@ -23,7 +23,14 @@ constexpr int kMaxBlocks = 1024;    // per-block pairwise flags in the signal ar
 constexpr int kTileBytes = 4096;    // 256 lanes x 16 B: the unit every engine moves
 constexpr int kBlockThreads = 256;  // 4 wave64s
 
-enum class DType : int32_t { F32 = 0, F16, BF16, F64, I8, U8, I32, I64, BOOL, kCount };
+// F8E4M3 / F8E5M2 are the OCP 8-bit floats (torch.float8_e4m3fn / float8_e5m2; not the gfx942 fnuz
+// formats). They are numbered from kCount on, and kCount keeps its value: tests/native/ipc_plan_dump.cpp
+// sizes its name table by it and walks `dt < kCount` against a recorded golden, so the first nine
+// values and their count are fixed. kEnd is the real end marker.
+enum class DType : int32_t {
+  F32 = 0, F16, BF16, F64, I8, U8, I32, I64, BOOL, kCount,
+  F8E4M3 = kCount, F8E5M2, kEnd
+};
 enum class RedOp : int32_t { SUM = 0, AVG, PROD, MIN, MAX, BAND, BOR, BXOR, COPY, kCount };
 
 inline size_t dtype_size(DType t) {
@@ -37,6 +44,8 @@ inline size_t dtype_size(DType t) {
     case DType::I32: return 4;
     case DType::I64: return 8;
     case DType::BOOL: return 1;
+    case DType::F8E4M3: return 1;
+    case DType::F8E5M2: return 1;
     default: return 0;
   }
 }
@@ -44,7 +53,8 @@ inline size_t dtype_size(DType t) {
 // true iff the (dtype, op) pair has a device kernel
 inline bool supports(DType t, RedOp op) {
   if (op == RedOp::COPY) return true;
-  const bool is_float = t == DType::F32 || t == DType::F16 || t == DType::BF16 || t == DType::F64;
+  const bool is_float = t == DType::F32 || t == DType::F16 || t == DType::BF16 || t == DType::F64 ||
+                        t == DType::F8E4M3 || t == DType::F8E5M2;
   const bool is_int = t == DType::I8 || t == DType::U8 || t == DType::I32 || t == DType::I64;
   if (t == DType::BOOL) return op == RedOp::MAX || op == RedOp::MIN || op == RedOp::BAND || op == RedOp::BOR ||
                                op == RedOp::BXOR || op == RedOp::SUM || op == RedOp::PROD;

@@ -1,7 +1,7 @@
 // K1 (standalone N-way reduce) and the reduction family of the IPC collectives,
 // templated on (dtype, op, #sources). Included once per dtype by reduce_<dt>.hip,
-// which instantiates PDCC_REDUCE_DTYPE(<dt>) -- 8 small TUs that hipcc builds in
-// parallel instead of one huge one.
+// which instantiates PDCC_REDUCE_DTYPE(<dt>) -- one small TU per dtype that hipcc
+// builds in parallel instead of one huge one.
 #pragma once
 #include <cstdlib>
 
@@ -1017,7 +1017,7 @@ __global__ void __launch_bounds__(256) k_ll_alltoall(IpcView v, IpcCall c) {
   hipError_t k1_dispatch_##DTNAME(const void* const* srcs, int n, void* out, size_t nb, RedOp op,    \
                                   int avg_div, hipStream_t s, int grid, int lds);                    \
   hipError_t ipc_dispatch_##DTNAME(const IpcView& v, const IpcCall& c, hipStream_t s, const kern::IpcPlan& p);
-#define PDCC_FOR_DTYPES(X) X(F32) X(F16) X(BF16) X(F64) X(I8) X(U8) X(I32) X(I64)
+#define PDCC_FOR_DTYPES(X) X(F32) X(F16) X(BF16) X(F64) X(I8) X(U8) X(I32) X(I64) X(F8E4M3) X(F8E5M2)
 PDCC_FOR_DTYPES(PDCC_DECL_DISPATCH)
 #undef PDCC_DECL_DISPATCH
 

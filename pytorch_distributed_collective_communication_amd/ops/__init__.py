@@ -2,7 +2,10 @@
 
 * :func:`reduce_nway` -- K1: ``out = op(srcs[0], ..., srcs[k-1])`` for 1..8
   same-shaped GPU tensors; ``op`` in sum/avg/prod/min/max (+ band/bor/bxor for
-  integers). Default implementation stages tiles through LDS with
+  integers). Floats include the OCP FP8 dtypes ``float8_e4m3fn`` / ``float8_e5m2``:
+  like bf16 / f16 they are widened to fp32, folded in source order and rounded
+  once (torch's CPU cast: nearest even, no saturation), with the gfx950 packed
+  converts. Default implementation stages tiles through LDS with
   ``global_load_lds_dwordx4`` (LDS-DMA ring); ``impl="regs"`` is the
   register-staged variant kept for A/B measurement; a ``_nt`` suffix
   (``"lds_nt"``, ``"regs_nt"``) makes the destination stores non-temporal.
@@ -57,7 +60,8 @@ def reduce_nway(srcs: Sequence[torch.Tensor], out: torch.Tensor | None = None, o
 
 
 def reduce_nway_reference(srcs: Sequence[torch.Tensor], op: str = "sum") -> torch.Tensor:
-    """Plain-PyTorch reference of :func:`reduce_nway` (f32 accumulation for floats)."""
+    """Plain-PyTorch reference of :func:`reduce_nway` (f32 accumulation for floats, FP8 included:
+    one cast back at the end)."""
     srcs = list(srcs)
     dt = srcs[0].dtype
     fl = dt.is_floating_point

@@ -1,0 +1,174 @@
+"""Rank functions of the FP8 (float8_e4m3fn / float8_e5m2) reduction tests.
+
+Contract under test: every source element widened to fp32, the W sources folded in rank order in
+fp32, AVG divided by W in fp32, the result rounded to FP8 once -- "rounded" being torch's CPU cast of
+an fp32 tensor (nearest even, subnormals kept, no saturation). The CPU fold below is the only
+reference: results must equal it as values (NaN where it is NaN).
+"""
+import torch
+
+FP8 = {"float8_e4m3fn": torch.float8_e4m3fn, "float8_e5m2": torch.float8_e5m2}
+OPS = ("SUM", "AVG", "PRODUCT", "MAX", "MIN")
+
+
+def _dev(device: str):
+    if device == "cpu":
+        return torch.device("cpu")
+    return torch.device("cuda", torch.cuda.current_device())
+
+
+def fold(xs, op, dt):
+    """The reference: fp32 fold of the CPU tensors `xs` in list order, one CPU cast to `dt`."""
+    acc = xs[0].float()
+    for x in xs[1:]:
+        s = x.float()
+        if op in ("SUM", "AVG"):
+            acc = acc + s
+        elif op == "PRODUCT":
+            acc = acc * s
+        elif op == "MAX":  # compared in fp32, NaN propagates (dev::apply_op)
+            acc = torch.where((acc > s) | acc.isnan(), acc, s)
+        elif op == "MIN":
+            acc = torch.where((acc < s) | acc.isnan(), acc, s)
+        else:
+            raise ValueError(op)
+    if op == "AVG":
+        acc = acc / float(len(xs))
+    assert acc.dtype == torch.float32
+    return acc.to(dt)
+
+
+def same(got, ref):
+    """Equal as values: ±0 and the NaN encodings do not matter, NaN positions do."""
+    g, r = got.detach().cpu(), ref.detach().cpu()
+    return (g.dtype == r.dtype and g.shape == r.shape
+            and bool(torch.allclose(g.float(), r.float(), rtol=0, atol=0, equal_nan=True)))
+
+
+def make_inputs(n, dt, seed, world, lo, hi, tail_pair=False):
+    """Every rank's input (CPU, so each rank can regenerate all of them): seeded values in
+    [lo, hi]; element 0 of rank 0 is NaN; element 1 of every rank is the format's largest finite
+    value (SUM overflows there). `tail_pair`: the same pair once more at the end of the buffer --
+    the largest finite value at n - 2 on every rank, NaN at n - 1 on the last rank."""
+    big = torch.finfo(dt).max
+    xs = []
+    for r in range(world):
+        g = torch.Generator().manual_seed(seed + 31 * r)
+        x = lo + (hi - lo) * torch.rand(n, generator=g)
+        if n > 1:
+            x[1] = big
+        if tail_pair and n >= 4:
+            x[n - 2] = big
+            if r == world - 1:
+                x[n - 1] = float("nan")
+        if r == 0:
+            x[0] = float("nan")
+        xs.append(x.to(dt))
+    return xs
+
+
+def reductions(rank, size, device="cpu", sizes=(1, 1000), tail_pair=False):
+    """all_reduce with the five ops, reduce to the last rank (non-root inputs unchanged) and
+    reduce_scatter_tensor (SUM) on both FP8 dtypes at every size of `sizes` (elements = bytes),
+    each compared exactly with the CPU fold. Returns {case: [ok, engine label]}."""
+    import torch.distributed as dist
+
+    d = _dev(device)
+    label = lambda: ""  # noqa: E731
+    if d.type == "cuda":
+        from pytorch_distributed_collective_communication_amd.parallel import backend as be
+
+        label = be.native_backend(None, "cuda").last_algo
+    root = size - 1 if d.type == "cuda" else 1
+    out = {}
+    for dtn, dt in FP8.items():
+        for n in sizes:
+            seed = 7 + n % 997
+            xs = make_inputs(n, dt, seed, size, -4.0, 4.0, tail_pair)
+            xp = make_inputs(n, dt, seed + 5, size, 0.5, 1.5, tail_pair) if size >= 4 else xs
+            for op in OPS:
+                src = xp if op == "PRODUCT" else xs
+                t = src[rank].clone().to(d)
+                dist.all_reduce(t, op=getattr(dist.ReduceOp, op))
+                out[f"all_reduce/{dtn}/{op}/{n}"] = [same(t, fold(src, op, dt)), label()]
+            t = xs[rank].clone().to(d)
+            dist.reduce(t, dst=root, op=dist.ReduceOp.SUM)
+            want = fold(xs, "SUM", dt) if rank == root else xs[rank]
+            out[f"reduce/{dtn}/SUM/{n}"] = [same(t, want), label()]
+            # W chunks of m elements per rank (on the GPU the total stays at the protocol's size)
+            m = n if d.type == "cpu" else max(1, n // size)
+            ys = make_inputs(size * m, dt, seed + 11, size, -4.0, 4.0, tail_pair)
+            o = torch.empty(m, dtype=dt, device=d)
+            dist.reduce_scatter_tensor(o, ys[rank].clone().to(d))
+            mine = [y[rank * m:(rank + 1) * m] for y in ys]
+            out[f"reduce_scatter/{dtn}/SUM/{m}"] = [same(o, fold(mine, "SUM", dt)), label()]
+    dist.barrier()
+    return out
+
+
+def cpu_reductions(rank, size, device="cpu"):
+    """`reductions` on CPU tensors (the shm transport), then: BXOR on FP8 raises the bitwise-dtype
+    message on every rank, and the group still works afterwards."""
+    import torch.distributed as dist
+
+    out = reductions(rank, size, "cpu", (1, 1000))
+    for dtn, dt in FP8.items():
+        t = torch.ones(8).to(dt)
+        try:
+            dist.all_reduce(t, op=dist.ReduceOp.BXOR)
+            out[f"bxor/{dtn}"] = [False, "no error"]
+        except RuntimeError as e:
+            out[f"bxor/{dtn}"] = ["bitwise reductions need an integer dtype" in str(e), str(e)[:200]]
+    t = torch.full((5,), float(rank + 1))
+    dist.all_reduce(t)
+    out["after/float32"] = [bool(torch.all(t == size * (size + 1) / 2)), ""]
+    t = torch.full((5,), 1.5).to(torch.float8_e5m2)
+    dist.all_reduce(t)
+    out["after/float8_e5m2"] = [bool(torch.all(t.float() == 1.5 * size)), ""]
+    return out
+
+
+def host_engine(rank, size, device="cuda", n=4099):
+    """The GPU `host` engine (PDCC_ALGO=host): all_reduce SUM and MAX of n bytes."""
+    import torch.distributed as dist
+
+    from pytorch_distributed_collective_communication_amd.parallel import backend as be
+
+    d = _dev(device)
+    gb = be.native_backend(None, "cuda")
+    out = {}
+    for dtn, dt in FP8.items():
+        xs = make_inputs(n, dt, 19, size, -4.0, 4.0)
+        for op in ("SUM", "MAX"):
+            t = xs[rank].to(d)
+            dist.all_reduce(t, op=getattr(dist.ReduceOp, op))
+            out[f"all_reduce/{dtn}/{op}/{n}"] = [same(t, fold(xs, op, dt)), gb.last_algo()]
+    dist.barrier()
+    return out
+
+
+def default_selection(rank, size, device="cuda", sizes=(4096, 4 << 20)):
+    """No forced engine: the static choice and the autotuner pick for FP8 SUM. Two calls per size
+    (the first one of a tuned bucket runs the race). Finite data only: the tuner's cross-engine
+    check compares values, and NaN never equals NaN there.
+    Returns {"cases": {case: [ok, engine]}, "table": the autotuner's rows}."""
+    import torch.distributed as dist
+
+    from pytorch_distributed_collective_communication_amd.parallel import backend as be
+
+    d = _dev(device)
+    gb = be.native_backend(None, "cuda")
+    cases = {}
+    for dtn, dt in FP8.items():
+        for n in sizes:
+            xs = []
+            for r in range(size):
+                g = torch.Generator().manual_seed(3 + n % 997 + 31 * r)
+                xs.append((-2.0 + 4.0 * torch.rand(n, generator=g)).to(dt))
+            want = fold(xs, "SUM", dt)
+            for k in range(2):
+                t = xs[rank].to(d)
+                dist.all_reduce(t)
+                cases[f"all_reduce/{dtn}/SUM/{n}/{k}"] = [same(t, want), gb.last_algo()]
+    dist.barrier()
+    return {"cases": cases, "table": be.autotune_table()}
