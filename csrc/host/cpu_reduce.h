@@ -22,16 +22,40 @@ namespace host {
 
 using RedOpType = c10d::ReduceOp::RedOpType;
 
+// Integer SUM / PRODUCT wrap (two's complement at the element width), as on the device: signed types
+// are computed in the unsigned type of the same width, where overflow is defined, and converted back.
+template <class T>
+inline T wrap_add(T a, T b) {
+  if constexpr (std::is_integral_v<T> && std::is_signed_v<T>) {
+    using U = std::make_unsigned_t<T>;
+    return static_cast<T>(static_cast<U>(static_cast<U>(a) + static_cast<U>(b)));
+  } else {
+    return a + b;
+  }
+}
+template <class T>
+inline T wrap_mul(T a, T b) {
+  if constexpr (std::is_integral_v<T> && std::is_signed_v<T>) {
+    using U = std::make_unsigned_t<T>;
+    // The unsigned images of int8 / int16 operands would promote to (signed) int, where the product of two
+    // 16-bit images can overflow: types narrower than int are multiplied in `unsigned` instead.
+    using W = std::conditional_t<(sizeof(U) < sizeof(unsigned)), unsigned, U>;
+    return static_cast<T>(static_cast<U>(static_cast<W>(static_cast<U>(a)) * static_cast<W>(static_cast<U>(b))));
+  } else {
+    return a * b;
+  }
+}
+
 template <class T>
 inline T op_apply(RedOpType op, T a, T b) {
   switch (op) {
     case RedOpType::SUM:
     case RedOpType::AVG:
       if constexpr (std::is_same_v<T, bool>) return a || b;
-      else return a + b;
+      else return wrap_add(a, b);
     case RedOpType::PRODUCT:
       if constexpr (std::is_same_v<T, bool>) return a && b;
-      else return a * b;
+      else return wrap_mul(a, b);
     case RedOpType::MAX: return (a > b || a != a) ? a : b;
     case RedOpType::MIN: return (a < b || a != a) ? a : b;
     case RedOpType::BAND:
@@ -65,11 +89,11 @@ void reduce_typed(void* dst_v, const void* const* srcs_v, int n, size_t count, R
         case RedOpType::SUM:
         case RedOpType::AVG:
           if constexpr (std::is_same_v<C, bool>) { for (size_t i = 0; i < m; ++i) acc[i] = acc[i] || (bool)sk[i]; }
-          else { for (size_t i = 0; i < m; ++i) acc[i] += static_cast<C>(sk[i]); }
+          else { for (size_t i = 0; i < m; ++i) acc[i] = wrap_add(acc[i], static_cast<C>(sk[i])); }
           break;
         case RedOpType::PRODUCT:
           if constexpr (std::is_same_v<C, bool>) { for (size_t i = 0; i < m; ++i) acc[i] = acc[i] && (bool)sk[i]; }
-          else { for (size_t i = 0; i < m; ++i) acc[i] *= static_cast<C>(sk[i]); }
+          else { for (size_t i = 0; i < m; ++i) acc[i] = wrap_mul(acc[i], static_cast<C>(sk[i])); }
           break;
         default:
           for (size_t i = 0; i < m; ++i) acc[i] = op_apply<C>(op, acc[i], static_cast<C>(sk[i]));

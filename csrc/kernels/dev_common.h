@@ -18,6 +18,8 @@
 #include <stddef.h>
 #include <stdint.h>
 
+#include <type_traits>
+
 #include "kernel_api.h"
 
 namespace pdcc {
@@ -154,10 +156,16 @@ template <> struct Tr<DType::F8E5M2> {
 template <DType DT>
 constexpr bool kPackedF8 = DT == DType::F8E4M3 || DT == DType::F8E5M2;
 
+// Integer SUM / PROD wrap (two's complement at the element width): signed types are computed in the
+// unsigned type of the same width, where overflow is defined, and converted back.
+template <class C, bool = std::is_integral_v<C>> struct wrap_of { using U = C; };
+template <class C> struct wrap_of<C, true> { using U = std::make_unsigned_t<C>; };
+
 template <RedOp OP, class C>
 __device__ __forceinline__ C apply_op(C a, C b) {
-  if constexpr (OP == RedOp::SUM || OP == RedOp::AVG) return a + b;
-  else if constexpr (OP == RedOp::PROD) return a * b;
+  using U = typename wrap_of<C>::U;
+  if constexpr (OP == RedOp::SUM || OP == RedOp::AVG) return (C)(U)((U)a + (U)b);
+  else if constexpr (OP == RedOp::PROD) return (C)(U)((U)a * (U)b);
   else if constexpr (OP == RedOp::MAX) return (a > b || a != a) ? a : b;  // NaN propagates
   else if constexpr (OP == RedOp::MIN) return (a < b || a != a) ? a : b;
   else if constexpr (OP == RedOp::BAND) return a & b;

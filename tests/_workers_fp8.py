@@ -3,11 +3,14 @@
 Contract under test: every source element widened to fp32, the W sources folded in rank order in
 fp32, AVG divided by W in fp32, the result rounded to FP8 once -- "rounded" being torch's CPU cast of
 an fp32 tensor (nearest even, subnormals kept, no saturation). The CPU fold below is the only
-reference: results must equal it as values (NaN where it is NaN).
+reference (tests/_exact.py `fold`): results must equal it as values (NaN where it is NaN).
 """
 import torch
 
-FP8 = {"float8_e4m3fn": torch.float8_e4m3fn, "float8_e5m2": torch.float8_e5m2}
+# the reference and the comparison of every dtype; FP8 is its narrow-float case
+from tests._exact import fold, same  # noqa: F401
+
+FP8 ={"float8_e4m3fn": torch.float8_e4m3fn, "float8_e5m2": torch.float8_e5m2}
 OPS = ("SUM", "AVG", "PRODUCT", "MAX", "MIN")
 
 
@@ -15,34 +18,6 @@ def _dev(device: str):
     if device == "cpu":
         return torch.device("cpu")
     return torch.device("cuda", torch.cuda.current_device())
-
-
-def fold(xs, op, dt):
-    """The reference: fp32 fold of the CPU tensors `xs` in list order, one CPU cast to `dt`."""
-    acc = xs[0].float()
-    for x in xs[1:]:
-        s = x.float()
-        if op in ("SUM", "AVG"):
-            acc = acc + s
-        elif op == "PRODUCT":
-            acc = acc * s
-        elif op == "MAX":  # compared in fp32, NaN propagates (dev::apply_op)
-            acc = torch.where((acc > s) | acc.isnan(), acc, s)
-        elif op == "MIN":
-            acc = torch.where((acc < s) | acc.isnan(), acc, s)
-        else:
-            raise ValueError(op)
-    if op == "AVG":
-        acc = acc / float(len(xs))
-    assert acc.dtype == torch.float32
-    return acc.to(dt)
-
-
-def same(got, ref):
-    """Equal as values: ±0 and the NaN encodings do not matter, NaN positions do."""
-    g, r = got.detach().cpu(), ref.detach().cpu()
-    return (g.dtype == r.dtype and g.shape == r.shape
-            and bool(torch.allclose(g.float(), r.float(), rtol=0, atol=0, equal_nan=True)))
 
 
 def make_inputs(n, dt, seed, world, lo, hi, tail_pair=False):
