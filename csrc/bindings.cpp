@@ -12,6 +12,7 @@
 #include "backend/process_group.h"
 #include "device/comm_util.h"
 #include "kernels/kernel_api.h"
+#include "kernels/mx_layout.h"
 
 namespace py = pybind11;
 
@@ -88,6 +89,85 @@ void multi_copy(const std::vector<at::Tensor>& srcs, const std::vector<at::Tenso
   hipStream_t s = c10::hip::getCurrentHIPStreamMasqueradingAsCUDA(srcs[0].device().index()).stream();
   hipError_t e = pdcc::kern::multi_copy(d.data(), (int)d.size(), s, max_blocks, depth, ntl);
   TORCH_CHECK(e == hipSuccess, "multi_copy launch failed: ", hipGetErrorString(e));
+}
+
+// ---- block-scaled FP8 wire (kernels/mx_wire.hip). The kernels want contiguous, 16-byte aligned
+// buffers: any other tensor goes through a contiguous copy (inputs) or is filled from one (outputs).
+at::Tensor mx_in(const at::Tensor& t) {
+  if (t.is_contiguous() && al16(t.data_ptr())) return t;
+  at::Tensor c = at::empty_like(t, at::MemoryFormat::Contiguous);
+  c.copy_(t);
+  return c;
+}
+at::Tensor mx_out(const at::Tensor& t) {
+  if (t.is_contiguous() && al16(t.data_ptr())) return t;
+  return at::empty_like(t, at::MemoryFormat::Contiguous);
+}
+pdcc::kern::DType mx_dtype(const at::Tensor& t, const char* who) {
+  TORCH_CHECK_TYPE(t.scalar_type() == at::kFloat || t.scalar_type() == at::kBFloat16 || t.scalar_type() == at::kHalf,
+                   who, ": float32, bfloat16 or float16 tensors only, got ", t.scalar_type());
+  return kdtype(t.scalar_type());
+}
+void mx_check_wire(const at::Tensor& w, const char* who) {
+  TORCH_CHECK(w.is_cuda() && w.scalar_type() == at::kByte && w.dim() == 1, who, ": the wire is a 1-d uint8 GPU tensor");
+}
+
+at::Tensor mx_quantize(const at::Tensor& x, int world, const c10::optional<at::Tensor>& out) {
+  TORCH_CHECK(x.is_cuda(), "mx_quantize: GPU tensors only");
+  TORCH_CHECK(world >= 1, "mx_quantize: world must be >= 1");
+  const auto d = mx_dtype(x, "mx_quantize");
+  const size_t numel = (size_t)x.numel();
+  const size_t cb = pdcc::kern::mx_chunk_blocks(numel, world);
+  const int64_t bytes = (int64_t)pdcc::kern::mx_wire_bytes(cb, (size_t)world);
+  c10::hip::HIPGuardMasqueradingAsCUDA g(x.device());
+  at::Tensor wire = out ? *out : at::empty({bytes}, x.options().dtype(at::kByte));
+  mx_check_wire(wire, "mx_quantize");
+  TORCH_CHECK(wire.device() == x.device() && wire.numel() == bytes, "mx_quantize: out must hold ", bytes, " bytes on ",
+              x.device());
+  at::Tensor src = mx_in(x), w = mx_out(wire);
+  hipStream_t s = c10::hip::getCurrentHIPStreamMasqueradingAsCUDA(x.device().index()).stream();
+  hipError_t e = pdcc::kern::mx_quantize(src.data_ptr(), numel, d, w.data_ptr(), cb, (size_t)world, s);
+  TORCH_CHECK(e == hipSuccess, "mx_quantize launch failed: ", hipGetErrorString(e));
+  if (!w.is_same(wire)) wire.copy_(w);
+  return wire;
+}
+
+at::Tensor mx_reduce(const at::Tensor& wire, int nsrc, const std::string& op, const c10::optional<at::Tensor>& out) {
+  mx_check_wire(wire, "mx_reduce");
+  TORCH_CHECK(nsrc >= 1 && nsrc <= pdcc::kern::kMaxRanks, "mx_reduce: 1..8 sources");
+  TORCH_CHECK_VALUE(op == "sum" || op == "avg", "mx_reduce: op must be 'sum' or 'avg', got '", op, "'");
+  const int64_t chunk = wire.numel() / nsrc;
+  TORCH_CHECK(chunk > 0 && chunk * nsrc == wire.numel() && chunk % (33 * 16) == 0, "mx_reduce: ", wire.numel(),
+              " bytes are not ", nsrc, " chunk wires (33 bytes per block, blocks in groups of 16)");
+  const size_t cb = (size_t)chunk / 33;
+  c10::hip::HIPGuardMasqueradingAsCUDA g(wire.device());
+  at::Tensor res = out ? *out : at::empty({chunk}, wire.options());
+  mx_check_wire(res, "mx_reduce");
+  TORCH_CHECK(res.device() == wire.device() && res.numel() == chunk, "mx_reduce: out must hold ", chunk, " bytes");
+  at::Tensor in = mx_in(wire), o = mx_out(res);
+  hipStream_t s = c10::hip::getCurrentHIPStreamMasqueradingAsCUDA(wire.device().index()).stream();
+  hipError_t e = pdcc::kern::mx_reduce(in.data_ptr(), nsrc, cb, kop(op), nsrc, o.data_ptr(), s);
+  TORCH_CHECK(e == hipSuccess, "mx_reduce launch failed: ", hipGetErrorString(e));
+  if (!o.is_same(res)) res.copy_(o);
+  return res;
+}
+
+void mx_dequantize(const at::Tensor& wire, int world, at::Tensor& out) {
+  mx_check_wire(wire, "mx_dequantize");
+  TORCH_CHECK(world >= 1, "mx_dequantize: world must be >= 1");
+  TORCH_CHECK(out.is_cuda() && out.device() == wire.device(), "mx_dequantize: out must be on the wire's GPU");
+  const auto d = mx_dtype(out, "mx_dequantize");
+  const size_t numel = (size_t)out.numel();
+  const size_t cb = pdcc::kern::mx_chunk_blocks(numel, world);
+  TORCH_CHECK((size_t)wire.numel() == pdcc::kern::mx_wire_bytes(cb, (size_t)world), "mx_dequantize: the wire of ",
+              numel, " elements in ", world, " chunks has ", pdcc::kern::mx_wire_bytes(cb, (size_t)world),
+              " bytes, got ", wire.numel());
+  c10::hip::HIPGuardMasqueradingAsCUDA g(wire.device());
+  at::Tensor w = mx_in(wire), o = mx_out(out);
+  hipStream_t s = c10::hip::getCurrentHIPStreamMasqueradingAsCUDA(wire.device().index()).stream();
+  hipError_t e = pdcc::kern::mx_dequantize(w.data_ptr(), cb, (size_t)world, o.data_ptr(), numel, d, s);
+  TORCH_CHECK(e == hipSuccess, "mx_dequantize launch failed: ", hipGetErrorString(e));
+  if (!o.is_same(out)) out.copy_(o);
 }
 
 // Peer links between every pair of visible GPUs, as the runtime reports them: HSA link
@@ -244,6 +324,13 @@ PYBIND11_MODULE(_C, m) {
   m.def("multi_copy", &multi_copy, py::arg("srcs"), py::arg("dsts"), py::arg("max_blocks") = 0, py::arg("depth") = 0,
         py::arg("ntl") = -1,
         "K2: one-launch multi-tensor copy (max_blocks/depth 0 = defaults)");
+  m.def("mx_quantize", &mx_quantize, py::arg("x"), py::arg("world") = 1, py::arg("out") = py::none(),
+        "tensor (f32 / bf16 / f16) -> mxfp8_e4m3 wire of `world` chunks, on the current stream");
+  m.def("mx_reduce", &mx_reduce, py::arg("wire"), py::arg("nsrc"), py::arg("op") = "sum", py::arg("out") = py::none(),
+        "nsrc chunk wires back to back -> one chunk wire (dequantize, fold in f32 in source order, requantize)");
+  m.def("mx_dequantize", &mx_dequantize, py::arg("wire"), py::arg("world"), py::arg("out"),
+        "mxfp8_e4m3 wire of `world` chunks -> out (f32 / bf16 / f16), exactly out.numel() elements");
+  m.def("mx_chunk_blocks", [](int64_t numel, int world) { return (int64_t)pdcc::kern::mx_chunk_blocks((size_t)numel, world); });
   m.def("ipc_signal_bytes", &pdcc::kern::ipc_signal_bytes);
   m.def("device_links", &device_links,
         "peer links between every pair of visible GPUs: link type (xgmi/pcie), hops, p2p, atomics, perf_rank");

@@ -322,5 +322,21 @@ using IpcCall = IpcCallT<RawPtr>;
 size_t ipc_signal_bytes();
 hipError_t ipc_launch(const IpcView& view, const IpcCall& call, hipStream_t stream);
 
+// ---------------------------------------------------------------- block-scaled FP8 wire (mxfp8_e4m3)
+// Layout: mx_layout.h; contract: docs/collectives.md "Compressed all-reduce". Single-GPU streaming
+// kernels (mx_wire.hip). `wire` buffers and the tensors are 16-byte aligned; `cb` (blocks per chunk) is
+// a multiple of 16.
+// Tensor (`t` in F32 / BF16 / F16, `numel` <= 32 cb nchunks elements) -> nchunks chunk wires. Every
+// block of every chunk is written (padding: scale 127, payload 0); nothing past src + numel is read.
+hipError_t mx_quantize(const void* src, size_t numel, DType t, void* wire, size_t cb, size_t nchunks,
+                       hipStream_t stream);
+// `nsrc` (1..kMaxRanks) chunk wires back to back -> one chunk wire: dequantize, fold in f32 in source
+// order (`op` SUM or AVG; AVG divides by avg_div), requantize.
+hipError_t mx_reduce(const void* wire_in, int nsrc, size_t cb, RedOp op, int avg_div, void* wire_out,
+                     hipStream_t stream);
+// nchunks chunk wires -> exactly `numel` elements of `dst`, rounded once to `t`.
+hipError_t mx_dequantize(const void* wire, size_t cb, size_t nchunks, void* dst, size_t numel, DType t,
+                         hipStream_t stream);
+
 }  // namespace kern
 }  // namespace pdcc

@@ -13,6 +13,11 @@
   whole list of tensors (the staging used by gather/scatter/all_gather with
   tensor lists, reference main.py:35-37,51-52,66-68).
 
+* :func:`mx_quantize`, :func:`mx_reduce`, :func:`mx_dequantize` -- the block-scaled FP8 wire format
+  ``mxfp8_e4m3`` (docs/collectives.md "Compressed all-reduce"): 32-element blocks, one E8M0 scale
+  byte and 32 ``float8_e4m3fn`` bytes each. ``parallel/compressed.py`` builds
+  ``all_reduce_compressed`` from them.
+
 Every function runs on the current HIP stream and raises if the native
 extension is missing (no silent eager fallback). ``*_reference`` functions are
 the plain-PyTorch fp32 references the tests compare against.
@@ -127,4 +132,146 @@ def unpack(flat: torch.Tensor, tensors: Sequence[torch.Tensor]) -> None:
     multi_copy(srcs, [_byte_view(t) for t in tensors])
 
 
-__all__ = ["reduce_nway", "reduce_nway_reference", "multi_copy", "pack", "unpack"]
+# ------------------------------------------------------------------ block-scaled FP8 wire (mxfp8_e4m3)
+MX_BLOCK = 32
+MX_DTYPES = (torch.float32, torch.bfloat16, torch.float16)
+
+
+def mx_chunk_blocks(numel: int, world: int = 1) -> int:
+    """Blocks per chunk when ``numel`` elements are dealt to ``world`` chunks (csrc/kernels/mx_layout.h):
+    a multiple of 16, and of 4096 once a chunk's wire reaches 1 MiB."""
+    world = max(1, int(world))
+    blocks = (int(numel) + MX_BLOCK - 1) // MX_BLOCK
+    cb = max(16, ((blocks + world - 1) // world + 15) // 16 * 16)
+    if 33 * cb >= 1 << 20:
+        cb = (cb + 4095) // 4096 * 4096
+    return cb
+
+
+def mx_wire_bytes(numel: int, world: int = 1) -> int:
+    """Bytes of the wire of ``numel`` elements in ``world`` chunks: ``world`` x (32 cb payload + cb scales)."""
+    return 33 * mx_chunk_blocks(numel, world) * max(1, int(world))
+
+
+def _mx_check_dtype(dt, who):
+    if dt not in MX_DTYPES:
+        raise TypeError(f"{who}: float32, bfloat16 or float16 tensors only, got {dt}")
+
+
+def mx_quantize(x: torch.Tensor, world: int = 1, out: torch.Tensor | None = None) -> torch.Tensor:
+    """``x`` (GPU; f32 / bf16 / f16) -> its ``mxfp8_e4m3`` wire: a uint8 tensor of ``world`` chunks of
+    ``[32 cb payload bytes][cb scale bytes]``, padding blocks included (scale 127, payload 0)."""
+    _mx_check_dtype(x.dtype, "mx_quantize")
+    return _C().mx_quantize(x.detach().reshape(-1), int(world), out)
+
+
+def mx_reduce(wire: torch.Tensor, nsrc: int, op: str = "sum", out: torch.Tensor | None = None) -> torch.Tensor:
+    """``nsrc`` (1..8) chunk wires back to back -> one chunk wire: every source dequantized, folded in
+    f32 in source order (``avg``: then divided by ``nsrc``), and quantized again."""
+    if op not in ("sum", "avg"):
+        raise ValueError(f"mx_reduce: op must be 'sum' or 'avg', got {op!r}")
+    return _C().mx_reduce(wire, int(nsrc), op, out)
+
+
+def mx_dequantize(wire: torch.Tensor, numel: int, dtype: torch.dtype = torch.float32, world: int = 1,
+                  out: torch.Tensor | None = None) -> torch.Tensor:
+    """The first ``numel`` elements of a wire of ``world`` chunks, rounded once to ``dtype``; written into
+    ``out`` (``numel`` elements, any shape) when given -- exactly those elements and nothing else."""
+    if out is None:
+        _mx_check_dtype(dtype, "mx_dequantize")
+        out = torch.empty(int(numel), dtype=dtype, device=wire.device)
+    else:
+        _mx_check_dtype(out.dtype, "mx_dequantize")
+        if out.numel() != int(numel):
+            raise ValueError(f"mx_dequantize: out has {out.numel()} elements, numel is {numel}")
+    _C().mx_dequantize(wire, int(world), out)
+    return out
+
+
+def _mx_exp2(e: torch.Tensor) -> torch.Tensor:
+    """2^e as f32 for integer -126 <= e <= 127, built from the exponent field (exact)."""
+    return ((e.to(torch.int32) + 127) << 23).view(torch.float32)
+
+
+def _mx_quantize_blocks(xb: torch.Tensor):
+    """(blocks, 32) f32 -> ((blocks, 32) uint8 payload, (blocks,) uint8 scales), the contract's Q."""
+    amax = xb.abs().amax(dim=1)
+    special = ~torch.isfinite(xb).all(dim=1)
+    zero = (amax == 0) & ~special
+    # amax = m 2^k with 1 <= m < 2: frexp returns m / 2 and k + 1 (for a subnormal amax the true
+    # exponent, below -126 either way: the clamp decides)
+    m, ex = torch.frexp(torch.where(special | zero, torch.ones_like(amax), amax))
+    e = (ex.to(torch.int64) - 1) - 8 + (m > 0.875).to(torch.int64)
+    e = e.clamp(-117, 120)
+    e[zero] = 0
+    q = (xb * _mx_exp2(-e)[:, None]).to(torch.float8_e4m3fn).view(torch.uint8).clone()
+    q[special | zero] = 0
+    s = (e + 127).to(torch.uint8)
+    s[special] = 255
+    return q, s
+
+
+def _mx_dequantize_blocks(q: torch.Tensor, s: torch.Tensor) -> torch.Tensor:
+    """The contract's D: (blocks, 32) payload bytes and (blocks,) scale bytes -> (blocks, 32) f32."""
+    si = s.to(torch.int32)
+    scale = torch.where(si == 0, torch.full_like(si, 0x00400000), si << 23).view(torch.float32).clone()
+    scale[si == 255] = float("nan")
+    return q.view(torch.float8_e4m3fn).to(torch.float32) * scale[:, None]
+
+
+def _mx_split(wire: torch.Tensor, nchunks: int):
+    """Wire of ``nchunks`` chunks -> ((nchunks * cb, 32) payload, (nchunks * cb,) scales)."""
+    if wire.dtype != torch.uint8 or wire.dim() != 1 or wire.numel() % (33 * 16 * nchunks):
+        raise ValueError(f"not a wire of {nchunks} chunks: {wire.dtype}, {tuple(wire.shape)}")
+    cb = wire.numel() // (33 * nchunks)
+    w = wire.view(nchunks, 33 * cb)
+    return w[:, :32 * cb].reshape(nchunks * cb, 32), w[:, 32 * cb:].reshape(nchunks * cb)
+
+
+def _mx_join(q: torch.Tensor, s: torch.Tensor, nchunks: int) -> torch.Tensor:
+    cb = s.numel() // nchunks
+    return torch.cat([q.reshape(nchunks, 32 * cb), s.reshape(nchunks, cb)], dim=1).reshape(-1).contiguous()
+
+
+def mx_quantize_reference(x: torch.Tensor, world: int = 1) -> torch.Tensor:
+    """Plain-PyTorch :func:`mx_quantize` on a CPU tensor, bit for bit the documented contract."""
+    _mx_check_dtype(x.dtype, "mx_quantize_reference")
+    world = max(1, int(world))
+    flat = x.detach().reshape(-1).to(torch.float32)
+    total = mx_chunk_blocks(flat.numel(), world) * world
+    xb = torch.zeros(total * MX_BLOCK, dtype=torch.float32)
+    xb[:flat.numel()] = flat
+    q, s = _mx_quantize_blocks(xb.view(total, MX_BLOCK))
+    return _mx_join(q, s, world)
+
+
+def mx_reduce_reference(wire: torch.Tensor, nsrc: int, op: str = "sum") -> torch.Tensor:
+    """Plain-PyTorch :func:`mx_reduce` on a CPU wire."""
+    if op not in ("sum", "avg"):
+        raise ValueError(f"mx_reduce_reference: op must be 'sum' or 'avg', got {op!r}")
+    q, s = _mx_split(wire, nsrc)
+    cb = s.numel() // nsrc
+    d = _mx_dequantize_blocks(q, s).view(nsrc, cb, MX_BLOCK)
+    acc = d[0].clone()
+    for r in range(1, nsrc):
+        acc = acc + d[r]
+    if op == "avg":
+        acc = acc / torch.tensor(float(nsrc), dtype=torch.float32)
+    return _mx_join(*_mx_quantize_blocks(acc), 1)
+
+
+def mx_dequantize_reference(wire: torch.Tensor, numel: int, dtype: torch.dtype = torch.float32,
+                            world: int = 1) -> torch.Tensor:
+    """Plain-PyTorch :func:`mx_dequantize` on a CPU wire."""
+    _mx_check_dtype(dtype, "mx_dequantize_reference")
+    world = max(1, int(world))
+    if wire.numel() != mx_wire_bytes(numel, world):
+        raise ValueError(f"the wire of {numel} elements in {world} chunks has {mx_wire_bytes(numel, world)} bytes, "
+                         f"got {wire.numel()}")
+    q, s = _mx_split(wire, world)
+    return _mx_dequantize_blocks(q, s).reshape(-1)[:int(numel)].to(dtype)
+
+
+__all__ = ["reduce_nway", "reduce_nway_reference", "multi_copy", "pack", "unpack",
+           "mx_quantize", "mx_reduce", "mx_dequantize", "mx_chunk_blocks", "mx_wire_bytes",
+           "mx_quantize_reference", "mx_reduce_reference", "mx_dequantize_reference"]

@@ -23,7 +23,10 @@ contract, MI355X-first:
   only accumulate into ``.grad``; the first backward after it launches the
   reduction of the accumulated gradients. A second backward before
   :meth:`finish` (outside ``no_sync``) raises instead of silently dropping a
-  micro-batch.
+  micro-batch;
+* ``wire="mxfp8_e4m3"``: every bucket goes through ``all_reduce_compressed`` (block-scaled FP8 on
+  the links, f32 sums, AVG; parallel/compressed.py) instead of ``dist.all_reduce``. The default
+  ``wire=None`` is the exact path above.
 
 ``broadcast_parameters`` and ``scatter_batch`` cover the other two uses.
 torch's own ``DistributedDataParallel`` also runs unchanged on this backend.
@@ -73,7 +76,15 @@ class GradBucketer:
     """Overlapped, bucketed gradient all-reduce (average) for one module."""
 
     def __init__(self, module: torch.nn.Module, group=None, bucket_bytes: int = 256 << 20,
-                 average: bool = True):
+                 average: bool = True, wire: str | None = None):
+        if wire is not None:
+            from .compressed import WIRES
+
+            if wire not in WIRES:
+                raise ValueError(f"GradBucketer: unknown wire format {wire!r} (supported: {', '.join(WIRES)})")
+            if not average:
+                raise ValueError("GradBucketer: a compressed wire averages (average=True)")
+        self.wire = wire
         self.group = group
         self.average = average
         self.world = dist.get_world_size(group)
@@ -93,7 +104,8 @@ class GradBucketer:
             self._add_bucket(cur)
         self._hooks = [p.register_post_accumulate_grad_hook(self._on_grad) for p in params]
         self._sync = True
-        self._fused_avg = average and self.world > 1 and _is_native(group, self.buckets)
+        # (a compressed wire divides before it requantizes: always fused)
+        self._fused_avg = average and self.world > 1 and (wire is not None or _is_native(group, self.buckets))
         self._op = dist.ReduceOp.AVG if self._fused_avg else dist.ReduceOp.SUM
         self._reset()
 
@@ -132,7 +144,14 @@ class GradBucketer:
         b.flat[off:off + p.numel()].copy_(p.grad.reshape(-1))
         b.pending -= 1
         if b.pending == 0:
-            b.work = dist.all_reduce(b.flat, op=self._op, group=self.group, async_op=True)
+            b.work = self._reduce(b)
+
+    def _reduce(self, b: _Bucket):
+        if self.wire is not None:
+            from .compressed import all_reduce_compressed
+
+            return all_reduce_compressed(b.flat, dist.ReduceOp.AVG, group=self.group, wire=self.wire, async_op=True)
+        return dist.all_reduce(b.flat, op=self._op, group=self.group, async_op=True)
 
     def finish(self) -> None:
         """Wait for every bucket, average, and write the result back into ``.grad``."""
@@ -143,7 +162,7 @@ class GradBucketer:
                         p.grad = torch.zeros_like(p)
                 for p, off in zip(b.params, b.offsets):
                     b.flat[off:off + p.numel()].copy_(p.grad.reshape(-1))
-                b.work = dist.all_reduce(b.flat, op=self._op, group=self.group, async_op=True)
+                b.work = self._reduce(b)
         for b in self.buckets:
             b.work.wait()
             if self.average and self.world > 1 and not self._fused_avg:
