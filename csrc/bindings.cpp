@@ -170,6 +170,69 @@ void mx_dequantize(const at::Tensor& wire, int world, at::Tensor& out) {
   if (!o.is_same(out)) out.copy_(o);
 }
 
+// ---- the shard layout (kernels/mx_layout.h): chunk r is shard r of `numel / world` elements
+at::Tensor mx_quantize_shards(const at::Tensor& x, int world, const c10::optional<at::Tensor>& out) {
+  TORCH_CHECK(x.is_cuda(), "mx_quantize_shards: GPU tensors only");
+  TORCH_CHECK(world >= 1 && world <= 65535, "mx_quantize_shards: world must be 1..65535");
+  const auto d = mx_dtype(x, "mx_quantize_shards");
+  TORCH_CHECK_VALUE(x.numel() > 0 && x.numel() % world == 0, "mx_quantize_shards: ", x.numel(),
+                    " elements are not ", world, " shards of one or more elements");
+  const size_t m = (size_t)x.numel() / (size_t)world;
+  const size_t cb = pdcc::kern::mx_shard_blocks(m);
+  const int64_t bytes = (int64_t)pdcc::kern::mx_shard_wire_bytes(m, (size_t)world);
+  c10::hip::HIPGuardMasqueradingAsCUDA g(x.device());
+  at::Tensor wire = out ? *out : at::empty({bytes}, x.options().dtype(at::kByte));
+  mx_check_wire(wire, "mx_quantize_shards");
+  TORCH_CHECK(wire.device() == x.device() && wire.numel() == bytes, "mx_quantize_shards: out must hold ", bytes,
+              " bytes on ", x.device());
+  at::Tensor src = mx_in(x), w = mx_out(wire);
+  hipStream_t s = c10::hip::getCurrentHIPStreamMasqueradingAsCUDA(x.device().index()).stream();
+  hipError_t e = pdcc::kern::mx_quantize_shards(src.data_ptr(), m, d, w.data_ptr(), cb, (size_t)world, s);
+  TORCH_CHECK(e == hipSuccess, "mx_quantize_shards launch failed: ", hipGetErrorString(e));
+  if (!w.is_same(wire)) wire.copy_(w);
+  return wire;
+}
+
+void mx_dequantize_shards(const at::Tensor& wire, int world, at::Tensor& out) {
+  mx_check_wire(wire, "mx_dequantize_shards");
+  TORCH_CHECK(world >= 1 && world <= 65535, "mx_dequantize_shards: world must be 1..65535");
+  TORCH_CHECK(out.is_cuda() && out.device() == wire.device(), "mx_dequantize_shards: out must be on the wire's GPU");
+  const auto d = mx_dtype(out, "mx_dequantize_shards");
+  TORCH_CHECK_VALUE(out.numel() > 0 && out.numel() % world == 0, "mx_dequantize_shards: ", out.numel(),
+                    " elements are not ", world, " shards of one or more elements");
+  const size_t m = (size_t)out.numel() / (size_t)world;
+  const size_t cb = pdcc::kern::mx_shard_blocks(m);
+  const size_t bytes = pdcc::kern::mx_shard_wire_bytes(m, (size_t)world);
+  TORCH_CHECK((size_t)wire.numel() == bytes, "mx_dequantize_shards: the wire of ", world, " shards of ", m,
+              " elements has ", bytes, " bytes, got ", wire.numel());
+  c10::hip::HIPGuardMasqueradingAsCUDA g(wire.device());
+  at::Tensor w = mx_in(wire), o = mx_out(out);
+  hipStream_t s = c10::hip::getCurrentHIPStreamMasqueradingAsCUDA(wire.device().index()).stream();
+  hipError_t e = pdcc::kern::mx_dequantize_shards(w.data_ptr(), cb, (size_t)world, o.data_ptr(), m, d, s);
+  TORCH_CHECK(e == hipSuccess, "mx_dequantize_shards launch failed: ", hipGetErrorString(e));
+  if (!o.is_same(out)) out.copy_(o);
+}
+
+void mx_fold(const at::Tensor& wire, int nsrc, const std::string& op, at::Tensor& out) {
+  mx_check_wire(wire, "mx_fold");
+  TORCH_CHECK(nsrc >= 1 && nsrc <= pdcc::kern::kMaxRanks, "mx_fold: 1..8 sources");
+  TORCH_CHECK_VALUE(op == "sum" || op == "avg", "mx_fold: op must be 'sum' or 'avg', got '", op, "'");
+  TORCH_CHECK(out.is_cuda() && out.device() == wire.device(), "mx_fold: out must be on the wire's GPU");
+  const auto d = mx_dtype(out, "mx_fold");
+  TORCH_CHECK_VALUE(out.numel() > 0, "mx_fold: out has no elements");
+  const size_t numel = (size_t)out.numel();
+  const size_t cb = pdcc::kern::mx_shard_blocks(numel);
+  const size_t bytes = pdcc::kern::mx_wire_bytes(cb, (size_t)nsrc);
+  TORCH_CHECK((size_t)wire.numel() == bytes, "mx_fold: ", nsrc, " chunk wires of ", numel, " elements have ", bytes,
+              " bytes, got ", wire.numel());
+  c10::hip::HIPGuardMasqueradingAsCUDA g(wire.device());
+  at::Tensor w = mx_in(wire), o = mx_out(out);
+  hipStream_t s = c10::hip::getCurrentHIPStreamMasqueradingAsCUDA(wire.device().index()).stream();
+  hipError_t e = pdcc::kern::mx_fold(w.data_ptr(), nsrc, cb, kop(op), nsrc, o.data_ptr(), numel, d, s);
+  TORCH_CHECK(e == hipSuccess, "mx_fold launch failed: ", hipGetErrorString(e));
+  if (!o.is_same(out)) out.copy_(o);
+}
+
 // Peer links between every pair of visible GPUs, as the runtime reports them: HSA link
 // type (xGMI on an MI355X node, PCIe otherwise), hop count, P2P access / atomics and
 // the runtime's relative performance rank. Local queries only (no collective).
@@ -330,6 +393,13 @@ PYBIND11_MODULE(_C, m) {
         "nsrc chunk wires back to back -> one chunk wire (dequantize, fold in f32 in source order, requantize)");
   m.def("mx_dequantize", &mx_dequantize, py::arg("wire"), py::arg("world"), py::arg("out"),
         "mxfp8_e4m3 wire of `world` chunks -> out (f32 / bf16 / f16), exactly out.numel() elements");
+  m.def("mx_quantize_shards", &mx_quantize_shards, py::arg("x"), py::arg("world"), py::arg("out") = py::none(),
+        "tensor of `world` shards -> shard wire: chunk r is the mxfp8_e4m3 wire of shard r alone");
+  m.def("mx_dequantize_shards", &mx_dequantize_shards, py::arg("wire"), py::arg("world"), py::arg("out"),
+        "shard wire of `world` chunks -> out: chunk r fills out[r m, (r + 1) m), m = out.numel() / world");
+  m.def("mx_fold", &mx_fold, py::arg("wire"), py::arg("nsrc"), py::arg("op"), py::arg("out"),
+        "nsrc chunk wires of out.numel() elements -> out (dequantize, fold in f32 in source order, round once)");
+  m.def("mx_shard_blocks", [](int64_t m) { return (int64_t)pdcc::kern::mx_shard_blocks((size_t)m); });
   m.def("mx_chunk_blocks", [](int64_t numel, int world) { return (int64_t)pdcc::kern::mx_chunk_blocks((size_t)numel, world); });
   m.def("ipc_signal_bytes", &pdcc::kern::ipc_signal_bytes);
   m.def("device_links", &device_links,

@@ -337,6 +337,19 @@ hipError_t mx_reduce(const void* wire_in, int nsrc, size_t cb, RedOp op, int avg
 // nchunks chunk wires -> exactly `numel` elements of `dst`, rounded once to `t`.
 hipError_t mx_dequantize(const void* wire, size_t cb, size_t nchunks, void* dst, size_t numel, DType t,
                          hipStream_t stream);
+// The shard layout (mx_layout.h): chunk r is shard r, the `m` elements from r * m on, cb >=
+// mx_blocks(m). Quantize reads nchunks * m elements and writes every block of every chunk; dequantize
+// writes exactly dst[0, nchunks * m). 16-byte vectors when m * element size is a multiple of 16 (every
+// shard then starts aligned), single elements otherwise.
+hipError_t mx_quantize_shards(const void* src, size_t m, DType t, void* wire, size_t cb, size_t nchunks,
+                              hipStream_t stream);
+hipError_t mx_dequantize_shards(const void* wire, size_t cb, size_t nchunks, void* dst, size_t m, DType t,
+                                hipStream_t stream);
+// `nsrc` (1..kMaxRanks) chunk wires back to back -> exactly `numel` (1..32 cb) elements of `dst`:
+// dequantize, fold in f32 in source order (AVG divides by avg_div), round once to `t`. What mx_reduce
+// then mx_dequantize compute, without the requantization in between.
+hipError_t mx_fold(const void* wire_in, int nsrc, size_t cb, RedOp op, int avg_div, void* dst, size_t numel, DType t,
+                   hipStream_t stream);
 
 }  // namespace kern
 }  // namespace pdcc

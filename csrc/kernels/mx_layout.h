@@ -8,6 +8,14 @@
 //     [32 * cb payload bytes][cb scale bytes]
 // and a wire tensor is `nchunks` such chunks back to back. Block g of the tensor (elements
 // 32 g .. 32 g + 31) is block g % cb of chunk g / cb.
+//
+// The shard layout ("Compressed reduce-scatter and all-gather") is the same chunks cut at shard
+// boundaries: a shard wire of `world` shards of `m` elements is `world` chunks of
+// cb = mx_shard_blocks(m) blocks, and block b of chunk r holds elements r m + 32 b .. r m + 32 b + 31
+// of the tensor, clipped at (r + 1) m -- positions past the shard's end count as +0 and are never
+// read from the next shard. Blocks are aligned to the start of each shard, not of the tensor, so for
+// m % 32 != 0 the bytes differ from the dealt layout; when 32 * mx_chunk_blocks(world m, world) == m
+// the two layouts are the same bytes.
 #pragma once
 #include <stddef.h>
 #include <stdint.h>
@@ -46,6 +54,22 @@ PDCC_MX_HD inline size_t mx_wire_bytes(size_t cb, size_t nchunks) { return mx_ch
 // byte offsets inside one chunk
 PDCC_MX_HD inline size_t mx_payload_off(size_t block) { return (size_t)kMxBlock * block; }
 PDCC_MX_HD inline size_t mx_scale_off(size_t cb, size_t block) { return (size_t)kMxBlock * cb + block; }
+
+
+// ---- shard layout: chunk r is shard r (elements r m .. (r + 1) m - 1), blocks counted from r m
+PDCC_MX_HD inline size_t mx_shard_blocks(size_t m) { return mx_chunk_blocks(m, 1); }
+PDCC_MX_HD inline size_t mx_shard_wire_bytes(size_t m, size_t world) {
+  return mx_wire_bytes(mx_shard_blocks(m), world > 0 ? world : 1);
+}
+// wire byte of the payload of element i (of world * m) and of the scale of its block
+PDCC_MX_HD inline size_t mx_shard_payload_byte(size_t m, size_t i) {
+  const size_t r = i / m;
+  return r * mx_chunk_bytes(mx_shard_blocks(m)) + (i - r * m);
+}
+PDCC_MX_HD inline size_t mx_shard_scale_byte(size_t m, size_t i) {
+  const size_t r = i / m, cb = mx_shard_blocks(m);
+  return r * mx_chunk_bytes(cb) + mx_scale_off(cb, (i - r * m) / kMxBlock);
+}
 
 }  // namespace kern
 }  // namespace pdcc

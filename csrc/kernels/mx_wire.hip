@@ -1,12 +1,16 @@
-// The three local kernels of the block-scaled FP8 wire format `mxfp8_e4m3` (layout: mx_layout.h,
-// contract: docs/collectives.md "Compressed all-reduce"):
+// The local kernels of the block-scaled FP8 wire format `mxfp8_e4m3` (layout: mx_layout.h,
+// contract: docs/collectives.md "Compressed all-reduce" and "Compressed reduce-scatter and
+// all-gather"):
 //
 //   mx_quantize    f32 / bf16 / f16 tensor -> wire           (reads 4n or 2n, writes 33n/32)
 //   mx_reduce      nsrc chunk wires -> one chunk wire         (dequantize, fold in f32, requantize)
 //   mx_dequantize  wire -> f32 / bf16 / f16 tensor
+//   mx_fold        nsrc chunk wires -> f32 / bf16 / f16 tensor (dequantize, fold in f32, round once)
+//   mx_quantize_shards / mx_dequantize_shards: quantize / dequantize with one chunk per shard of m
+//                  elements (the SHARD instantiations of the same two kernels)
 //
-// All three are streaming kernels: a lane moves 16 B on the wide side of its conversion (the tensor
-// for quantize / dequantize, the payload for reduce), the lanes of a block sit next to each other
+// All of them are streaming kernels: a lane moves 16 B on the wide side of its conversion (the tensor
+// for quantize / dequantize / fold, the payload for reduce), the lanes of a block sit next to each other
 // in a wave64, and a block's amax is a butterfly over those lanes with DPP moves -- no LDS, no
 // atomics, no cross-workgroup traffic. A chunk is one grid row (blockIdx.y), so no lane divides by
 // the chunk size.
@@ -84,16 +88,20 @@ __device__ __forceinline__ void widen4(uint32_t w, float scale, float* f) {
 // ---------------------------------------------------------------------------- quantize
 // Lane layout of one chunk (grid row): vector v of the chunk is 16 B of the tensor = EPL elements,
 // LPB = 32 / EPL consecutive lanes make a block. The chunk has cb * LPB vectors, a multiple of 64.
-template <DType DT>
+// SHARD: chunk r is the `m` elements from r * m on (numel = nchunks * m) instead of the 32 cb from
+// r * 32 cb on, and nothing at or past (r + 1) * m enters it. VEC = false (shards that do not start
+// 16-byte aligned) reads every element on its own.
+template <DType DT, bool SHARD, bool VEC>
 __global__ __launch_bounds__(256) void k_mx_quantize(const char* __restrict__ src, size_t numel,
-                                                     char* __restrict__ wire, uint32_t cb) {
+                                                     char* __restrict__ wire, uint32_t cb, size_t m) {
   using T = Tr<DT>;
   using S = typename T::S;
   constexpr int EPL = 16 / (int)sizeof(S);
   constexpr int LPB = kern::kMxBlock / EPL;
   const size_t chunk = blockIdx.y;
   char* __restrict__ w = wire + chunk * kern::mx_chunk_bytes(cb);
-  const size_t el0 = chunk * cb * (size_t)kern::kMxBlock;  // first element of the chunk
+  const size_t el0 = SHARD ? chunk * m : chunk * cb * (size_t)kern::kMxBlock;  // first element of the chunk
+  const size_t end = SHARD ? el0 + m : numel;                                  // one past its last
   const uint32_t nvec = cb * LPB;
   // a workgroup takes one contiguous span of kMxUnroll * 256 vectors per pass (16 KiB of the tensor)
   constexpr uint32_t stride = 256u;
@@ -104,16 +112,16 @@ __global__ __launch_bounds__(256) void k_mx_quantize(const char* __restrict__ sr
     for (int u = 0; u < kMxUnroll; ++u) {
       const uint32_t v = v0 + u * stride;
       const size_t el = el0 + (size_t)v * EPL;
-      if (v < nvec && el + EPL <= numel) {
+      if (VEC && v < nvec && el + EPL <= end) {
         const uint4 x = *reinterpret_cast<const uint4*>(src + el * sizeof(S));
         __builtin_memcpy(s[u], &x, 16);
       } else {
-        // the tensor's last vector, or padding: elements past numel count as +0 and are never read
+        // the last vector, or padding: elements past the end count as +0 and are never read
 #pragma unroll
         for (int i = 0; i < EPL; ++i) {
           S z;
           __builtin_memset(&z, 0, sizeof(S));
-          if (v < nvec && el + i < numel) z = reinterpret_cast<const S*>(src)[el + i];
+          if (v < nvec && el + i < end) z = reinterpret_cast<const S*>(src)[el + i];
           s[u][i] = z;
         }
       }
@@ -147,19 +155,20 @@ __global__ __launch_bounds__(256) void k_mx_quantize(const char* __restrict__ sr
 
 // ---------------------------------------------------------------------------- dequantize
 // The same lane layout as quantize: a lane reads EPL payload bytes and its block's scale byte and
-// stores 16 B of the tensor; nothing at or past `numel` is written.
-template <DType DT>
+// stores 16 B of the tensor; nothing at or past `numel` is written. SHARD / VEC as in quantize:
+// chunk r fills exactly dst[r m, (r + 1) m).
+template <DType DT, bool SHARD, bool VEC>
 __global__ __launch_bounds__(256) void k_mx_dequantize(const char* __restrict__ wire, uint32_t cb,
-                                                       char* __restrict__ dst, size_t numel) {
+                                                       char* __restrict__ dst, size_t numel, size_t m) {
   using T = Tr<DT>;
   using S = typename T::S;
   constexpr int EPL = 16 / (int)sizeof(S);
   constexpr int LPB = kern::kMxBlock / EPL;
   const size_t chunk = blockIdx.y;
   const char* __restrict__ w = wire + chunk * kern::mx_chunk_bytes(cb);
-  const size_t el0 = chunk * cb * (size_t)kern::kMxBlock;
+  const size_t el0 = SHARD ? chunk * m : chunk * cb * (size_t)kern::kMxBlock;
   if (el0 >= numel) return;  // a padding chunk
-  const size_t left = numel - el0;
+  const size_t left = SHARD ? m : numel - el0;
   // vectors of this chunk that hold at least one element of the tensor
   const uint32_t nvec = (uint32_t)(left >= (size_t)cb * kern::kMxBlock ? (size_t)cb * LPB : (left + EPL - 1) / EPL);
   constexpr uint32_t stride = 256u;  // (contiguous spans per workgroup, as in quantize)
@@ -198,7 +207,7 @@ __global__ __launch_bounds__(256) void k_mx_dequantize(const char* __restrict__ 
       for (int i = 0; i < EPL; ++i) s[i] = T::out(f[i]);
       const size_t el = (size_t)v * EPL;  // within the chunk
       S* o = reinterpret_cast<S*>(dst) + el0 + el;
-      if (el + EPL <= left) {
+      if (VEC && el + EPL <= left) {
         uint4 x;
         __builtin_memcpy(&x, s, 16);
         *reinterpret_cast<uint4*>(o) = x;
@@ -262,6 +271,87 @@ __global__ __launch_bounds__(256) void k_mx_reduce(const char* __restrict__ in, 
   }
 }
 
+// ---------------------------------------------------------------------------- fold
+// nsrc chunk wires -> a tensor: what mx_reduce then mx_dequantize would give without the wire in
+// between (and without its requantization). The lane layout is dequantize's: the wide side is the
+// output, 16 B = EPL elements per lane, so a lane reads EPL payload bytes and its block's scale byte
+// of every source and a wave's store is contiguous. All NSRC * U loads are issued before the first
+// convert; U keeps about eight of them in flight per lane whatever NSRC is.
+template <int NSRC>
+constexpr int kMxFoldUnroll = NSRC <= 2 ? 4 : (NSRC <= 4 ? 2 : 1);
+
+template <DType DT, int NSRC, bool AVG>
+__global__ __launch_bounds__(256) void k_mx_fold(const char* __restrict__ in, uint32_t cb, int avg_div,
+                                                 char* __restrict__ dst, size_t numel) {
+  using T = Tr<DT>;
+  using S = typename T::S;
+  constexpr int EPL = 16 / (int)sizeof(S);
+  constexpr int LPB = kern::kMxBlock / EPL;
+  constexpr int U = kMxFoldUnroll<NSRC>;
+  const size_t cbytes = kern::mx_chunk_bytes(cb);
+  const uint32_t nvec = (uint32_t)((numel + EPL - 1) / EPL);  // <= cb * LPB: numel <= 32 cb
+  const uint32_t pass = gridDim.x * 256u * U;
+  for (uint32_t v0 = blockIdx.x * 256u * U + threadIdx.x; v0 < nvec; v0 += pass) {
+    uint32_t q[U][NSRC][EPL / 4];
+    uint32_t sb[U][NSRC];
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      const uint32_t v = v0 + u * 256u;
+#pragma unroll
+      for (int r = 0; r < NSRC; ++r) {
+        sb[u][r] = 127u;
+#pragma unroll
+        for (int d = 0; d < EPL / 4; ++d) q[u][r][d] = 0u;
+        if (v < nvec) {
+          const char* c = in + (size_t)r * cbytes;
+          const char* p = c + (size_t)v * EPL;
+          if constexpr (EPL == 4) {
+            q[u][r][0] = *reinterpret_cast<const uint32_t*>(p);
+          } else {
+            const uint2 x = *reinterpret_cast<const uint2*>(p);
+            q[u][r][0] = x.x;
+            q[u][r][1] = x.y;
+          }
+          sb[u][r] = (uint8_t)c[kern::mx_scale_off(cb, v / LPB)];
+        }
+      }
+    }
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      const uint32_t v = v0 + u * 256u;
+      if (v >= nvec) break;
+      float acc[EPL];
+#pragma unroll
+      for (int r = 0; r < NSRC; ++r) {
+        const float scale = mx_scale_value(sb[u][r]);
+        float f[EPL];
+#pragma unroll
+        for (int d = 0; d < EPL / 4; ++d) widen4(q[u][r][d], scale, f + 4 * d);
+#pragma unroll
+        for (int i = 0; i < EPL; ++i) acc[i] = r == 0 ? f[i] : acc[i] + f[i];  // source order
+      }
+      if constexpr (AVG) {
+#pragma unroll
+        for (int i = 0; i < EPL; ++i) acc[i] = acc[i] / (float)avg_div;
+      }
+      S s[EPL];
+#pragma unroll
+      for (int i = 0; i < EPL; ++i) s[i] = T::out(acc[i]);
+      const size_t el = (size_t)v * EPL;
+      S* o = reinterpret_cast<S*>(dst) + el;
+      if (el + EPL <= numel) {
+        uint4 x;
+        __builtin_memcpy(&x, s, 16);
+        *reinterpret_cast<uint4*>(o) = x;
+      } else {
+#pragma unroll
+        for (int i = 0; i < EPL; ++i)
+          if (el + i < numel) o[i] = s[i];
+      }
+    }
+  }
+}
+
 // grid row of `nvec` vectors with `per` of them per lane and pass, at most `most` workgroups in all
 // rows (the kernels loop past that). Quantize / dequantize: one pass per workgroup up to 2^20 of them;
 // reduce: a grid-stride loop over 8 workgroups per CU.
@@ -293,9 +383,9 @@ hipError_t mx_quantize(const void* src, size_t numel, DType t, void* wire, size_
   const char* s = static_cast<const char*>(src);
   char* w = static_cast<char*>(wire);
   switch (t) {
-    case DType::F32: hipLaunchKernelGGL(dev::k_mx_quantize<DType::F32>, grid, dim3(256), 0, stream, s, numel, w, (uint32_t)cb); break;
-    case DType::BF16: hipLaunchKernelGGL(dev::k_mx_quantize<DType::BF16>, grid, dim3(256), 0, stream, s, numel, w, (uint32_t)cb); break;
-    case DType::F16: hipLaunchKernelGGL(dev::k_mx_quantize<DType::F16>, grid, dim3(256), 0, stream, s, numel, w, (uint32_t)cb); break;
+    case DType::F32: hipLaunchKernelGGL((dev::k_mx_quantize<DType::F32, false, true>), grid, dim3(256), 0, stream, s, numel, w, (uint32_t)cb, size_t(0)); break;
+    case DType::BF16: hipLaunchKernelGGL((dev::k_mx_quantize<DType::BF16, false, true>), grid, dim3(256), 0, stream, s, numel, w, (uint32_t)cb, size_t(0)); break;
+    case DType::F16: hipLaunchKernelGGL((dev::k_mx_quantize<DType::F16, false, true>), grid, dim3(256), 0, stream, s, numel, w, (uint32_t)cb, size_t(0)); break;
     default: return hipErrorInvalidValue;
   }
   return hipGetLastError();
@@ -312,10 +402,67 @@ hipError_t mx_dequantize(const void* wire, size_t cb, size_t nchunks, void* dst,
   const char* w = static_cast<const char*>(wire);
   char* d = static_cast<char*>(dst);
   switch (t) {
-    case DType::F32: hipLaunchKernelGGL(dev::k_mx_dequantize<DType::F32>, grid, dim3(256), 0, stream, w, (uint32_t)cb, d, numel); break;
-    case DType::BF16: hipLaunchKernelGGL(dev::k_mx_dequantize<DType::BF16>, grid, dim3(256), 0, stream, w, (uint32_t)cb, d, numel); break;
-    case DType::F16: hipLaunchKernelGGL(dev::k_mx_dequantize<DType::F16>, grid, dim3(256), 0, stream, w, (uint32_t)cb, d, numel); break;
+    case DType::F32: hipLaunchKernelGGL((dev::k_mx_dequantize<DType::F32, false, true>), grid, dim3(256), 0, stream, w, (uint32_t)cb, d, numel, size_t(0)); break;
+    case DType::BF16: hipLaunchKernelGGL((dev::k_mx_dequantize<DType::BF16, false, true>), grid, dim3(256), 0, stream, w, (uint32_t)cb, d, numel, size_t(0)); break;
+    case DType::F16: hipLaunchKernelGGL((dev::k_mx_dequantize<DType::F16, false, true>), grid, dim3(256), 0, stream, w, (uint32_t)cb, d, numel, size_t(0)); break;
     default: return hipErrorInvalidValue;
+  }
+  return hipGetLastError();
+}
+
+namespace {
+size_t mx_esize(DType t) { return t == DType::F32 ? 4 : 2; }
+// the shard arguments: m elements per shard fit the chunk, and the whole tensor's size is a size_t
+bool mx_shards_ok(size_t m, size_t cb, size_t nchunks) {
+  return mx_cb_ok(cb) && m > 0 && m <= cb * kMxBlock && nchunks > 0 && nchunks <= 65535;
+}
+
+template <DType DT>
+void mx_quantize_shards_go(const dim3& grid, bool vec, const char* s, size_t numel, char* w, uint32_t cb, size_t m,
+                           hipStream_t stream) {
+  if (vec) hipLaunchKernelGGL((dev::k_mx_quantize<DT, true, true>), grid, dim3(256), 0, stream, s, numel, w, cb, m);
+  else hipLaunchKernelGGL((dev::k_mx_quantize<DT, true, false>), grid, dim3(256), 0, stream, s, numel, w, cb, m);
+}
+template <DType DT>
+void mx_dequantize_shards_go(const dim3& grid, bool vec, const char* w, uint32_t cb, char* d, size_t numel, size_t m,
+                             hipStream_t stream) {
+  if (vec) hipLaunchKernelGGL((dev::k_mx_dequantize<DT, true, true>), grid, dim3(256), 0, stream, w, cb, d, numel, m);
+  else hipLaunchKernelGGL((dev::k_mx_dequantize<DT, true, false>), grid, dim3(256), 0, stream, w, cb, d, numel, m);
+}
+}  // namespace
+
+hipError_t mx_quantize_shards(const void* src, size_t m, DType t, void* wire, size_t cb, size_t nchunks,
+                              hipStream_t stream) {
+  if (!mx_shards_ok(m, cb, nchunks) || !mx_al16(wire) || !mx_al16(src)) return hipErrorInvalidValue;
+  if (t != DType::F32 && t != DType::BF16 && t != DType::F16) return hipErrorInvalidValue;
+  const int lpb = t == DType::F32 ? 8 : 4;
+  const bool vec = m * mx_esize(t) % 16 == 0;  // every shard starts 16-byte aligned
+  const dim3 grid(dev::mx_grid_x((uint64_t)cb * lpb, dev::kMxUnroll, nchunks, dev::kMxGridStream), (uint32_t)nchunks);
+  const char* s = static_cast<const char*>(src);
+  char* w = static_cast<char*>(wire);
+  const size_t numel = m * nchunks;
+  switch (t) {
+    case DType::F32: mx_quantize_shards_go<DType::F32>(grid, vec, s, numel, w, (uint32_t)cb, m, stream); break;
+    case DType::BF16: mx_quantize_shards_go<DType::BF16>(grid, vec, s, numel, w, (uint32_t)cb, m, stream); break;
+    default: mx_quantize_shards_go<DType::F16>(grid, vec, s, numel, w, (uint32_t)cb, m, stream); break;
+  }
+  return hipGetLastError();
+}
+
+hipError_t mx_dequantize_shards(const void* wire, size_t cb, size_t nchunks, void* dst, size_t m, DType t,
+                                hipStream_t stream) {
+  if (!mx_shards_ok(m, cb, nchunks) || !mx_al16(wire) || !mx_al16(dst)) return hipErrorInvalidValue;
+  if (t != DType::F32 && t != DType::BF16 && t != DType::F16) return hipErrorInvalidValue;
+  const int lpb = t == DType::F32 ? 8 : 4;
+  const bool vec = m * mx_esize(t) % 16 == 0;
+  const dim3 grid(dev::mx_grid_x((uint64_t)cb * lpb, dev::kMxUnroll, nchunks, dev::kMxGridStream), (uint32_t)nchunks);
+  const char* w = static_cast<const char*>(wire);
+  char* d = static_cast<char*>(dst);
+  const size_t numel = m * nchunks;
+  switch (t) {
+    case DType::F32: mx_dequantize_shards_go<DType::F32>(grid, vec, w, (uint32_t)cb, d, numel, m, stream); break;
+    case DType::BF16: mx_dequantize_shards_go<DType::BF16>(grid, vec, w, (uint32_t)cb, d, numel, m, stream); break;
+    default: mx_dequantize_shards_go<DType::F16>(grid, vec, w, (uint32_t)cb, d, numel, m, stream); break;
   }
   return hipGetLastError();
 }
@@ -345,6 +492,50 @@ hipError_t mx_reduce(const void* wire_in, int nsrc, size_t cb, RedOp op, int avg
   char* out = static_cast<char*>(wire_out);
   return op == RedOp::AVG ? mx_reduce_go<true>(in, nsrc, (uint32_t)cb, avg_div, out, stream)
                           : mx_reduce_go<false>(in, nsrc, (uint32_t)cb, avg_div, out, stream);
+}
+
+namespace {
+template <DType DT, bool AVG>
+hipError_t mx_fold_go(const char* in, int nsrc, uint32_t cb, int avg_div, char* dst, size_t numel, hipStream_t stream) {
+  constexpr int epl = 16 / (int)sizeof(typename dev::Tr<DT>::S);
+  const uint64_t nvec = (numel + epl - 1) / epl;
+  const dim3 block(256);
+  switch (nsrc) {
+#define PDCC_MX_N(N)                                                                                        \
+  case N: {                                                                                                 \
+    const dim3 grid(dev::mx_grid_x(nvec, dev::kMxFoldUnroll<N>, 1, dev::kMxGridReduce));                    \
+    hipLaunchKernelGGL((dev::k_mx_fold<DT, N, AVG>), grid, block, 0, stream, in, cb, avg_div, dst, numel); \
+    break;                                                                                                  \
+  }
+    PDCC_MX_N(1) PDCC_MX_N(2) PDCC_MX_N(3) PDCC_MX_N(4) PDCC_MX_N(5) PDCC_MX_N(6) PDCC_MX_N(7) PDCC_MX_N(8)
+#undef PDCC_MX_N
+    default: return hipErrorInvalidValue;
+  }
+  return hipGetLastError();
+}
+template <DType DT>
+hipError_t mx_fold_op(const char* in, int nsrc, uint32_t cb, RedOp op, int avg_div, char* dst, size_t numel,
+                      hipStream_t stream) {
+  return op == RedOp::AVG ? mx_fold_go<DT, true>(in, nsrc, cb, avg_div, dst, numel, stream)
+                          : mx_fold_go<DT, false>(in, nsrc, cb, avg_div, dst, numel, stream);
+}
+}  // namespace
+
+hipError_t mx_fold(const void* wire_in, int nsrc, size_t cb, RedOp op, int avg_div, void* dst, size_t numel, DType t,
+                   hipStream_t stream) {
+  if (!mx_cb_ok(cb) || nsrc < 1 || nsrc > kMaxRanks || !mx_al16(wire_in) || !mx_al16(dst))
+    return hipErrorInvalidValue;
+  if (numel == 0 || numel > cb * kMxBlock) return hipErrorInvalidValue;
+  if (op != RedOp::SUM && op != RedOp::AVG) return hipErrorInvalidValue;
+  if (op == RedOp::AVG && avg_div < 1) return hipErrorInvalidValue;
+  const char* in = static_cast<const char*>(wire_in);
+  char* d = static_cast<char*>(dst);
+  switch (t) {
+    case DType::F32: return mx_fold_op<DType::F32>(in, nsrc, (uint32_t)cb, op, avg_div, d, numel, stream);
+    case DType::BF16: return mx_fold_op<DType::BF16>(in, nsrc, (uint32_t)cb, op, avg_div, d, numel, stream);
+    case DType::F16: return mx_fold_op<DType::F16>(in, nsrc, (uint32_t)cb, op, avg_div, d, numel, stream);
+    default: return hipErrorInvalidValue;
+  }
 }
 
 }  // namespace kern

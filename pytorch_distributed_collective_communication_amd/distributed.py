@@ -14,7 +14,8 @@ import torch.distributed as _td
 from torch.distributed import *  # noqa: F401,F403 - re-export the full front-end
 
 from .parallel.backend import BACKEND_NAME, describe, last_algo, register, stats  # noqa: F401
-from .parallel.compressed import all_reduce_compressed  # noqa: F401
+from .parallel.compressed import (all_gather_compressed, all_reduce_compressed,  # noqa: F401
+                                  reduce_scatter_compressed)
 
 register()
 

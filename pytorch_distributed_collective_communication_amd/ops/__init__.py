@@ -17,6 +17,9 @@
   ``mxfp8_e4m3`` (docs/collectives.md "Compressed all-reduce"): 32-element blocks, one E8M0 scale
   byte and 32 ``float8_e4m3fn`` bytes each. ``parallel/compressed.py`` builds
   ``all_reduce_compressed`` from them.
+* :func:`mx_quantize_shards`, :func:`mx_dequantize_shards`, :func:`mx_fold` -- the same wire with one
+  chunk per shard (docs/collectives.md "Compressed reduce-scatter and all-gather") and the fold of
+  chunk wires straight into a tensor; ``reduce_scatter_compressed`` / ``all_gather_compressed``.
 
 Every function runs on the current HIP stream and raises if the native
 extension is missing (no silent eager fallback). ``*_reference`` functions are
@@ -153,6 +156,17 @@ def mx_wire_bytes(numel: int, world: int = 1) -> int:
     return 33 * mx_chunk_blocks(numel, world) * max(1, int(world))
 
 
+def mx_shard_blocks(m: int) -> int:
+    """Blocks per chunk of a shard wire of ``m``-element shards: ``mx_chunk_blocks(m, 1)``. Chunk ``r`` of
+    such a wire holds shard ``r`` alone, its blocks counted from the shard's first element."""
+    return mx_chunk_blocks(m, 1)
+
+
+def mx_shard_wire_bytes(m: int, world: int = 1) -> int:
+    """Bytes of the shard wire of ``world`` shards of ``m`` elements."""
+    return 33 * mx_shard_blocks(m) * max(1, int(world))
+
+
 def _mx_check_dtype(dt, who):
     if dt not in MX_DTYPES:
         raise TypeError(f"{who}: float32, bfloat16 or float16 tensors only, got {dt}")
@@ -185,6 +199,57 @@ def mx_dequantize(wire: torch.Tensor, numel: int, dtype: torch.dtype = torch.flo
         if out.numel() != int(numel):
             raise ValueError(f"mx_dequantize: out has {out.numel()} elements, numel is {numel}")
     _C().mx_dequantize(wire, int(world), out)
+    return out
+
+
+def _mx_check_shards(numel: int, world: int, who: str) -> int:
+    world = int(world)
+    if world < 1 or numel < 1 or numel % world:
+        raise ValueError(f"{who}: {numel} elements are not {world} shards of one or more elements")
+    return numel // world
+
+
+def mx_quantize_shards(x: torch.Tensor, world: int, out: torch.Tensor | None = None) -> torch.Tensor:
+    """``x`` (GPU; ``world`` shards of ``m`` elements) -> its shard wire: chunk ``r`` is the wire of shard
+    ``r`` alone (``mx_shard_blocks(m)`` blocks; what lies past the shard's end counts as +0)."""
+    _mx_check_dtype(x.dtype, "mx_quantize_shards")
+    _mx_check_shards(x.numel(), world, "mx_quantize_shards")
+    return _C().mx_quantize_shards(x.detach().reshape(-1), int(world), out)
+
+
+def mx_dequantize_shards(wire: torch.Tensor, shard_numel: int, dtype: torch.dtype = torch.float32, world: int = 1,
+                         out: torch.Tensor | None = None) -> torch.Tensor:
+    """A shard wire of ``world`` chunks -> ``world * shard_numel`` elements: chunk ``r`` fills
+    ``out[r * m:(r + 1) * m]``, rounded once to the dtype; nothing outside ``out`` is written."""
+    n = int(shard_numel) * int(world)
+    if out is None:
+        _mx_check_dtype(dtype, "mx_dequantize_shards")
+        out = torch.empty(n, dtype=dtype, device=wire.device)
+    else:
+        _mx_check_dtype(out.dtype, "mx_dequantize_shards")
+        if out.numel() != n:
+            raise ValueError(f"mx_dequantize_shards: out has {out.numel()} elements, {world} shards of "
+                             f"{shard_numel} are {n}")
+    _mx_check_shards(n, world, "mx_dequantize_shards")
+    _C().mx_dequantize_shards(wire, int(world), out)
+    return out
+
+
+def mx_fold(wire: torch.Tensor, nsrc: int, numel: int, dtype: torch.dtype = torch.float32, op: str = "sum",
+            out: torch.Tensor | None = None) -> torch.Tensor:
+    """``nsrc`` (1..8) chunk wires of ``mx_shard_blocks(numel)`` blocks back to back -> ``numel`` elements:
+    every source dequantized, folded in f32 in source order (``avg``: then divided by ``nsrc``) and rounded
+    once to the dtype -- :func:`mx_reduce` then :func:`mx_dequantize` without the requantization between."""
+    if op not in ("sum", "avg"):
+        raise ValueError(f"mx_fold: op must be 'sum' or 'avg', got {op!r}")
+    if out is None:
+        _mx_check_dtype(dtype, "mx_fold")
+        out = torch.empty(int(numel), dtype=dtype, device=wire.device)
+    else:
+        _mx_check_dtype(out.dtype, "mx_fold")
+        if out.numel() != int(numel):
+            raise ValueError(f"mx_fold: out has {out.numel()} elements, numel is {numel}")
+    _C().mx_fold(wire, int(nsrc), op, out)
     return out
 
 
@@ -272,6 +337,49 @@ def mx_dequantize_reference(wire: torch.Tensor, numel: int, dtype: torch.dtype =
     return _mx_dequantize_blocks(q, s).reshape(-1)[:int(numel)].to(dtype)
 
 
+def mx_quantize_shards_reference(x: torch.Tensor, world: int) -> torch.Tensor:
+    """Plain-PyTorch :func:`mx_quantize_shards` on a CPU tensor."""
+    _mx_check_dtype(x.dtype, "mx_quantize_shards_reference")
+    m = _mx_check_shards(x.numel(), world, "mx_quantize_shards_reference")
+    flat = x.detach().reshape(-1)
+    return torch.cat([mx_quantize_reference(flat[r * m:(r + 1) * m], 1) for r in range(int(world))])
+
+
+def mx_dequantize_shards_reference(wire: torch.Tensor, shard_numel: int, dtype: torch.dtype = torch.float32,
+                                   world: int = 1) -> torch.Tensor:
+    """Plain-PyTorch :func:`mx_dequantize_shards` on a CPU wire."""
+    _mx_check_dtype(dtype, "mx_dequantize_shards_reference")
+    m, world = int(shard_numel), int(world)
+    _mx_check_shards(m * world, world, "mx_dequantize_shards_reference")
+    if wire.numel() != mx_shard_wire_bytes(m, world):
+        raise ValueError(f"the wire of {world} shards of {m} elements has {mx_shard_wire_bytes(m, world)} bytes, "
+                         f"got {wire.numel()}")
+    q, s = _mx_split(wire, world)
+    return _mx_dequantize_blocks(q, s).view(world, -1)[:, :m].reshape(-1).to(dtype)
+
+
+def mx_fold_reference(wire: torch.Tensor, nsrc: int, numel: int, dtype: torch.dtype = torch.float32,
+                      op: str = "sum") -> torch.Tensor:
+    """Plain-PyTorch :func:`mx_fold` on a CPU wire."""
+    if op not in ("sum", "avg"):
+        raise ValueError(f"mx_fold_reference: op must be 'sum' or 'avg', got {op!r}")
+    _mx_check_dtype(dtype, "mx_fold_reference")
+    nsrc, numel = int(nsrc), int(numel)
+    if numel < 1 or wire.numel() != mx_shard_wire_bytes(numel, nsrc):
+        raise ValueError(f"{nsrc} chunk wires of {numel} elements have {mx_shard_wire_bytes(numel, nsrc)} bytes, "
+                         f"got {wire.numel()}")
+    q, s = _mx_split(wire, nsrc)
+    d = _mx_dequantize_blocks(q, s).view(nsrc, -1)
+    acc = d[0].clone()
+    for r in range(1, nsrc):
+        acc = acc + d[r]
+    if op == "avg":
+        acc = acc / torch.tensor(float(nsrc), dtype=torch.float32)
+    return acc[:numel].to(dtype)
+
+
 __all__ = ["reduce_nway", "reduce_nway_reference", "multi_copy", "pack", "unpack",
            "mx_quantize", "mx_reduce", "mx_dequantize", "mx_chunk_blocks", "mx_wire_bytes",
-           "mx_quantize_reference", "mx_reduce_reference", "mx_dequantize_reference"]
+           "mx_quantize_reference", "mx_reduce_reference", "mx_dequantize_reference",
+           "mx_shard_blocks", "mx_shard_wire_bytes", "mx_quantize_shards", "mx_dequantize_shards", "mx_fold",
+           "mx_quantize_shards_reference", "mx_dequantize_shards_reference", "mx_fold_reference"]

@@ -32,6 +32,15 @@ Gradient accumulation: backward passes inside ``with opt.no_sync():`` only
 accumulate; a second backward outside it before :meth:`step` raises instead of
 double-reducing a bucket.
 
+Compressed links: ``grad_wire="mxfp8_e4m3"`` sends every gradient bucket through
+``reduce_scatter_compressed`` (AVG, divided inside the fold) and
+``param_wire="mxfp8_e4m3"`` every parameter bucket through
+``all_gather_compressed`` (parallel/compressed.py; 3.9x / 1.94x fewer bytes on
+the links for f32 / bf16). Master weights and optimizer state stay exact f32:
+only the replicated copy used for forward and backward is the dequantized
+wire, the same bits on every rank. Spaces of other dtypes keep the uncompressed
+calls; the defaults (``None``) are the uncompressed path, call for call.
+
 ``state_dict()`` / ``load_state_dict()`` save and restore this rank's shard
 (sharded checkpoint: every rank writes its own file) and re-gather the
 parameters on load.
@@ -150,13 +159,22 @@ class ShardedOptimizer:
     master weights and optimizer state for floating-point parameters -- with
     bf16 parameters the optimizer math runs in fp32 and only the gathered
     parameters are bf16. ``overlap=False`` defers every reduce-scatter to
-    :meth:`step`. One parameter group: the inner optimizer's hyper-parameters
+    :meth:`step`. ``grad_wire`` / ``param_wire`` (default ``None``: uncompressed;
+    ``"mxfp8_e4m3"``) pick the wire of the reduce-scatters / the all-gathers of
+    float32, bfloat16 and float16 parameters. One parameter group: the inner optimizer's hyper-parameters
     come from ``**opt_kwargs``.
     """
 
     def __init__(self, params: Iterable[torch.nn.Parameter], optimizer_cls=torch.optim.SGD, group=None,
                  master_dtype: torch.dtype = torch.float32, broadcast_from: int | None = 0,
-                 bucket_bytes: int = 256 << 20, overlap: bool = True, **opt_kwargs):
+                 bucket_bytes: int = 256 << 20, overlap: bool = True, grad_wire: str | None = None,
+                 param_wire: str | None = None, **opt_kwargs):
+        from .compressed import WIRES
+
+        for name, w in (("grad_wire", grad_wire), ("param_wire", param_wire)):
+            if w is not None and w not in WIRES:
+                raise ValueError(f"ShardedOptimizer: unknown {name} {w!r} (supported: {', '.join(WIRES)})")
+        self.grad_wire, self.param_wire = grad_wire, param_wire
         self.group = group
         self.world = dist.get_world_size(group)
         self.rank = dist.get_rank(group)
@@ -204,8 +222,31 @@ class ShardedOptimizer:
         finally:
             self._sync = prev
 
+    @staticmethod
+    def _on_wire(s: _FlatSpace, wire) -> bool:
+        from .. import ops
+
+        return wire is not None and s.dtype in ops.MX_DTYPES
+
+    def _fence(self, s: _FlatSpace) -> None:
+        """An uncompressed call next to compressed ones (a space of another dtype): the compressed calls
+        run on a side stream the backend does not order its own streams against, and two collectives of
+        one group must not overlap -- the current stream, which the backend does wait for, waits for it."""
+        if s.device.type == "cuda" and (self.grad_wire is not None or self.param_wire is not None):
+            from .compressed import order_after_compressed
+
+            order_after_compressed(s.device)
+
     def _launch(self, s: _FlatSpace, b: _Bucket) -> None:
         s.sync_grads_in(b)
+        if self._on_wire(s, self.grad_wire):
+            from .compressed import reduce_scatter_compressed
+
+            b.work = reduce_scatter_compressed(s.grad_shard[b.soff:b.soff + b.shard], s.grad[b.off:b.off + b.padded],
+                                               op=dist.ReduceOp.AVG, group=self.group, wire=self.grad_wire,
+                                               async_op=True)
+            return
+        self._fence(s)
         b.work = dist.reduce_scatter_tensor(s.grad_shard[b.soff:b.soff + b.shard], s.grad[b.off:b.off + b.padded],
                                             op=self._op, group=self.group, async_op=True)
 
@@ -241,7 +282,7 @@ class ShardedOptimizer:
                 b.work = None
                 b.pending = len(b.idx)
             g = s.grad_shard if s.master.dtype == s.dtype else s.grad_shard.to(s.master.dtype)
-            if not self._avg and self.world > 1:
+            if not self._avg and self.world > 1 and not self._on_wire(s, self.grad_wire):  # (a wire divides inside)
                 g = g / self.world
             s.master.grad = g
         self.inner.step()
@@ -253,6 +294,14 @@ class ShardedOptimizer:
         for s in self.spaces:
             s.param_shard.copy_(s.master)
             for b in s.buckets:
+                if self._on_wire(s, self.param_wire):
+                    from .compressed import all_gather_compressed
+
+                    works.append(all_gather_compressed(s.flat[b.off:b.off + b.padded],
+                                                       s.param_shard[b.soff:b.soff + b.shard], group=self.group,
+                                                       wire=self.param_wire, async_op=True))
+                    continue
+                self._fence(s)
                 works.append(dist.all_gather_into_tensor(s.flat[b.off:b.off + b.padded],
                                                          s.param_shard[b.soff:b.soff + b.shard],
                                                          group=self.group, async_op=True))
