@@ -91,7 +91,7 @@ void multi_copy(const std::vector<at::Tensor>& srcs, const std::vector<at::Tenso
   TORCH_CHECK(e == hipSuccess, "multi_copy launch failed: ", hipGetErrorString(e));
 }
 
-// ---- block-scaled FP8 wire (kernels/mx_wire.hip). The kernels want contiguous, 16-byte aligned
+// ---- block-scaled wires, mxfp8_e4m3 and mxfp4_e2m1 (kernels/mx_wire.hip). The kernels want contiguous, 16-byte aligned
 // buffers: any other tensor goes through a contiguous copy (inputs) or is filled from one (outputs).
 at::Tensor mx_in(const at::Tensor& t) {
   if (t.is_contiguous() && al16(t.data_ptr())) return t;
@@ -111,14 +111,22 @@ pdcc::kern::DType mx_dtype(const at::Tensor& t, const char* who) {
 void mx_check_wire(const at::Tensor& w, const char* who) {
   TORCH_CHECK(w.is_cuda() && w.scalar_type() == at::kByte && w.dim() == 1, who, ": the wire is a 1-d uint8 GPU tensor");
 }
+using pdcc::kern::MxFormat;
+MxFormat mx_format(const std::string& wire, const char* who) {
+  if (wire == "mxfp8_e4m3") return MxFormat::FP8_E4M3;
+  if (wire == "mxfp4_e2m1") return MxFormat::FP4_E2M1;
+  TORCH_CHECK_VALUE(false, who, ": unknown wire format '", wire, "' (supported: mxfp8_e4m3, mxfp4_e2m1)");
+  return MxFormat::FP8_E4M3;
+}
 
-at::Tensor mx_quantize(const at::Tensor& x, int world, const c10::optional<at::Tensor>& out) {
+at::Tensor mx_quantize(const at::Tensor& x, int world, const c10::optional<at::Tensor>& out, const std::string& fmt) {
+  const MxFormat f = mx_format(fmt, "mx_quantize");
   TORCH_CHECK(x.is_cuda(), "mx_quantize: GPU tensors only");
   TORCH_CHECK(world >= 1, "mx_quantize: world must be >= 1");
   const auto d = mx_dtype(x, "mx_quantize");
   const size_t numel = (size_t)x.numel();
-  const size_t cb = pdcc::kern::mx_chunk_blocks(numel, world);
-  const int64_t bytes = (int64_t)pdcc::kern::mx_wire_bytes(cb, (size_t)world);
+  const size_t cb = pdcc::kern::mx_chunk_blocks(f, numel, world);
+  const int64_t bytes = (int64_t)pdcc::kern::mx_wire_bytes(f, cb, (size_t)world);
   c10::hip::HIPGuardMasqueradingAsCUDA g(x.device());
   at::Tensor wire = out ? *out : at::empty({bytes}, x.options().dtype(at::kByte));
   mx_check_wire(wire, "mx_quantize");
@@ -126,60 +134,66 @@ at::Tensor mx_quantize(const at::Tensor& x, int world, const c10::optional<at::T
               x.device());
   at::Tensor src = mx_in(x), w = mx_out(wire);
   hipStream_t s = c10::hip::getCurrentHIPStreamMasqueradingAsCUDA(x.device().index()).stream();
-  hipError_t e = pdcc::kern::mx_quantize(src.data_ptr(), numel, d, w.data_ptr(), cb, (size_t)world, s);
+  hipError_t e = pdcc::kern::mx_quantize(src.data_ptr(), numel, d, w.data_ptr(), cb, (size_t)world, s, f);
   TORCH_CHECK(e == hipSuccess, "mx_quantize launch failed: ", hipGetErrorString(e));
   if (!w.is_same(wire)) wire.copy_(w);
   return wire;
 }
 
-at::Tensor mx_reduce(const at::Tensor& wire, int nsrc, const std::string& op, const c10::optional<at::Tensor>& out) {
+at::Tensor mx_reduce(const at::Tensor& wire, int nsrc, const std::string& op, const c10::optional<at::Tensor>& out,
+                     const std::string& fmt) {
+  const MxFormat f = mx_format(fmt, "mx_reduce");
   mx_check_wire(wire, "mx_reduce");
   TORCH_CHECK(nsrc >= 1 && nsrc <= pdcc::kern::kMaxRanks, "mx_reduce: 1..8 sources");
   TORCH_CHECK_VALUE(op == "sum" || op == "avg", "mx_reduce: op must be 'sum' or 'avg', got '", op, "'");
   const int64_t chunk = wire.numel() / nsrc;
-  TORCH_CHECK(chunk > 0 && chunk * nsrc == wire.numel() && chunk % (33 * 16) == 0, "mx_reduce: ", wire.numel(),
-              " bytes are not ", nsrc, " chunk wires (33 bytes per block, blocks in groups of 16)");
-  const size_t cb = (size_t)chunk / 33;
+  const int64_t bw = (int64_t)pdcc::kern::mx_block_wire(f);  // 33 or 17
+  TORCH_CHECK(chunk > 0 && chunk * nsrc == wire.numel() && chunk % (bw * 16) == 0, "mx_reduce: ", wire.numel(),
+              " bytes are not ", nsrc, " chunk wires (", bw, " bytes per block, blocks in groups of 16)");
+  const size_t cb = (size_t)(chunk / bw);
   c10::hip::HIPGuardMasqueradingAsCUDA g(wire.device());
   at::Tensor res = out ? *out : at::empty({chunk}, wire.options());
   mx_check_wire(res, "mx_reduce");
   TORCH_CHECK(res.device() == wire.device() && res.numel() == chunk, "mx_reduce: out must hold ", chunk, " bytes");
   at::Tensor in = mx_in(wire), o = mx_out(res);
   hipStream_t s = c10::hip::getCurrentHIPStreamMasqueradingAsCUDA(wire.device().index()).stream();
-  hipError_t e = pdcc::kern::mx_reduce(in.data_ptr(), nsrc, cb, kop(op), nsrc, o.data_ptr(), s);
+  hipError_t e = pdcc::kern::mx_reduce(in.data_ptr(), nsrc, cb, kop(op), nsrc, o.data_ptr(), s, f);
   TORCH_CHECK(e == hipSuccess, "mx_reduce launch failed: ", hipGetErrorString(e));
   if (!o.is_same(res)) res.copy_(o);
   return res;
 }
 
-void mx_dequantize(const at::Tensor& wire, int world, at::Tensor& out) {
+void mx_dequantize(const at::Tensor& wire, int world, at::Tensor& out, const std::string& fmt) {
+  const MxFormat f = mx_format(fmt, "mx_dequantize");
   mx_check_wire(wire, "mx_dequantize");
   TORCH_CHECK(world >= 1, "mx_dequantize: world must be >= 1");
   TORCH_CHECK(out.is_cuda() && out.device() == wire.device(), "mx_dequantize: out must be on the wire's GPU");
   const auto d = mx_dtype(out, "mx_dequantize");
   const size_t numel = (size_t)out.numel();
-  const size_t cb = pdcc::kern::mx_chunk_blocks(numel, world);
-  TORCH_CHECK((size_t)wire.numel() == pdcc::kern::mx_wire_bytes(cb, (size_t)world), "mx_dequantize: the wire of ",
-              numel, " elements in ", world, " chunks has ", pdcc::kern::mx_wire_bytes(cb, (size_t)world),
+  const size_t cb = pdcc::kern::mx_chunk_blocks(f, numel, world);
+  TORCH_CHECK((size_t)wire.numel() == pdcc::kern::mx_wire_bytes(f, cb, (size_t)world), "mx_dequantize: the wire of ",
+              numel, " elements in ", world, " chunks has ", pdcc::kern::mx_wire_bytes(f, cb, (size_t)world),
               " bytes, got ", wire.numel());
   c10::hip::HIPGuardMasqueradingAsCUDA g(wire.device());
   at::Tensor w = mx_in(wire), o = mx_out(out);
   hipStream_t s = c10::hip::getCurrentHIPStreamMasqueradingAsCUDA(wire.device().index()).stream();
-  hipError_t e = pdcc::kern::mx_dequantize(w.data_ptr(), cb, (size_t)world, o.data_ptr(), numel, d, s);
+  hipError_t e = pdcc::kern::mx_dequantize(w.data_ptr(), cb, (size_t)world, o.data_ptr(), numel, d, s, f);
   TORCH_CHECK(e == hipSuccess, "mx_dequantize launch failed: ", hipGetErrorString(e));
   if (!o.is_same(out)) out.copy_(o);
 }
 
 // ---- the shard layout (kernels/mx_layout.h): chunk r is shard r of `numel / world` elements
-at::Tensor mx_quantize_shards(const at::Tensor& x, int world, const c10::optional<at::Tensor>& out) {
+at::Tensor mx_quantize_shards(const at::Tensor& x, int world, const c10::optional<at::Tensor>& out,
+                              const std::string& fmt) {
+  const MxFormat f = mx_format(fmt, "mx_quantize_shards");
   TORCH_CHECK(x.is_cuda(), "mx_quantize_shards: GPU tensors only");
   TORCH_CHECK(world >= 1 && world <= 65535, "mx_quantize_shards: world must be 1..65535");
   const auto d = mx_dtype(x, "mx_quantize_shards");
   TORCH_CHECK_VALUE(x.numel() > 0 && x.numel() % world == 0, "mx_quantize_shards: ", x.numel(),
                     " elements are not ", world, " shards of one or more elements");
   const size_t m = (size_t)x.numel() / (size_t)world;
-  const size_t cb = pdcc::kern::mx_shard_blocks(m);
-  const int64_t bytes = (int64_t)pdcc::kern::mx_shard_wire_bytes(m, (size_t)world);
+  const size_t cb = pdcc::kern::mx_shard_blocks(f, m);
+  const int64_t bytes = (int64_t)pdcc::kern::mx_shard_wire_bytes(f, m, (size_t)world);
   c10::hip::HIPGuardMasqueradingAsCUDA g(x.device());
   at::Tensor wire = out ? *out : at::empty({bytes}, x.options().dtype(at::kByte));
   mx_check_wire(wire, "mx_quantize_shards");
@@ -187,13 +201,14 @@ at::Tensor mx_quantize_shards(const at::Tensor& x, int world, const c10::optiona
               " bytes on ", x.device());
   at::Tensor src = mx_in(x), w = mx_out(wire);
   hipStream_t s = c10::hip::getCurrentHIPStreamMasqueradingAsCUDA(x.device().index()).stream();
-  hipError_t e = pdcc::kern::mx_quantize_shards(src.data_ptr(), m, d, w.data_ptr(), cb, (size_t)world, s);
+  hipError_t e = pdcc::kern::mx_quantize_shards(src.data_ptr(), m, d, w.data_ptr(), cb, (size_t)world, s, f);
   TORCH_CHECK(e == hipSuccess, "mx_quantize_shards launch failed: ", hipGetErrorString(e));
   if (!w.is_same(wire)) wire.copy_(w);
   return wire;
 }
 
-void mx_dequantize_shards(const at::Tensor& wire, int world, at::Tensor& out) {
+void mx_dequantize_shards(const at::Tensor& wire, int world, at::Tensor& out, const std::string& fmt) {
+  const MxFormat f = mx_format(fmt, "mx_dequantize_shards");
   mx_check_wire(wire, "mx_dequantize_shards");
   TORCH_CHECK(world >= 1 && world <= 65535, "mx_dequantize_shards: world must be 1..65535");
   TORCH_CHECK(out.is_cuda() && out.device() == wire.device(), "mx_dequantize_shards: out must be on the wire's GPU");
@@ -201,19 +216,20 @@ void mx_dequantize_shards(const at::Tensor& wire, int world, at::Tensor& out) {
   TORCH_CHECK_VALUE(out.numel() > 0 && out.numel() % world == 0, "mx_dequantize_shards: ", out.numel(),
                     " elements are not ", world, " shards of one or more elements");
   const size_t m = (size_t)out.numel() / (size_t)world;
-  const size_t cb = pdcc::kern::mx_shard_blocks(m);
-  const size_t bytes = pdcc::kern::mx_shard_wire_bytes(m, (size_t)world);
+  const size_t cb = pdcc::kern::mx_shard_blocks(f, m);
+  const size_t bytes = pdcc::kern::mx_shard_wire_bytes(f, m, (size_t)world);
   TORCH_CHECK((size_t)wire.numel() == bytes, "mx_dequantize_shards: the wire of ", world, " shards of ", m,
               " elements has ", bytes, " bytes, got ", wire.numel());
   c10::hip::HIPGuardMasqueradingAsCUDA g(wire.device());
   at::Tensor w = mx_in(wire), o = mx_out(out);
   hipStream_t s = c10::hip::getCurrentHIPStreamMasqueradingAsCUDA(wire.device().index()).stream();
-  hipError_t e = pdcc::kern::mx_dequantize_shards(w.data_ptr(), cb, (size_t)world, o.data_ptr(), m, d, s);
+  hipError_t e = pdcc::kern::mx_dequantize_shards(w.data_ptr(), cb, (size_t)world, o.data_ptr(), m, d, s, f);
   TORCH_CHECK(e == hipSuccess, "mx_dequantize_shards launch failed: ", hipGetErrorString(e));
   if (!o.is_same(out)) out.copy_(o);
 }
 
-void mx_fold(const at::Tensor& wire, int nsrc, const std::string& op, at::Tensor& out) {
+void mx_fold(const at::Tensor& wire, int nsrc, const std::string& op, at::Tensor& out, const std::string& fmt) {
+  const MxFormat f = mx_format(fmt, "mx_fold");
   mx_check_wire(wire, "mx_fold");
   TORCH_CHECK(nsrc >= 1 && nsrc <= pdcc::kern::kMaxRanks, "mx_fold: 1..8 sources");
   TORCH_CHECK_VALUE(op == "sum" || op == "avg", "mx_fold: op must be 'sum' or 'avg', got '", op, "'");
@@ -221,14 +237,14 @@ void mx_fold(const at::Tensor& wire, int nsrc, const std::string& op, at::Tensor
   const auto d = mx_dtype(out, "mx_fold");
   TORCH_CHECK_VALUE(out.numel() > 0, "mx_fold: out has no elements");
   const size_t numel = (size_t)out.numel();
-  const size_t cb = pdcc::kern::mx_shard_blocks(numel);
-  const size_t bytes = pdcc::kern::mx_wire_bytes(cb, (size_t)nsrc);
+  const size_t cb = pdcc::kern::mx_shard_blocks(f, numel);
+  const size_t bytes = pdcc::kern::mx_wire_bytes(f, cb, (size_t)nsrc);
   TORCH_CHECK((size_t)wire.numel() == bytes, "mx_fold: ", nsrc, " chunk wires of ", numel, " elements have ", bytes,
               " bytes, got ", wire.numel());
   c10::hip::HIPGuardMasqueradingAsCUDA g(wire.device());
   at::Tensor w = mx_in(wire), o = mx_out(out);
   hipStream_t s = c10::hip::getCurrentHIPStreamMasqueradingAsCUDA(wire.device().index()).stream();
-  hipError_t e = pdcc::kern::mx_fold(w.data_ptr(), nsrc, cb, kop(op), nsrc, o.data_ptr(), numel, d, s);
+  hipError_t e = pdcc::kern::mx_fold(w.data_ptr(), nsrc, cb, kop(op), nsrc, o.data_ptr(), numel, d, s, f);
   TORCH_CHECK(e == hipSuccess, "mx_fold launch failed: ", hipGetErrorString(e));
   if (!o.is_same(out)) out.copy_(o);
 }
@@ -388,19 +404,28 @@ PYBIND11_MODULE(_C, m) {
         py::arg("ntl") = -1,
         "K2: one-launch multi-tensor copy (max_blocks/depth 0 = defaults)");
   m.def("mx_quantize", &mx_quantize, py::arg("x"), py::arg("world") = 1, py::arg("out") = py::none(),
-        "tensor (f32 / bf16 / f16) -> mxfp8_e4m3 wire of `world` chunks, on the current stream");
+        py::arg("fmt") = "mxfp8_e4m3",
+        "tensor (f32 / bf16 / f16) -> mxfp8_e4m3 / mxfp4_e2m1 wire of `world` chunks, on the current stream");
   m.def("mx_reduce", &mx_reduce, py::arg("wire"), py::arg("nsrc"), py::arg("op") = "sum", py::arg("out") = py::none(),
+        py::arg("fmt") = "mxfp8_e4m3",
         "nsrc chunk wires back to back -> one chunk wire (dequantize, fold in f32 in source order, requantize)");
   m.def("mx_dequantize", &mx_dequantize, py::arg("wire"), py::arg("world"), py::arg("out"),
-        "mxfp8_e4m3 wire of `world` chunks -> out (f32 / bf16 / f16), exactly out.numel() elements");
+        py::arg("fmt") = "mxfp8_e4m3",
+        "mxfp8_e4m3 / mxfp4_e2m1 wire of `world` chunks -> out (f32 / bf16 / f16), exactly out.numel() elements");
   m.def("mx_quantize_shards", &mx_quantize_shards, py::arg("x"), py::arg("world"), py::arg("out") = py::none(),
-        "tensor of `world` shards -> shard wire: chunk r is the mxfp8_e4m3 wire of shard r alone");
+        py::arg("fmt") = "mxfp8_e4m3", "tensor of `world` shards -> shard wire: chunk r is the wire of shard r alone");
   m.def("mx_dequantize_shards", &mx_dequantize_shards, py::arg("wire"), py::arg("world"), py::arg("out"),
+        py::arg("fmt") = "mxfp8_e4m3",
         "shard wire of `world` chunks -> out: chunk r fills out[r m, (r + 1) m), m = out.numel() / world");
   m.def("mx_fold", &mx_fold, py::arg("wire"), py::arg("nsrc"), py::arg("op"), py::arg("out"),
+        py::arg("fmt") = "mxfp8_e4m3",
         "nsrc chunk wires of out.numel() elements -> out (dequantize, fold in f32 in source order, round once)");
-  m.def("mx_shard_blocks", [](int64_t m) { return (int64_t)pdcc::kern::mx_shard_blocks((size_t)m); });
-  m.def("mx_chunk_blocks", [](int64_t numel, int world) { return (int64_t)pdcc::kern::mx_chunk_blocks((size_t)numel, world); });
+  m.def("mx_shard_blocks", [](int64_t m, const std::string& fmt) {
+    return (int64_t)pdcc::kern::mx_shard_blocks(mx_format(fmt, "mx_shard_blocks"), (size_t)m);
+  }, py::arg("m"), py::arg("fmt") = "mxfp8_e4m3");
+  m.def("mx_chunk_blocks", [](int64_t numel, int world, const std::string& fmt) {
+    return (int64_t)pdcc::kern::mx_chunk_blocks(mx_format(fmt, "mx_chunk_blocks"), (size_t)numel, world);
+  }, py::arg("numel"), py::arg("world"), py::arg("fmt") = "mxfp8_e4m3");
   m.def("ipc_signal_bytes", &pdcc::kern::ipc_signal_bytes);
   m.def("device_links", &device_links,
         "peer links between every pair of visible GPUs: link type (xgmi/pcie), hops, p2p, atomics, perf_rank");

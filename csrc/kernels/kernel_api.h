@@ -15,6 +15,8 @@
 #include <stddef.h>
 #include <stdint.h>
 
+#include "mx_layout.h"
+
 namespace pdcc {
 namespace kern {
 
@@ -322,34 +324,35 @@ using IpcCall = IpcCallT<RawPtr>;
 size_t ipc_signal_bytes();
 hipError_t ipc_launch(const IpcView& view, const IpcCall& call, hipStream_t stream);
 
-// ---------------------------------------------------------------- block-scaled FP8 wire (mxfp8_e4m3)
-// Layout: mx_layout.h; contract: docs/collectives.md "Compressed all-reduce". Single-GPU streaming
-// kernels (mx_wire.hip). `wire` buffers and the tensors are 16-byte aligned; `cb` (blocks per chunk) is
-// a multiple of 16.
+// ---------------------------------------------------------------- block-scaled wires (mxfp8_e4m3, mxfp4_e2m1)
+// Layout: mx_layout.h; contract: docs/collectives.md "Compressed all-reduce" and "The `mxfp4_e2m1`
+// wire format". Single-GPU streaming kernels (mx_wire.hip). `wire` buffers and the tensors are 16-byte
+// aligned; `cb` (blocks per chunk) is a multiple of 16; `fmt` picks the payload (32 float8_e4m3fn
+// bytes or 16 bytes of e2m1 nibbles per block) and with it the chunk size (33 cb or 17 cb bytes).
 // Tensor (`t` in F32 / BF16 / F16, `numel` <= 32 cb nchunks elements) -> nchunks chunk wires. Every
 // block of every chunk is written (padding: scale 127, payload 0); nothing past src + numel is read.
 hipError_t mx_quantize(const void* src, size_t numel, DType t, void* wire, size_t cb, size_t nchunks,
-                       hipStream_t stream);
+                       hipStream_t stream, MxFormat fmt = MxFormat::FP8_E4M3);
 // `nsrc` (1..kMaxRanks) chunk wires back to back -> one chunk wire: dequantize, fold in f32 in source
 // order (`op` SUM or AVG; AVG divides by avg_div), requantize.
 hipError_t mx_reduce(const void* wire_in, int nsrc, size_t cb, RedOp op, int avg_div, void* wire_out,
-                     hipStream_t stream);
+                     hipStream_t stream, MxFormat fmt = MxFormat::FP8_E4M3);
 // nchunks chunk wires -> exactly `numel` elements of `dst`, rounded once to `t`.
 hipError_t mx_dequantize(const void* wire, size_t cb, size_t nchunks, void* dst, size_t numel, DType t,
-                         hipStream_t stream);
+                         hipStream_t stream, MxFormat fmt = MxFormat::FP8_E4M3);
 // The shard layout (mx_layout.h): chunk r is shard r, the `m` elements from r * m on, cb >=
 // mx_blocks(m). Quantize reads nchunks * m elements and writes every block of every chunk; dequantize
 // writes exactly dst[0, nchunks * m). 16-byte vectors when m * element size is a multiple of 16 (every
 // shard then starts aligned), single elements otherwise.
 hipError_t mx_quantize_shards(const void* src, size_t m, DType t, void* wire, size_t cb, size_t nchunks,
-                              hipStream_t stream);
+                              hipStream_t stream, MxFormat fmt = MxFormat::FP8_E4M3);
 hipError_t mx_dequantize_shards(const void* wire, size_t cb, size_t nchunks, void* dst, size_t m, DType t,
-                                hipStream_t stream);
+                                hipStream_t stream, MxFormat fmt = MxFormat::FP8_E4M3);
 // `nsrc` (1..kMaxRanks) chunk wires back to back -> exactly `numel` (1..32 cb) elements of `dst`:
 // dequantize, fold in f32 in source order (AVG divides by avg_div), round once to `t`. What mx_reduce
 // then mx_dequantize compute, without the requantization in between.
 hipError_t mx_fold(const void* wire_in, int nsrc, size_t cb, RedOp op, int avg_div, void* dst, size_t numel, DType t,
-                   hipStream_t stream);
+                   hipStream_t stream, MxFormat fmt = MxFormat::FP8_E4M3);
 
 }  // namespace kern
 }  // namespace pdcc

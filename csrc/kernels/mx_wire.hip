@@ -1,8 +1,8 @@
-// The local kernels of the block-scaled FP8 wire format `mxfp8_e4m3` (layout: mx_layout.h,
-// contract: docs/collectives.md "Compressed all-reduce" and "Compressed reduce-scatter and
-// all-gather"):
+// The local kernels of the block-scaled wire formats `mxfp8_e4m3` and `mxfp4_e2m1` (layout:
+// mx_layout.h, contract: docs/collectives.md "Compressed all-reduce", "Compressed reduce-scatter and
+// all-gather" and "The `mxfp4_e2m1` wire format"):
 //
-//   mx_quantize    f32 / bf16 / f16 tensor -> wire           (reads 4n or 2n, writes 33n/32)
+//   mx_quantize    f32 / bf16 / f16 tensor -> wire           (reads 4n or 2n, writes 33n/32 or 17n/32)
 //   mx_reduce      nsrc chunk wires -> one chunk wire         (dequantize, fold in f32, requantize)
 //   mx_dequantize  wire -> f32 / bf16 / f16 tensor
 //   mx_fold        nsrc chunk wires -> f32 / bf16 / f16 tensor (dequantize, fold in f32, round once)
@@ -20,6 +20,13 @@
 // product x * 2^-e is one f32 multiply with subnormals kept (the default kernel mode), the
 // narrowing is the packed convert the FP8 reductions use (nearest even), and 2^e never overflows
 // or flushes: e is clamped to [-117, 120].
+//
+// Every kernel is a template over the format (MxFmt below): the formats share the lane layout on the
+// tensor side and differ in the bytes a lane moves on the wire side (half as many for FP4), in the
+// scale rule and in the packed converts. The FP4 payload goes through v_cvt_scalef32_pk_fp4_f32 /
+// v_cvt_scalef32_pk_f32_fp4 with a unit scale operand: the product with 2^-e (2^e) is the same f32
+// multiply as on the FP8 path, so the scale byte 255 -> NaN and the inf at the very top of the range
+// come out of ordinary f32 arithmetic. e is clamped to [-125, 126] there.
 #include <algorithm>
 
 #include "dev_common.h"
@@ -31,6 +38,7 @@ namespace dev {
 namespace {
 
 using F8 = Tr<DType::F8E4M3>;
+using kern::MxFormat;
 constexpr int kMxUnroll = 4;  // independent 16-B loads in flight per lane (quantize / dequantize)
 
 // quad_perm [1,0,3,2], quad_perm [2,3,0,1], row_half_mirror: lane ^ 1, lane ^ 2, 7 - lane (of 8)
@@ -41,10 +49,10 @@ __device__ __forceinline__ uint32_t dpp_max(uint32_t x) {
   const uint32_t y = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, CTRL, 0xf, 0xf, true);
   return x > y ? x : y;
 }
-// max over the LANES (2, 4 or 8) aligned neighbours that share a block; every one of them is active
+// max over the LANES (1, 2, 4 or 8) aligned neighbours that share a block; every one of them is active
 template <int LANES>
 __device__ __forceinline__ uint32_t group_max(uint32_t x) {
-  x = dpp_max<kDppXor1>(x);
+  if constexpr (LANES >= 2) x = dpp_max<kDppXor1>(x);
   if constexpr (LANES >= 4) x = dpp_max<kDppXor2>(x);
   if constexpr (LANES >= 8) x = dpp_max<kDppHalfMirror>(x);  // (both quads hold their max by now)
   return x;
@@ -85,21 +93,124 @@ __device__ __forceinline__ void widen4(uint32_t w, float scale, float* f) {
   f[0] = lo[0] * scale; f[1] = lo[1] * scale; f[2] = hi[0] * scale; f[3] = hi[1] * scale;
 }
 
+// e2m1: element 2j of a dword's eight sits in the low nibble of byte j, element 2j + 1 in the high one.
+// The scale operand of the converts is 1: the kernels multiply in f32 (see the top of the file).
+__device__ __forceinline__ uint32_t fp4_narrow4(float a, float b, float c, float d, float inv, uint32_t old, bool hi) {
+  if (hi) {
+    old = __builtin_amdgcn_cvt_scalef32_pk_fp4_f32(old, a * inv, b * inv, 1.0f, 2);
+    return __builtin_amdgcn_cvt_scalef32_pk_fp4_f32(old, c * inv, d * inv, 1.0f, 3);
+  }
+  old = __builtin_amdgcn_cvt_scalef32_pk_fp4_f32(old, a * inv, b * inv, 1.0f, 0);
+  return __builtin_amdgcn_cvt_scalef32_pk_fp4_f32(old, c * inv, d * inv, 1.0f, 1);
+}
+__device__ __forceinline__ void fp4_widen8(uint32_t w, float scale, float* f) {
+  const f32x2 a = __builtin_amdgcn_cvt_scalef32_pk_f32_fp4(w, 1.0f, 0);
+  const f32x2 b = __builtin_amdgcn_cvt_scalef32_pk_f32_fp4(w, 1.0f, 1);
+  const f32x2 c = __builtin_amdgcn_cvt_scalef32_pk_f32_fp4(w, 1.0f, 2);
+  const f32x2 d = __builtin_amdgcn_cvt_scalef32_pk_f32_fp4(w, 1.0f, 3);
+  f[0] = a[0] * scale; f[1] = a[1] * scale; f[2] = b[0] * scale; f[3] = b[1] * scale;
+  f[4] = c[0] * scale; f[5] = c[1] * scale; f[6] = d[0] * scale; f[7] = d[1] * scale;
+}
+__device__ __forceinline__ MxScale mx4_scale(uint32_t amax) {
+  // the smallest e with amax 2^-e <= 6 = 1.5 2^2 is k - 2 for m <= 1.5 and k - 1 above; the lower
+  // clamp keeps 0.5 2^e a normal f32, the upper one is never reached (k <= 127)
+  int e = (int)(amax >> 23) - 127 - 2 + ((amax & 0x7fffffu) > 0x400000u ? 1 : 0);
+  e = e < -125 ? -125 : (e > 126 ? 126 : e);
+  const bool special = amax >= 0x7f800000u;
+  if (amax == 0) e = 0;
+  MxScale r;
+  r.byte = special ? 255u : (uint32_t)(e + 127);
+  r.inv = __uint_as_float((uint32_t)(127 - e) << 23);
+  r.blank = special || amax == 0;
+  return r;
+}
+
+// What the kernels need of a format: payload bytes per block, the scale of a block, and N elements
+// (4, 8, 16 or 32) to and from their N * kPayload / 32 payload bytes, held in dwords (kWords<N> of
+// them; FP4 with N = 4 fills the low half of one). pack writes zeros for a blank block.
+template <MxFormat F> struct MxFmt;
+template <> struct MxFmt<MxFormat::FP8_E4M3> {
+  static constexpr int kPayload = 32;
+  template <int N> static constexpr int kWords = N / 4;
+  __device__ static __forceinline__ MxScale scale(uint32_t amax) { return mx_scale(amax); }
+  template <int N> __device__ static __forceinline__ void pack(const float* f, const MxScale& sc, uint32_t* q) {
+#pragma unroll
+    for (int d = 0; d < N / 4; ++d) {
+      q[d] = narrow4(f[4 * d], f[4 * d + 1], f[4 * d + 2], f[4 * d + 3], sc.inv);
+      if (sc.blank) q[d] = 0u;
+    }
+  }
+  template <int N> __device__ static __forceinline__ void unpack(const uint32_t* q, float scale, float* f) {
+#pragma unroll
+    for (int d = 0; d < N / 4; ++d) widen4(q[d], scale, f + 4 * d);
+  }
+};
+template <> struct MxFmt<MxFormat::FP4_E2M1> {
+  static constexpr int kPayload = 16;
+  template <int N> static constexpr int kWords = (N + 7) / 8;
+  __device__ static __forceinline__ MxScale scale(uint32_t amax) { return mx4_scale(amax); }
+  template <int N> __device__ static __forceinline__ void pack(const float* f, const MxScale& sc, uint32_t* q) {
+#pragma unroll
+    for (int d = 0; d < (N + 7) / 8; ++d) {
+      q[d] = fp4_narrow4(f[8 * d], f[8 * d + 1], f[8 * d + 2], f[8 * d + 3], sc.inv, 0u, false);
+      if constexpr (N >= 8) q[d] = fp4_narrow4(f[8 * d + 4], f[8 * d + 5], f[8 * d + 6], f[8 * d + 7], sc.inv, q[d], true);
+      if (sc.blank) q[d] = 0u;
+    }
+  }
+  template <int N> __device__ static __forceinline__ void unpack(const uint32_t* q, float scale, float* f) {
+    if constexpr (N == 4) {
+      float g[8];
+      fp4_widen8(q[0], scale, g);
+      f[0] = g[0]; f[1] = g[1]; f[2] = g[2]; f[3] = g[3];  // (the converts of the unused half fall away)
+    } else {
+#pragma unroll
+      for (int d = 0; d < N / 8; ++d) fp4_widen8(q[d], scale, f + 8 * d);
+    }
+  }
+};
+
+// B (2, 4, 8 or 16) wire bytes at p (B-aligned) <-> the low bytes of q[(B + 3) / 4]
+template <int B>
+__device__ __forceinline__ void ld_wire(const char* p, uint32_t* q) {
+  if constexpr (B == 2) {
+    q[0] = *reinterpret_cast<const uint16_t*>(p);
+  } else if constexpr (B == 4) {
+    q[0] = *reinterpret_cast<const uint32_t*>(p);
+  } else if constexpr (B == 8) {
+    const uint2 x = *reinterpret_cast<const uint2*>(p);
+    q[0] = x.x;
+    q[1] = x.y;
+  } else {
+    const uint4 x = *reinterpret_cast<const uint4*>(p);
+    q[0] = x.x; q[1] = x.y; q[2] = x.z; q[3] = x.w;
+  }
+}
+template <int B>
+__device__ __forceinline__ void st_wire(char* p, const uint32_t* q) {
+  if constexpr (B == 2) *reinterpret_cast<uint16_t*>(p) = (uint16_t)q[0];
+  else if constexpr (B == 4) *reinterpret_cast<uint32_t*>(p) = q[0];
+  else if constexpr (B == 8) *reinterpret_cast<uint2*>(p) = make_uint2(q[0], q[1]);
+  else *reinterpret_cast<uint4*>(p) = make_uint4(q[0], q[1], q[2], q[3]);
+}
+
 // ---------------------------------------------------------------------------- quantize
 // Lane layout of one chunk (grid row): vector v of the chunk is 16 B of the tensor = EPL elements,
 // LPB = 32 / EPL consecutive lanes make a block. The chunk has cb * LPB vectors, a multiple of 64.
 // SHARD: chunk r is the `m` elements from r * m on (numel = nchunks * m) instead of the 32 cb from
 // r * 32 cb on, and nothing at or past (r + 1) * m enters it. VEC = false (shards that do not start
-// 16-byte aligned) reads every element on its own.
-template <DType DT, bool SHARD, bool VEC>
+// 16-byte aligned) reads every element on its own. On the wire a lane stores QB = EPL (FP8) or
+// EPL / 2 (FP4) payload bytes.
+template <MxFormat F, DType DT, bool SHARD, bool VEC>
 __global__ __launch_bounds__(256) void k_mx_quantize(const char* __restrict__ src, size_t numel,
                                                      char* __restrict__ wire, uint32_t cb, size_t m) {
   using T = Tr<DT>;
   using S = typename T::S;
   constexpr int EPL = 16 / (int)sizeof(S);
   constexpr int LPB = kern::kMxBlock / EPL;
+  using M = MxFmt<F>;
+  constexpr int QB = EPL * M::kPayload / kern::kMxBlock, QW = M::template kWords<EPL>;
   const size_t chunk = blockIdx.y;
-  char* __restrict__ w = wire + chunk * kern::mx_chunk_bytes(cb);
+  char* __restrict__ w = wire + chunk * kern::mx_chunk_bytes(F, cb);
   const size_t el0 = SHARD ? chunk * m : chunk * cb * (size_t)kern::kMxBlock;  // first element of the chunk
   const size_t end = SHARD ? el0 + m : numel;                                  // one past its last
   const uint32_t nvec = cb * LPB;
@@ -138,17 +249,12 @@ __global__ __launch_bounds__(256) void k_mx_quantize(const char* __restrict__ sr
         const uint32_t a = abs_bits(f[i]);
         am = a > am ? a : am;
       }
-      const MxScale sc = mx_scale(group_max<LPB>(am));
-      uint32_t q[EPL / 4];
-#pragma unroll
-      for (int d = 0; d < EPL / 4; ++d) {
-        q[d] = narrow4(f[4 * d], f[4 * d + 1], f[4 * d + 2], f[4 * d + 3], sc.inv);
-        if (sc.blank) q[d] = 0u;
-      }
-      char* p = w + (size_t)v * EPL;  // payload byte e of the chunk is element e of the chunk
-      if constexpr (EPL == 4) *reinterpret_cast<uint32_t*>(p) = q[0];
-      else *reinterpret_cast<uint2*>(p) = make_uint2(q[0], q[1]);
-      if (v % LPB == 0) w[kern::mx_scale_off(cb, v / LPB)] = (char)sc.byte;
+      const MxScale sc = M::scale(group_max<LPB>(am));
+      uint32_t q[QW];
+      M::template pack<EPL>(f, sc, q);
+      // FP8: payload byte e of the chunk is element e of the chunk; FP4: byte e holds elements 2e, 2e + 1
+      st_wire<QB>(w + (size_t)v * QB, q);
+      if (v % LPB == 0) w[kern::mx_scale_off(F, cb, v / LPB)] = (char)sc.byte;
     }
   }
 }
@@ -157,15 +263,17 @@ __global__ __launch_bounds__(256) void k_mx_quantize(const char* __restrict__ sr
 // The same lane layout as quantize: a lane reads EPL payload bytes and its block's scale byte and
 // stores 16 B of the tensor; nothing at or past `numel` is written. SHARD / VEC as in quantize:
 // chunk r fills exactly dst[r m, (r + 1) m).
-template <DType DT, bool SHARD, bool VEC>
+template <MxFormat F, DType DT, bool SHARD, bool VEC>
 __global__ __launch_bounds__(256) void k_mx_dequantize(const char* __restrict__ wire, uint32_t cb,
                                                        char* __restrict__ dst, size_t numel, size_t m) {
   using T = Tr<DT>;
   using S = typename T::S;
   constexpr int EPL = 16 / (int)sizeof(S);
   constexpr int LPB = kern::kMxBlock / EPL;
+  using M = MxFmt<F>;
+  constexpr int QB = EPL * M::kPayload / kern::kMxBlock, QW = M::template kWords<EPL>;
   const size_t chunk = blockIdx.y;
-  const char* __restrict__ w = wire + chunk * kern::mx_chunk_bytes(cb);
+  const char* __restrict__ w = wire + chunk * kern::mx_chunk_bytes(F, cb);
   const size_t el0 = SHARD ? chunk * m : chunk * cb * (size_t)kern::kMxBlock;
   if (el0 >= numel) return;  // a padding chunk
   const size_t left = SHARD ? m : numel - el0;
@@ -174,24 +282,17 @@ __global__ __launch_bounds__(256) void k_mx_dequantize(const char* __restrict__ 
   constexpr uint32_t stride = 256u;  // (contiguous spans per workgroup, as in quantize)
   const uint32_t pass = gridDim.x * 256u * kMxUnroll;
   for (uint32_t v0 = blockIdx.x * 256u * kMxUnroll + threadIdx.x; v0 < nvec; v0 += pass) {
-    uint32_t q[kMxUnroll][EPL / 4];
+    uint32_t q[kMxUnroll][QW];
     uint32_t sb[kMxUnroll];
 #pragma unroll
     for (int u = 0; u < kMxUnroll; ++u) {
       const uint32_t v = v0 + u * stride;
       sb[u] = 127u;
 #pragma unroll
-      for (int d = 0; d < EPL / 4; ++d) q[u][d] = 0u;
+      for (int d = 0; d < QW; ++d) q[u][d] = 0u;
       if (v < nvec) {
-        const char* p = w + (size_t)v * EPL;
-        if constexpr (EPL == 4) {
-          q[u][0] = *reinterpret_cast<const uint32_t*>(p);
-        } else {
-          const uint2 x = *reinterpret_cast<const uint2*>(p);
-          q[u][0] = x.x;
-          q[u][1] = x.y;
-        }
-        sb[u] = (uint8_t)w[kern::mx_scale_off(cb, v / LPB)];
+        ld_wire<QB>(w + (size_t)v * QB, q[u]);
+        sb[u] = (uint8_t)w[kern::mx_scale_off(F, cb, v / LPB)];
       }
     }
 #pragma unroll
@@ -200,8 +301,7 @@ __global__ __launch_bounds__(256) void k_mx_dequantize(const char* __restrict__ 
       if (v >= nvec) break;
       const float scale = mx_scale_value(sb[u]);
       float f[EPL];
-#pragma unroll
-      for (int d = 0; d < EPL / 4; ++d) widen4(q[u][d], scale, f + 4 * d);
+      M::template unpack<EPL>(q[u], scale, f);
       S s[EPL];
 #pragma unroll
       for (int i = 0; i < EPL; ++i) s[i] = T::out(f[i]);
@@ -221,13 +321,18 @@ __global__ __launch_bounds__(256) void k_mx_dequantize(const char* __restrict__ 
 }
 
 // ---------------------------------------------------------------------------- reduce
-// A lane takes 16 payload bytes (half a block) of every source, so a block is two neighbouring
-// lanes and the amax of the folded block is one exchange between them.
-template <int NSRC, bool AVG>
+// A lane takes 16 payload bytes of every source. FP8: that is half a block, so a block is two
+// neighbouring lanes and the amax of the folded block is one exchange between them. FP4: 16 payload
+// bytes are a whole block (EPL = 32), so the lane holds its block's amax and there is no exchange;
+// the price is 32 accumulators per lane instead of 16.
+template <MxFormat F, int NSRC, bool AVG>
 __global__ __launch_bounds__(256) void k_mx_reduce(const char* __restrict__ in, uint32_t cb, int avg_div,
                                                    char* __restrict__ out) {
-  const size_t cbytes = kern::mx_chunk_bytes(cb);
-  const uint32_t nvec = cb * 2u;
+  using M = MxFmt<F>;
+  constexpr int EPL = 16 * kern::kMxBlock / M::kPayload;  // 16 or 32
+  constexpr int LPB = kern::kMxBlock / EPL;               // 2 or 1
+  const size_t cbytes = kern::mx_chunk_bytes(F, cb);
+  const uint32_t nvec = cb * (uint32_t)LPB;
   const uint32_t stride = gridDim.x * 256u;
   for (uint32_t v = blockIdx.x * 256u + threadIdx.x; v < nvec; v += stride) {
     uint4 p[NSRC];
@@ -236,51 +341,46 @@ __global__ __launch_bounds__(256) void k_mx_reduce(const char* __restrict__ in, 
     for (int r = 0; r < NSRC; ++r) {
       const char* c = in + (size_t)r * cbytes;
       p[r] = *reinterpret_cast<const uint4*>(c + (size_t)v * 16);
-      sb[r] = (uint8_t)c[kern::mx_scale_off(cb, v >> 1)];
+      sb[r] = (uint8_t)c[kern::mx_scale_off(F, cb, v / LPB)];
     }
-    float acc[16];
+    float acc[EPL];
 #pragma unroll
     for (int r = 0; r < NSRC; ++r) {
       const float scale = mx_scale_value(sb[r]);
       const uint32_t w[4] = {p[r].x, p[r].y, p[r].z, p[r].w};
-      float f[16];
+      float f[EPL];
+      M::template unpack<EPL>(w, scale, f);
 #pragma unroll
-      for (int d = 0; d < 4; ++d) widen4(w[d], scale, f + 4 * d);
-#pragma unroll
-      for (int i = 0; i < 16; ++i) acc[i] = r == 0 ? f[i] : acc[i] + f[i];  // rank order
+      for (int i = 0; i < EPL; ++i) acc[i] = r == 0 ? f[i] : acc[i] + f[i];  // rank order
     }
     if constexpr (AVG) {
 #pragma unroll
-      for (int i = 0; i < 16; ++i) acc[i] = acc[i] / (float)avg_div;
+      for (int i = 0; i < EPL; ++i) acc[i] = acc[i] / (float)avg_div;
     }
     uint32_t am = 0;
 #pragma unroll
-    for (int i = 0; i < 16; ++i) {
+    for (int i = 0; i < EPL; ++i) {
       const uint32_t a = abs_bits(acc[i]);
       am = a > am ? a : am;
     }
-    const MxScale sc = mx_scale(group_max<2>(am));
+    const MxScale sc = M::scale(group_max<LPB>(am));
     uint32_t q[4];
-#pragma unroll
-    for (int d = 0; d < 4; ++d) {
-      q[d] = narrow4(acc[4 * d], acc[4 * d + 1], acc[4 * d + 2], acc[4 * d + 3], sc.inv);
-      if (sc.blank) q[d] = 0u;
-    }
+    M::template pack<EPL>(acc, sc, q);
     *reinterpret_cast<uint4*>(out + (size_t)v * 16) = make_uint4(q[0], q[1], q[2], q[3]);
-    if ((v & 1u) == 0) out[kern::mx_scale_off(cb, v >> 1)] = (char)sc.byte;
+    if (v % LPB == 0) out[kern::mx_scale_off(F, cb, v / LPB)] = (char)sc.byte;
   }
 }
 
 // ---------------------------------------------------------------------------- fold
 // nsrc chunk wires -> a tensor: what mx_reduce then mx_dequantize would give without the wire in
 // between (and without its requantization). The lane layout is dequantize's: the wide side is the
-// output, 16 B = EPL elements per lane, so a lane reads EPL payload bytes and its block's scale byte
+// output, 16 B = EPL elements per lane, so a lane reads EPL (FP4: EPL / 2) payload bytes and its block's scale byte
 // of every source and a wave's store is contiguous. All NSRC * U loads are issued before the first
 // convert; U keeps about eight of them in flight per lane whatever NSRC is.
 template <int NSRC>
 constexpr int kMxFoldUnroll = NSRC <= 2 ? 4 : (NSRC <= 4 ? 2 : 1);
 
-template <DType DT, int NSRC, bool AVG>
+template <MxFormat F, DType DT, int NSRC, bool AVG>
 __global__ __launch_bounds__(256) void k_mx_fold(const char* __restrict__ in, uint32_t cb, int avg_div,
                                                  char* __restrict__ dst, size_t numel) {
   using T = Tr<DT>;
@@ -288,11 +388,13 @@ __global__ __launch_bounds__(256) void k_mx_fold(const char* __restrict__ in, ui
   constexpr int EPL = 16 / (int)sizeof(S);
   constexpr int LPB = kern::kMxBlock / EPL;
   constexpr int U = kMxFoldUnroll<NSRC>;
-  const size_t cbytes = kern::mx_chunk_bytes(cb);
+  using M = MxFmt<F>;
+  constexpr int QB = EPL * M::kPayload / kern::kMxBlock, QW = M::template kWords<EPL>;
+  const size_t cbytes = kern::mx_chunk_bytes(F, cb);
   const uint32_t nvec = (uint32_t)((numel + EPL - 1) / EPL);  // <= cb * LPB: numel <= 32 cb
   const uint32_t pass = gridDim.x * 256u * U;
   for (uint32_t v0 = blockIdx.x * 256u * U + threadIdx.x; v0 < nvec; v0 += pass) {
-    uint32_t q[U][NSRC][EPL / 4];
+    uint32_t q[U][NSRC][QW];
     uint32_t sb[U][NSRC];
 #pragma unroll
     for (int u = 0; u < U; ++u) {
@@ -301,18 +403,11 @@ __global__ __launch_bounds__(256) void k_mx_fold(const char* __restrict__ in, ui
       for (int r = 0; r < NSRC; ++r) {
         sb[u][r] = 127u;
 #pragma unroll
-        for (int d = 0; d < EPL / 4; ++d) q[u][r][d] = 0u;
+        for (int d = 0; d < QW; ++d) q[u][r][d] = 0u;
         if (v < nvec) {
           const char* c = in + (size_t)r * cbytes;
-          const char* p = c + (size_t)v * EPL;
-          if constexpr (EPL == 4) {
-            q[u][r][0] = *reinterpret_cast<const uint32_t*>(p);
-          } else {
-            const uint2 x = *reinterpret_cast<const uint2*>(p);
-            q[u][r][0] = x.x;
-            q[u][r][1] = x.y;
-          }
-          sb[u][r] = (uint8_t)c[kern::mx_scale_off(cb, v / LPB)];
+          ld_wire<QB>(c + (size_t)v * QB, q[u][r]);
+          sb[u][r] = (uint8_t)c[kern::mx_scale_off(F, cb, v / LPB)];
         }
       }
     }
@@ -325,8 +420,7 @@ __global__ __launch_bounds__(256) void k_mx_fold(const char* __restrict__ in, ui
       for (int r = 0; r < NSRC; ++r) {
         const float scale = mx_scale_value(sb[u][r]);
         float f[EPL];
-#pragma unroll
-        for (int d = 0; d < EPL / 4; ++d) widen4(q[u][r][d], scale, f + 4 * d);
+        M::template unpack<EPL>(q[u][r], scale, f);
 #pragma unroll
         for (int i = 0; i < EPL; ++i) acc[i] = r == 0 ? f[i] : acc[i] + f[i];  // source order
       }
@@ -371,141 +465,149 @@ namespace {
 bool mx_al16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 // cb: a multiple of 16, and a chunk's lanes are counted in 32 bits
 bool mx_cb_ok(size_t cb) { return cb > 0 && cb % kMxScaleAlign == 0 && cb <= (size_t(1) << 27); }
-}  // namespace
-
-hipError_t mx_quantize(const void* src, size_t numel, DType t, void* wire, size_t cb, size_t nchunks,
-                       hipStream_t stream) {
-  if (!mx_cb_ok(cb) || nchunks == 0 || nchunks > 65535 || !mx_al16(wire) || (numel && !mx_al16(src)))
-    return hipErrorInvalidValue;
-  if (numel > cb * nchunks * kMxBlock) return hipErrorInvalidValue;
-  const int lpb = t == DType::F32 ? 8 : 4;
-  const dim3 grid(dev::mx_grid_x((uint64_t)cb * lpb, dev::kMxUnroll, nchunks, dev::kMxGridStream), (uint32_t)nchunks);
-  const char* s = static_cast<const char*>(src);
-  char* w = static_cast<char*>(wire);
-  switch (t) {
-    case DType::F32: hipLaunchKernelGGL((dev::k_mx_quantize<DType::F32, false, true>), grid, dim3(256), 0, stream, s, numel, w, (uint32_t)cb, size_t(0)); break;
-    case DType::BF16: hipLaunchKernelGGL((dev::k_mx_quantize<DType::BF16, false, true>), grid, dim3(256), 0, stream, s, numel, w, (uint32_t)cb, size_t(0)); break;
-    case DType::F16: hipLaunchKernelGGL((dev::k_mx_quantize<DType::F16, false, true>), grid, dim3(256), 0, stream, s, numel, w, (uint32_t)cb, size_t(0)); break;
-    default: return hipErrorInvalidValue;
-  }
-  return hipGetLastError();
-}
-
-hipError_t mx_dequantize(const void* wire, size_t cb, size_t nchunks, void* dst, size_t numel, DType t,
-                         hipStream_t stream) {
-  if (!mx_cb_ok(cb) || nchunks == 0 || nchunks > 65535 || !mx_al16(wire) || (numel && !mx_al16(dst)))
-    return hipErrorInvalidValue;
-  if (numel > cb * nchunks * kMxBlock) return hipErrorInvalidValue;
-  if (numel == 0) return hipSuccess;
-  const int lpb = t == DType::F32 ? 8 : 4;
-  const dim3 grid(dev::mx_grid_x((uint64_t)cb * lpb, dev::kMxUnroll, nchunks, dev::kMxGridStream), (uint32_t)nchunks);
-  const char* w = static_cast<const char*>(wire);
-  char* d = static_cast<char*>(dst);
-  switch (t) {
-    case DType::F32: hipLaunchKernelGGL((dev::k_mx_dequantize<DType::F32, false, true>), grid, dim3(256), 0, stream, w, (uint32_t)cb, d, numel, size_t(0)); break;
-    case DType::BF16: hipLaunchKernelGGL((dev::k_mx_dequantize<DType::BF16, false, true>), grid, dim3(256), 0, stream, w, (uint32_t)cb, d, numel, size_t(0)); break;
-    case DType::F16: hipLaunchKernelGGL((dev::k_mx_dequantize<DType::F16, false, true>), grid, dim3(256), 0, stream, w, (uint32_t)cb, d, numel, size_t(0)); break;
-    default: return hipErrorInvalidValue;
-  }
-  return hipGetLastError();
-}
-
-namespace {
+bool mx_fmt_ok(MxFormat f) { return f == MxFormat::FP8_E4M3 || f == MxFormat::FP4_E2M1; }
 size_t mx_esize(DType t) { return t == DType::F32 ? 4 : 2; }
+bool mx_dtype_ok(DType t) { return t == DType::F32 || t == DType::BF16 || t == DType::F16; }
 // the shard arguments: m elements per shard fit the chunk, and the whole tensor's size is a size_t
 bool mx_shards_ok(size_t m, size_t cb, size_t nchunks) {
   return mx_cb_ok(cb) && m > 0 && m <= cb * kMxBlock && nchunks > 0 && nchunks <= 65535;
 }
-
-template <DType DT>
-void mx_quantize_shards_go(const dim3& grid, bool vec, const char* s, size_t numel, char* w, uint32_t cb, size_t m,
-                           hipStream_t stream) {
-  if (vec) hipLaunchKernelGGL((dev::k_mx_quantize<DT, true, true>), grid, dim3(256), 0, stream, s, numel, w, cb, m);
-  else hipLaunchKernelGGL((dev::k_mx_quantize<DT, true, false>), grid, dim3(256), 0, stream, s, numel, w, cb, m);
+dim3 mx_stream_grid(size_t cb, DType t, size_t nchunks) {
+  const int lpb = t == DType::F32 ? 8 : 4;
+  return dim3(dev::mx_grid_x((uint64_t)cb * lpb, dev::kMxUnroll, nchunks, dev::kMxGridStream), (uint32_t)nchunks);
 }
-template <DType DT>
-void mx_dequantize_shards_go(const dim3& grid, bool vec, const char* w, uint32_t cb, char* d, size_t numel, size_t m,
-                             hipStream_t stream) {
-  if (vec) hipLaunchKernelGGL((dev::k_mx_dequantize<DT, true, true>), grid, dim3(256), 0, stream, w, cb, d, numel, m);
-  else hipLaunchKernelGGL((dev::k_mx_dequantize<DT, true, false>), grid, dim3(256), 0, stream, w, cb, d, numel, m);
+
+// quantize / dequantize of one format and dtype: the dealt kernel, or the shard one with or without vectors
+template <MxFormat F, DType DT>
+void mx_quantize_go(bool shard, bool vec, const dim3& grid, const char* s, size_t numel, char* w, uint32_t cb, size_t m,
+                    hipStream_t stream) {
+  if (!shard) hipLaunchKernelGGL((dev::k_mx_quantize<F, DT, false, true>), grid, dim3(256), 0, stream, s, numel, w, cb, m);
+  else if (vec) hipLaunchKernelGGL((dev::k_mx_quantize<F, DT, true, true>), grid, dim3(256), 0, stream, s, numel, w, cb, m);
+  else hipLaunchKernelGGL((dev::k_mx_quantize<F, DT, true, false>), grid, dim3(256), 0, stream, s, numel, w, cb, m);
+}
+template <MxFormat F, DType DT>
+void mx_dequantize_go(bool shard, bool vec, const dim3& grid, const char* w, uint32_t cb, char* d, size_t numel, size_t m,
+                      hipStream_t stream) {
+  if (!shard) hipLaunchKernelGGL((dev::k_mx_dequantize<F, DT, false, true>), grid, dim3(256), 0, stream, w, cb, d, numel, m);
+  else if (vec) hipLaunchKernelGGL((dev::k_mx_dequantize<F, DT, true, true>), grid, dim3(256), 0, stream, w, cb, d, numel, m);
+  else hipLaunchKernelGGL((dev::k_mx_dequantize<F, DT, true, false>), grid, dim3(256), 0, stream, w, cb, d, numel, m);
+}
+template <MxFormat F, class... A>
+void mx_quantize_dt(DType t, A... a) {
+  switch (t) {
+    case DType::F32: mx_quantize_go<F, DType::F32>(a...); break;
+    case DType::BF16: mx_quantize_go<F, DType::BF16>(a...); break;
+    default: mx_quantize_go<F, DType::F16>(a...); break;
+  }
+}
+template <MxFormat F, class... A>
+void mx_dequantize_dt(DType t, A... a) {
+  switch (t) {
+    case DType::F32: mx_dequantize_go<F, DType::F32>(a...); break;
+    case DType::BF16: mx_dequantize_go<F, DType::BF16>(a...); break;
+    default: mx_dequantize_go<F, DType::F16>(a...); break;
+  }
+}
+hipError_t mx_quantize_any(MxFormat fmt, DType t, bool shard, bool vec, const void* src, size_t numel, void* wire,
+                           size_t cb, size_t nchunks, size_t m, hipStream_t stream) {
+  const dim3 grid = mx_stream_grid(cb, t, nchunks);
+  const char* s = static_cast<const char*>(src);
+  char* w = static_cast<char*>(wire);
+  if (fmt == MxFormat::FP4_E2M1) mx_quantize_dt<MxFormat::FP4_E2M1>(t, shard, vec, grid, s, numel, w, (uint32_t)cb, m, stream);
+  else mx_quantize_dt<MxFormat::FP8_E4M3>(t, shard, vec, grid, s, numel, w, (uint32_t)cb, m, stream);
+  return hipGetLastError();
+}
+hipError_t mx_dequantize_any(MxFormat fmt, DType t, bool shard, bool vec, const void* wire, size_t cb, size_t nchunks,
+                             void* dst, size_t numel, size_t m, hipStream_t stream) {
+  const dim3 grid = mx_stream_grid(cb, t, nchunks);
+  const char* w = static_cast<const char*>(wire);
+  char* d = static_cast<char*>(dst);
+  if (fmt == MxFormat::FP4_E2M1) mx_dequantize_dt<MxFormat::FP4_E2M1>(t, shard, vec, grid, w, (uint32_t)cb, d, numel, m, stream);
+  else mx_dequantize_dt<MxFormat::FP8_E4M3>(t, shard, vec, grid, w, (uint32_t)cb, d, numel, m, stream);
+  return hipGetLastError();
 }
 }  // namespace
 
+hipError_t mx_quantize(const void* src, size_t numel, DType t, void* wire, size_t cb, size_t nchunks,
+                       hipStream_t stream, MxFormat fmt) {
+  if (!mx_fmt_ok(fmt) || !mx_dtype_ok(t)) return hipErrorInvalidValue;
+  if (!mx_cb_ok(cb) || nchunks == 0 || nchunks > 65535 || !mx_al16(wire) || (numel && !mx_al16(src)))
+    return hipErrorInvalidValue;
+  if (numel > cb * nchunks * kMxBlock) return hipErrorInvalidValue;
+  return mx_quantize_any(fmt, t, false, true, src, numel, wire, cb, nchunks, 0, stream);
+}
+
+hipError_t mx_dequantize(const void* wire, size_t cb, size_t nchunks, void* dst, size_t numel, DType t,
+                         hipStream_t stream, MxFormat fmt) {
+  if (!mx_fmt_ok(fmt) || !mx_dtype_ok(t)) return hipErrorInvalidValue;
+  if (!mx_cb_ok(cb) || nchunks == 0 || nchunks > 65535 || !mx_al16(wire) || (numel && !mx_al16(dst)))
+    return hipErrorInvalidValue;
+  if (numel > cb * nchunks * kMxBlock) return hipErrorInvalidValue;
+  if (numel == 0) return hipSuccess;
+  return mx_dequantize_any(fmt, t, false, true, wire, cb, nchunks, dst, numel, 0, stream);
+}
+
 hipError_t mx_quantize_shards(const void* src, size_t m, DType t, void* wire, size_t cb, size_t nchunks,
-                              hipStream_t stream) {
+                              hipStream_t stream, MxFormat fmt) {
+  if (!mx_fmt_ok(fmt) || !mx_dtype_ok(t)) return hipErrorInvalidValue;
   if (!mx_shards_ok(m, cb, nchunks) || !mx_al16(wire) || !mx_al16(src)) return hipErrorInvalidValue;
-  if (t != DType::F32 && t != DType::BF16 && t != DType::F16) return hipErrorInvalidValue;
-  const int lpb = t == DType::F32 ? 8 : 4;
   const bool vec = m * mx_esize(t) % 16 == 0;  // every shard starts 16-byte aligned
-  const dim3 grid(dev::mx_grid_x((uint64_t)cb * lpb, dev::kMxUnroll, nchunks, dev::kMxGridStream), (uint32_t)nchunks);
-  const char* s = static_cast<const char*>(src);
-  char* w = static_cast<char*>(wire);
-  const size_t numel = m * nchunks;
-  switch (t) {
-    case DType::F32: mx_quantize_shards_go<DType::F32>(grid, vec, s, numel, w, (uint32_t)cb, m, stream); break;
-    case DType::BF16: mx_quantize_shards_go<DType::BF16>(grid, vec, s, numel, w, (uint32_t)cb, m, stream); break;
-    default: mx_quantize_shards_go<DType::F16>(grid, vec, s, numel, w, (uint32_t)cb, m, stream); break;
-  }
-  return hipGetLastError();
+  return mx_quantize_any(fmt, t, true, vec, src, m * nchunks, wire, cb, nchunks, m, stream);
 }
 
 hipError_t mx_dequantize_shards(const void* wire, size_t cb, size_t nchunks, void* dst, size_t m, DType t,
-                                hipStream_t stream) {
+                                hipStream_t stream, MxFormat fmt) {
+  if (!mx_fmt_ok(fmt) || !mx_dtype_ok(t)) return hipErrorInvalidValue;
   if (!mx_shards_ok(m, cb, nchunks) || !mx_al16(wire) || !mx_al16(dst)) return hipErrorInvalidValue;
-  if (t != DType::F32 && t != DType::BF16 && t != DType::F16) return hipErrorInvalidValue;
-  const int lpb = t == DType::F32 ? 8 : 4;
   const bool vec = m * mx_esize(t) % 16 == 0;
-  const dim3 grid(dev::mx_grid_x((uint64_t)cb * lpb, dev::kMxUnroll, nchunks, dev::kMxGridStream), (uint32_t)nchunks);
-  const char* w = static_cast<const char*>(wire);
-  char* d = static_cast<char*>(dst);
-  const size_t numel = m * nchunks;
-  switch (t) {
-    case DType::F32: mx_dequantize_shards_go<DType::F32>(grid, vec, w, (uint32_t)cb, d, numel, m, stream); break;
-    case DType::BF16: mx_dequantize_shards_go<DType::BF16>(grid, vec, w, (uint32_t)cb, d, numel, m, stream); break;
-    default: mx_dequantize_shards_go<DType::F16>(grid, vec, w, (uint32_t)cb, d, numel, m, stream); break;
-  }
-  return hipGetLastError();
+  return mx_dequantize_any(fmt, t, true, vec, wire, cb, nchunks, dst, m * nchunks, m, stream);
 }
 
 namespace {
-template <bool AVG>
+template <MxFormat F, bool AVG>
 hipError_t mx_reduce_go(const char* in, int nsrc, uint32_t cb, int avg_div, char* out, hipStream_t stream) {
-  const dim3 grid(dev::mx_grid_x((uint64_t)cb * 2, 1, 1, dev::kMxGridReduce)), block(256);
+  constexpr int lpb = F == MxFormat::FP4_E2M1 ? 1 : 2;  // lanes per block: 16 payload bytes per lane
+  const dim3 grid(dev::mx_grid_x((uint64_t)cb * lpb, 1, 1, dev::kMxGridReduce)), block(256);
   switch (nsrc) {
 #define PDCC_MX_N(N) \
-  case N: hipLaunchKernelGGL((dev::k_mx_reduce<N, AVG>), grid, block, 0, stream, in, cb, avg_div, out); break;
+  case N: hipLaunchKernelGGL((dev::k_mx_reduce<F, N, AVG>), grid, block, 0, stream, in, cb, avg_div, out); break;
     PDCC_MX_N(1) PDCC_MX_N(2) PDCC_MX_N(3) PDCC_MX_N(4) PDCC_MX_N(5) PDCC_MX_N(6) PDCC_MX_N(7) PDCC_MX_N(8)
 #undef PDCC_MX_N
     default: return hipErrorInvalidValue;
   }
   return hipGetLastError();
 }
+template <MxFormat F>
+hipError_t mx_reduce_op(const char* in, int nsrc, uint32_t cb, RedOp op, int avg_div, char* out, hipStream_t stream) {
+  return op == RedOp::AVG ? mx_reduce_go<F, true>(in, nsrc, cb, avg_div, out, stream)
+                          : mx_reduce_go<F, false>(in, nsrc, cb, avg_div, out, stream);
+}
 }  // namespace
 
 hipError_t mx_reduce(const void* wire_in, int nsrc, size_t cb, RedOp op, int avg_div, void* wire_out,
-                     hipStream_t stream) {
-  if (!mx_cb_ok(cb) || nsrc < 1 || nsrc > kMaxRanks || !mx_al16(wire_in) || !mx_al16(wire_out))
+                     hipStream_t stream, MxFormat fmt) {
+  if (!mx_fmt_ok(fmt) || !mx_cb_ok(cb) || nsrc < 1 || nsrc > kMaxRanks || !mx_al16(wire_in) || !mx_al16(wire_out))
     return hipErrorInvalidValue;
   if (op != RedOp::SUM && op != RedOp::AVG) return hipErrorInvalidValue;
   if (op == RedOp::AVG && avg_div < 1) return hipErrorInvalidValue;
   const char* in = static_cast<const char*>(wire_in);
   char* out = static_cast<char*>(wire_out);
-  return op == RedOp::AVG ? mx_reduce_go<true>(in, nsrc, (uint32_t)cb, avg_div, out, stream)
-                          : mx_reduce_go<false>(in, nsrc, (uint32_t)cb, avg_div, out, stream);
+  return fmt == MxFormat::FP4_E2M1 ? mx_reduce_op<MxFormat::FP4_E2M1>(in, nsrc, (uint32_t)cb, op, avg_div, out, stream)
+                                   : mx_reduce_op<MxFormat::FP8_E4M3>(in, nsrc, (uint32_t)cb, op, avg_div, out, stream);
 }
 
 namespace {
-template <DType DT, bool AVG>
+template <MxFormat F, DType DT, bool AVG>
 hipError_t mx_fold_go(const char* in, int nsrc, uint32_t cb, int avg_div, char* dst, size_t numel, hipStream_t stream) {
   constexpr int epl = 16 / (int)sizeof(typename dev::Tr<DT>::S);
   const uint64_t nvec = (numel + epl - 1) / epl;
   const dim3 block(256);
   switch (nsrc) {
-#define PDCC_MX_N(N)                                                                                        \
-  case N: {                                                                                                 \
-    const dim3 grid(dev::mx_grid_x(nvec, dev::kMxFoldUnroll<N>, 1, dev::kMxGridReduce));                    \
-    hipLaunchKernelGGL((dev::k_mx_fold<DT, N, AVG>), grid, block, 0, stream, in, cb, avg_div, dst, numel); \
-    break;                                                                                                  \
+#define PDCC_MX_N(N)                                                                                           \
+  case N: {                                                                                                    \
+    const dim3 grid(dev::mx_grid_x(nvec, dev::kMxFoldUnroll<N>, 1, dev::kMxGridReduce));                       \
+    hipLaunchKernelGGL((dev::k_mx_fold<F, DT, N, AVG>), grid, block, 0, stream, in, cb, avg_div, dst, numel); \
+    break;                                                                                                     \
   }
     PDCC_MX_N(1) PDCC_MX_N(2) PDCC_MX_N(3) PDCC_MX_N(4) PDCC_MX_N(5) PDCC_MX_N(6) PDCC_MX_N(7) PDCC_MX_N(8)
 #undef PDCC_MX_N
@@ -513,29 +615,35 @@ hipError_t mx_fold_go(const char* in, int nsrc, uint32_t cb, int avg_div, char* 
   }
   return hipGetLastError();
 }
-template <DType DT>
+template <MxFormat F, DType DT>
 hipError_t mx_fold_op(const char* in, int nsrc, uint32_t cb, RedOp op, int avg_div, char* dst, size_t numel,
                       hipStream_t stream) {
-  return op == RedOp::AVG ? mx_fold_go<DT, true>(in, nsrc, cb, avg_div, dst, numel, stream)
-                          : mx_fold_go<DT, false>(in, nsrc, cb, avg_div, dst, numel, stream);
+  return op == RedOp::AVG ? mx_fold_go<F, DT, true>(in, nsrc, cb, avg_div, dst, numel, stream)
+                          : mx_fold_go<F, DT, false>(in, nsrc, cb, avg_div, dst, numel, stream);
+}
+template <MxFormat F>
+hipError_t mx_fold_dt(DType t, const char* in, int nsrc, uint32_t cb, RedOp op, int avg_div, char* d, size_t numel,
+                      hipStream_t stream) {
+  switch (t) {
+    case DType::F32: return mx_fold_op<F, DType::F32>(in, nsrc, cb, op, avg_div, d, numel, stream);
+    case DType::BF16: return mx_fold_op<F, DType::BF16>(in, nsrc, cb, op, avg_div, d, numel, stream);
+    case DType::F16: return mx_fold_op<F, DType::F16>(in, nsrc, cb, op, avg_div, d, numel, stream);
+    default: return hipErrorInvalidValue;
+  }
 }
 }  // namespace
 
 hipError_t mx_fold(const void* wire_in, int nsrc, size_t cb, RedOp op, int avg_div, void* dst, size_t numel, DType t,
-                   hipStream_t stream) {
-  if (!mx_cb_ok(cb) || nsrc < 1 || nsrc > kMaxRanks || !mx_al16(wire_in) || !mx_al16(dst))
+                   hipStream_t stream, MxFormat fmt) {
+  if (!mx_fmt_ok(fmt) || !mx_cb_ok(cb) || nsrc < 1 || nsrc > kMaxRanks || !mx_al16(wire_in) || !mx_al16(dst))
     return hipErrorInvalidValue;
   if (numel == 0 || numel > cb * kMxBlock) return hipErrorInvalidValue;
   if (op != RedOp::SUM && op != RedOp::AVG) return hipErrorInvalidValue;
   if (op == RedOp::AVG && avg_div < 1) return hipErrorInvalidValue;
   const char* in = static_cast<const char*>(wire_in);
   char* d = static_cast<char*>(dst);
-  switch (t) {
-    case DType::F32: return mx_fold_op<DType::F32>(in, nsrc, (uint32_t)cb, op, avg_div, d, numel, stream);
-    case DType::BF16: return mx_fold_op<DType::BF16>(in, nsrc, (uint32_t)cb, op, avg_div, d, numel, stream);
-    case DType::F16: return mx_fold_op<DType::F16>(in, nsrc, (uint32_t)cb, op, avg_div, d, numel, stream);
-    default: return hipErrorInvalidValue;
-  }
+  return fmt == MxFormat::FP4_E2M1 ? mx_fold_dt<MxFormat::FP4_E2M1>(t, in, nsrc, (uint32_t)cb, op, avg_div, d, numel, stream)
+                                   : mx_fold_dt<MxFormat::FP8_E4M3>(t, in, nsrc, (uint32_t)cb, op, avg_div, d, numel, stream);
 }
 
 }  // namespace kern

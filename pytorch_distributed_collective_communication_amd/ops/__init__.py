@@ -13,10 +13,11 @@
   whole list of tensors (the staging used by gather/scatter/all_gather with
   tensor lists, reference main.py:35-37,51-52,66-68).
 
-* :func:`mx_quantize`, :func:`mx_reduce`, :func:`mx_dequantize` -- the block-scaled FP8 wire format
-  ``mxfp8_e4m3`` (docs/collectives.md "Compressed all-reduce"): 32-element blocks, one E8M0 scale
-  byte and 32 ``float8_e4m3fn`` bytes each. ``parallel/compressed.py`` builds
-  ``all_reduce_compressed`` from them.
+* :func:`mx_quantize`, :func:`mx_reduce`, :func:`mx_dequantize` -- the block-scaled wire formats
+  ``mxfp8_e4m3`` (docs/collectives.md "Compressed all-reduce": 32-element blocks, one E8M0 scale
+  byte and 32 ``float8_e4m3fn`` bytes each) and ``mxfp4_e2m1`` ("The ``mxfp4_e2m1`` wire format":
+  16 bytes of two e2m1 nibbles instead), picked by the trailing keyword ``wire``.
+  ``parallel/compressed.py`` builds ``all_reduce_compressed`` from them.
 * :func:`mx_quantize_shards`, :func:`mx_dequantize_shards`, :func:`mx_fold` -- the same wire with one
   chunk per shard (docs/collectives.md "Compressed reduce-scatter and all-gather") and the fold of
   chunk wires straight into a tensor; ``reduce_scatter_compressed`` / ``all_gather_compressed``.
@@ -135,36 +136,49 @@ def unpack(flat: torch.Tensor, tensors: Sequence[torch.Tensor]) -> None:
     multi_copy(srcs, [_byte_view(t) for t in tensors])
 
 
-# ------------------------------------------------------------------ block-scaled FP8 wire (mxfp8_e4m3)
+# ------------------------------------------------------- block-scaled wires (mxfp8_e4m3, mxfp4_e2m1)
+# Every function below takes the format as the trailing keyword ``wire``. Where the first argument is the
+# wire tensor itself it is positional-only (``w``), so the keyword is free for the format's name.
 MX_BLOCK = 32
 MX_DTYPES = (torch.float32, torch.bfloat16, torch.float16)
+MX_WIRES = ("mxfp8_e4m3", "mxfp4_e2m1")
+_MX_PAYLOAD = {"mxfp8_e4m3": 32, "mxfp4_e2m1": 16}  # payload bytes per block; one scale byte follows
 
 
-def mx_chunk_blocks(numel: int, world: int = 1) -> int:
+def _mx_payload(wire, who: str) -> int:
+    """Payload bytes per block of a wire format; ValueError for a name that is not one."""
+    if not isinstance(wire, str) or wire not in _MX_PAYLOAD:
+        raise ValueError(f"{who}: unknown wire format {wire!r} (supported: {', '.join(MX_WIRES)})")
+    return _MX_PAYLOAD[wire]
+
+
+def mx_chunk_blocks(numel: int, world: int = 1, *, wire: str = "mxfp8_e4m3") -> int:
     """Blocks per chunk when ``numel`` elements are dealt to ``world`` chunks (csrc/kernels/mx_layout.h):
-    a multiple of 16, and of 4096 once a chunk's wire reaches 1 MiB."""
+    a multiple of 16, and of 4096 once a chunk's wire (33 or 17 bytes per block) reaches 1 MiB."""
+    bw = _mx_payload(wire, "mx_chunk_blocks") + 1
     world = max(1, int(world))
     blocks = (int(numel) + MX_BLOCK - 1) // MX_BLOCK
     cb = max(16, ((blocks + world - 1) // world + 15) // 16 * 16)
-    if 33 * cb >= 1 << 20:
+    if bw * cb >= 1 << 20:
         cb = (cb + 4095) // 4096 * 4096
     return cb
 
 
-def mx_wire_bytes(numel: int, world: int = 1) -> int:
-    """Bytes of the wire of ``numel`` elements in ``world`` chunks: ``world`` x (32 cb payload + cb scales)."""
-    return 33 * mx_chunk_blocks(numel, world) * max(1, int(world))
+def mx_wire_bytes(numel: int, world: int = 1, *, wire: str = "mxfp8_e4m3") -> int:
+    """Bytes of the wire of ``numel`` elements in ``world`` chunks: ``world`` x (32 cb payload + cb scales);
+    16 cb payload bytes for ``mxfp4_e2m1``."""
+    return (_mx_payload(wire, "mx_wire_bytes") + 1) * mx_chunk_blocks(numel, world, wire=wire) * max(1, int(world))
 
 
-def mx_shard_blocks(m: int) -> int:
+def mx_shard_blocks(m: int, *, wire: str = "mxfp8_e4m3") -> int:
     """Blocks per chunk of a shard wire of ``m``-element shards: ``mx_chunk_blocks(m, 1)``. Chunk ``r`` of
     such a wire holds shard ``r`` alone, its blocks counted from the shard's first element."""
-    return mx_chunk_blocks(m, 1)
+    return mx_chunk_blocks(m, 1, wire=wire)
 
 
-def mx_shard_wire_bytes(m: int, world: int = 1) -> int:
+def mx_shard_wire_bytes(m: int, world: int = 1, *, wire: str = "mxfp8_e4m3") -> int:
     """Bytes of the shard wire of ``world`` shards of ``m`` elements."""
-    return 33 * mx_shard_blocks(m) * max(1, int(world))
+    return (_mx_payload(wire, "mx_shard_wire_bytes") + 1) * mx_shard_blocks(m, wire=wire) * max(1, int(world))
 
 
 def _mx_check_dtype(dt, who):
@@ -172,33 +186,39 @@ def _mx_check_dtype(dt, who):
         raise TypeError(f"{who}: float32, bfloat16 or float16 tensors only, got {dt}")
 
 
-def mx_quantize(x: torch.Tensor, world: int = 1, out: torch.Tensor | None = None) -> torch.Tensor:
-    """``x`` (GPU; f32 / bf16 / f16) -> its ``mxfp8_e4m3`` wire: a uint8 tensor of ``world`` chunks of
-    ``[32 cb payload bytes][cb scale bytes]``, padding blocks included (scale 127, payload 0)."""
+def mx_quantize(x: torch.Tensor, world: int = 1, out: torch.Tensor | None = None, *,
+                wire: str = "mxfp8_e4m3") -> torch.Tensor:
+    """``x`` (GPU; f32 / bf16 / f16) -> its wire in the format ``wire``: a uint8 tensor of ``world`` chunks
+    of ``[32 cb payload bytes][cb scale bytes]`` (``mxfp4_e2m1``: 16 cb payload bytes, two elements to a
+    byte), padding blocks included (scale 127, payload 0)."""
     _mx_check_dtype(x.dtype, "mx_quantize")
-    return _C().mx_quantize(x.detach().reshape(-1), int(world), out)
+    _mx_payload(wire, "mx_quantize")
+    return _C().mx_quantize(x.detach().reshape(-1), int(world), out, wire)
 
 
-def mx_reduce(wire: torch.Tensor, nsrc: int, op: str = "sum", out: torch.Tensor | None = None) -> torch.Tensor:
-    """``nsrc`` (1..8) chunk wires back to back -> one chunk wire: every source dequantized, folded in
-    f32 in source order (``avg``: then divided by ``nsrc``), and quantized again."""
+def mx_reduce(w: torch.Tensor, /, nsrc: int, op: str = "sum", out: torch.Tensor | None = None, *,
+              wire: str = "mxfp8_e4m3") -> torch.Tensor:
+    """``nsrc`` (1..8) chunk wires ``w`` back to back -> one chunk wire: every source dequantized, folded
+    in f32 in source order (``avg``: then divided by ``nsrc``), and quantized again."""
     if op not in ("sum", "avg"):
         raise ValueError(f"mx_reduce: op must be 'sum' or 'avg', got {op!r}")
-    return _C().mx_reduce(wire, int(nsrc), op, out)
+    _mx_payload(wire, "mx_reduce")
+    return _C().mx_reduce(w, int(nsrc), op, out, wire)
 
 
-def mx_dequantize(wire: torch.Tensor, numel: int, dtype: torch.dtype = torch.float32, world: int = 1,
-                  out: torch.Tensor | None = None) -> torch.Tensor:
-    """The first ``numel`` elements of a wire of ``world`` chunks, rounded once to ``dtype``; written into
-    ``out`` (``numel`` elements, any shape) when given -- exactly those elements and nothing else."""
+def mx_dequantize(w: torch.Tensor, /, numel: int, dtype: torch.dtype = torch.float32, world: int = 1,
+                  out: torch.Tensor | None = None, *, wire: str = "mxfp8_e4m3") -> torch.Tensor:
+    """The first ``numel`` elements of a wire ``w`` of ``world`` chunks, rounded once to ``dtype``; written
+    into ``out`` (``numel`` elements, any shape) when given -- exactly those elements and nothing else."""
+    _mx_payload(wire, "mx_dequantize")
     if out is None:
         _mx_check_dtype(dtype, "mx_dequantize")
-        out = torch.empty(int(numel), dtype=dtype, device=wire.device)
+        out = torch.empty(int(numel), dtype=dtype, device=w.device)
     else:
         _mx_check_dtype(out.dtype, "mx_dequantize")
         if out.numel() != int(numel):
             raise ValueError(f"mx_dequantize: out has {out.numel()} elements, numel is {numel}")
-    _C().mx_dequantize(wire, int(world), out)
+    _C().mx_dequantize(w, int(world), out, wire)
     return out
 
 
@@ -209,47 +229,52 @@ def _mx_check_shards(numel: int, world: int, who: str) -> int:
     return numel // world
 
 
-def mx_quantize_shards(x: torch.Tensor, world: int, out: torch.Tensor | None = None) -> torch.Tensor:
+def mx_quantize_shards(x: torch.Tensor, world: int, out: torch.Tensor | None = None, *,
+                       wire: str = "mxfp8_e4m3") -> torch.Tensor:
     """``x`` (GPU; ``world`` shards of ``m`` elements) -> its shard wire: chunk ``r`` is the wire of shard
     ``r`` alone (``mx_shard_blocks(m)`` blocks; what lies past the shard's end counts as +0)."""
     _mx_check_dtype(x.dtype, "mx_quantize_shards")
+    _mx_payload(wire, "mx_quantize_shards")
     _mx_check_shards(x.numel(), world, "mx_quantize_shards")
-    return _C().mx_quantize_shards(x.detach().reshape(-1), int(world), out)
+    return _C().mx_quantize_shards(x.detach().reshape(-1), int(world), out, wire)
 
 
-def mx_dequantize_shards(wire: torch.Tensor, shard_numel: int, dtype: torch.dtype = torch.float32, world: int = 1,
-                         out: torch.Tensor | None = None) -> torch.Tensor:
-    """A shard wire of ``world`` chunks -> ``world * shard_numel`` elements: chunk ``r`` fills
+def mx_dequantize_shards(w: torch.Tensor, /, shard_numel: int, dtype: torch.dtype = torch.float32, world: int = 1,
+                         out: torch.Tensor | None = None, *, wire: str = "mxfp8_e4m3") -> torch.Tensor:
+    """A shard wire ``w`` of ``world`` chunks -> ``world * shard_numel`` elements: chunk ``r`` fills
     ``out[r * m:(r + 1) * m]``, rounded once to the dtype; nothing outside ``out`` is written."""
+    _mx_payload(wire, "mx_dequantize_shards")
     n = int(shard_numel) * int(world)
     if out is None:
         _mx_check_dtype(dtype, "mx_dequantize_shards")
-        out = torch.empty(n, dtype=dtype, device=wire.device)
+        out = torch.empty(n, dtype=dtype, device=w.device)
     else:
         _mx_check_dtype(out.dtype, "mx_dequantize_shards")
         if out.numel() != n:
             raise ValueError(f"mx_dequantize_shards: out has {out.numel()} elements, {world} shards of "
                              f"{shard_numel} are {n}")
     _mx_check_shards(n, world, "mx_dequantize_shards")
-    _C().mx_dequantize_shards(wire, int(world), out)
+    _C().mx_dequantize_shards(w, int(world), out, wire)
     return out
 
 
-def mx_fold(wire: torch.Tensor, nsrc: int, numel: int, dtype: torch.dtype = torch.float32, op: str = "sum",
-            out: torch.Tensor | None = None) -> torch.Tensor:
-    """``nsrc`` (1..8) chunk wires of ``mx_shard_blocks(numel)`` blocks back to back -> ``numel`` elements:
-    every source dequantized, folded in f32 in source order (``avg``: then divided by ``nsrc``) and rounded
-    once to the dtype -- :func:`mx_reduce` then :func:`mx_dequantize` without the requantization between."""
+def mx_fold(w: torch.Tensor, /, nsrc: int, numel: int, dtype: torch.dtype = torch.float32, op: str = "sum",
+            out: torch.Tensor | None = None, *, wire: str = "mxfp8_e4m3") -> torch.Tensor:
+    """``nsrc`` (1..8) chunk wires ``w`` of ``mx_shard_blocks(numel)`` blocks back to back -> ``numel``
+    elements: every source dequantized, folded in f32 in source order (``avg``: then divided by ``nsrc``)
+    and rounded once to the dtype -- :func:`mx_reduce` then :func:`mx_dequantize` without the
+    requantization between."""
     if op not in ("sum", "avg"):
         raise ValueError(f"mx_fold: op must be 'sum' or 'avg', got {op!r}")
+    _mx_payload(wire, "mx_fold")
     if out is None:
         _mx_check_dtype(dtype, "mx_fold")
-        out = torch.empty(int(numel), dtype=dtype, device=wire.device)
+        out = torch.empty(int(numel), dtype=dtype, device=w.device)
     else:
         _mx_check_dtype(out.dtype, "mx_fold")
         if out.numel() != int(numel):
             raise ValueError(f"mx_fold: out has {out.numel()} elements, numel is {numel}")
-    _C().mx_fold(wire, int(nsrc), op, out)
+    _C().mx_fold(w, int(nsrc), op, out, wire)
     return out
 
 
@@ -259,7 +284,7 @@ def _mx_exp2(e: torch.Tensor) -> torch.Tensor:
 
 
 def _mx_quantize_blocks(xb: torch.Tensor):
-    """(blocks, 32) f32 -> ((blocks, 32) uint8 payload, (blocks,) uint8 scales), the contract's Q."""
+    """(blocks, 32) f32 -> ((blocks, 32) uint8 payload, (blocks,) uint8 scales), the FP8 contract's Q."""
     amax = xb.abs().amax(dim=1)
     special = ~torch.isfinite(xb).all(dim=1)
     zero = (amax == 0) & ~special
@@ -276,100 +301,151 @@ def _mx_quantize_blocks(xb: torch.Tensor):
     return q, s
 
 
-def _mx_dequantize_blocks(q: torch.Tensor, s: torch.Tensor) -> torch.Tensor:
-    """The contract's D: (blocks, 32) payload bytes and (blocks,) scale bytes -> (blocks, 32) f32."""
+def _mx_scale_values(s: torch.Tensor) -> torch.Tensor:
+    """(blocks,) scale bytes -> f32 2^(s - 127), NaN for 255."""
     si = s.to(torch.int32)
     scale = torch.where(si == 0, torch.full_like(si, 0x00400000), si << 23).view(torch.float32).clone()
     scale[si == 255] = float("nan")
-    return q.view(torch.float8_e4m3fn).to(torch.float32) * scale[:, None]
+    return scale
 
 
-def _mx_split(wire: torch.Tensor, nchunks: int):
-    """Wire of ``nchunks`` chunks -> ((nchunks * cb, 32) payload, (nchunks * cb,) scales)."""
-    if wire.dtype != torch.uint8 or wire.dim() != 1 or wire.numel() % (33 * 16 * nchunks):
-        raise ValueError(f"not a wire of {nchunks} chunks: {wire.dtype}, {tuple(wire.shape)}")
-    cb = wire.numel() // (33 * nchunks)
-    w = wire.view(nchunks, 33 * cb)
-    return w[:, :32 * cb].reshape(nchunks * cb, 32), w[:, 32 * cb:].reshape(nchunks * cb)
+def _mx_dequantize_blocks(q: torch.Tensor, s: torch.Tensor) -> torch.Tensor:
+    """The FP8 contract's D: (blocks, 32) payload bytes and (blocks,) scale bytes -> (blocks, 32) f32."""
+    return q.view(torch.float8_e4m3fn).to(torch.float32) * _mx_scale_values(s)[:, None]
+
+
+_MX4_VALUES = (0.0, 0.5, 1.0, 1.5, 2.0, 3.0, 4.0, 6.0)  # magnitudes of the e2m1 codes 0..7
+
+
+def _mx4_quantize_blocks(xb: torch.Tensor):
+    """(blocks, 32) f32 -> ((blocks, 16) uint8 payload, (blocks,) uint8 scales), the FP4 contract's Q."""
+    amax = xb.abs().amax(dim=1)
+    special = ~torch.isfinite(xb).all(dim=1)
+    zero = (amax == 0) & ~special
+    m, ex = torch.frexp(torch.where(special | zero, torch.ones_like(amax), amax))
+    e = (ex.to(torch.int64) - 1) - 2 + (m > 0.75).to(torch.int64)  # m here is half the contract's m
+    e = e.clamp(-125, 126)
+    e[zero] = 0
+    a = (xb * _mx_exp2(-e)[:, None]).abs()  # exact, or far below 0.25 where the product is subnormal
+    # nearest code, ties to the even one: a midpoint belongs to the even neighbour
+    code = ((a > 0.25).to(torch.uint8) + (a >= 0.75).to(torch.uint8) + (a > 1.25).to(torch.uint8)
+            + (a >= 1.75).to(torch.uint8) + (a > 2.5).to(torch.uint8) + (a >= 3.5).to(torch.uint8)
+            + (a > 5.0).to(torch.uint8))
+    code = code | (torch.signbit(xb).to(torch.uint8) << 3)
+    code[special | zero] = 0
+    q = (code[:, 0::2] | (code[:, 1::2] << 4)).contiguous()
+    s = (e + 127).to(torch.uint8)
+    s[special] = 255
+    return q, s
+
+
+def _mx4_dequantize_blocks(q: torch.Tensor, s: torch.Tensor) -> torch.Tensor:
+    """The FP4 contract's D: (blocks, 16) payload bytes and (blocks,) scale bytes -> (blocks, 32) f32."""
+    code = torch.stack([q & 15, q >> 4], dim=2).reshape(q.shape[0], 32).to(torch.int64)
+    v = torch.tensor(_MX4_VALUES, dtype=torch.float32)[code & 7]
+    v = torch.where((code & 8) != 0, -v, v)
+    return v * _mx_scale_values(s)[:, None]  # 6 2^126 -> inf: one f32 product
+
+
+def _mx_blocks_fns(wire: str, who: str):
+    """(payload bytes per block, Q, D) of a format."""
+    pb = _mx_payload(wire, who)
+    return (pb, _mx_quantize_blocks, _mx_dequantize_blocks) if pb == 32 else (pb, _mx4_quantize_blocks,
+                                                                             _mx4_dequantize_blocks)
+
+
+def _mx_split(w: torch.Tensor, nchunks: int, pb: int = 32):
+    """Wire of ``nchunks`` chunks -> ((nchunks * cb, pb) payload, (nchunks * cb,) scales)."""
+    if w.dtype != torch.uint8 or w.dim() != 1 or w.numel() % ((pb + 1) * 16 * nchunks):
+        raise ValueError(f"not a wire of {nchunks} chunks: {w.dtype}, {tuple(w.shape)}")
+    cb = w.numel() // ((pb + 1) * nchunks)
+    w = w.view(nchunks, (pb + 1) * cb)
+    return w[:, :pb * cb].reshape(nchunks * cb, pb), w[:, pb * cb:].reshape(nchunks * cb)
 
 
 def _mx_join(q: torch.Tensor, s: torch.Tensor, nchunks: int) -> torch.Tensor:
     cb = s.numel() // nchunks
-    return torch.cat([q.reshape(nchunks, 32 * cb), s.reshape(nchunks, cb)], dim=1).reshape(-1).contiguous()
+    return torch.cat([q.reshape(nchunks, q.shape[1] * cb), s.reshape(nchunks, cb)], dim=1).reshape(-1).contiguous()
 
 
-def mx_quantize_reference(x: torch.Tensor, world: int = 1) -> torch.Tensor:
+def mx_quantize_reference(x: torch.Tensor, world: int = 1, *, wire: str = "mxfp8_e4m3") -> torch.Tensor:
     """Plain-PyTorch :func:`mx_quantize` on a CPU tensor, bit for bit the documented contract."""
     _mx_check_dtype(x.dtype, "mx_quantize_reference")
+    _, Q, _ = _mx_blocks_fns(wire, "mx_quantize_reference")
     world = max(1, int(world))
     flat = x.detach().reshape(-1).to(torch.float32)
-    total = mx_chunk_blocks(flat.numel(), world) * world
+    total = mx_chunk_blocks(flat.numel(), world, wire=wire) * world
     xb = torch.zeros(total * MX_BLOCK, dtype=torch.float32)
     xb[:flat.numel()] = flat
-    q, s = _mx_quantize_blocks(xb.view(total, MX_BLOCK))
+    q, s = Q(xb.view(total, MX_BLOCK))
     return _mx_join(q, s, world)
 
 
-def mx_reduce_reference(wire: torch.Tensor, nsrc: int, op: str = "sum") -> torch.Tensor:
+def mx_reduce_reference(w: torch.Tensor, /, nsrc: int, op: str = "sum", *, wire: str = "mxfp8_e4m3") -> torch.Tensor:
     """Plain-PyTorch :func:`mx_reduce` on a CPU wire."""
     if op not in ("sum", "avg"):
         raise ValueError(f"mx_reduce_reference: op must be 'sum' or 'avg', got {op!r}")
-    q, s = _mx_split(wire, nsrc)
+    pb, Q, D = _mx_blocks_fns(wire, "mx_reduce_reference")
+    q, s = _mx_split(w, nsrc, pb)
     cb = s.numel() // nsrc
-    d = _mx_dequantize_blocks(q, s).view(nsrc, cb, MX_BLOCK)
+    d = D(q, s).view(nsrc, cb, MX_BLOCK)
     acc = d[0].clone()
     for r in range(1, nsrc):
         acc = acc + d[r]
     if op == "avg":
         acc = acc / torch.tensor(float(nsrc), dtype=torch.float32)
-    return _mx_join(*_mx_quantize_blocks(acc), 1)
+    return _mx_join(*Q(acc), 1)
 
 
-def mx_dequantize_reference(wire: torch.Tensor, numel: int, dtype: torch.dtype = torch.float32,
-                            world: int = 1) -> torch.Tensor:
+def mx_dequantize_reference(w: torch.Tensor, /, numel: int, dtype: torch.dtype = torch.float32,
+                            world: int = 1, *, wire: str = "mxfp8_e4m3") -> torch.Tensor:
     """Plain-PyTorch :func:`mx_dequantize` on a CPU wire."""
     _mx_check_dtype(dtype, "mx_dequantize_reference")
+    pb, _, D = _mx_blocks_fns(wire, "mx_dequantize_reference")
     world = max(1, int(world))
-    if wire.numel() != mx_wire_bytes(numel, world):
-        raise ValueError(f"the wire of {numel} elements in {world} chunks has {mx_wire_bytes(numel, world)} bytes, "
-                         f"got {wire.numel()}")
-    q, s = _mx_split(wire, world)
-    return _mx_dequantize_blocks(q, s).reshape(-1)[:int(numel)].to(dtype)
+    if w.numel() != mx_wire_bytes(numel, world, wire=wire):
+        raise ValueError(f"the wire of {numel} elements in {world} chunks has "
+                         f"{mx_wire_bytes(numel, world, wire=wire)} bytes, got {w.numel()}")
+    q, s = _mx_split(w, world, pb)
+    return D(q, s).reshape(-1)[:int(numel)].to(dtype)
 
 
-def mx_quantize_shards_reference(x: torch.Tensor, world: int) -> torch.Tensor:
+def mx_quantize_shards_reference(x: torch.Tensor, world: int, *, wire: str = "mxfp8_e4m3") -> torch.Tensor:
     """Plain-PyTorch :func:`mx_quantize_shards` on a CPU tensor."""
     _mx_check_dtype(x.dtype, "mx_quantize_shards_reference")
+    _mx_payload(wire, "mx_quantize_shards_reference")
     m = _mx_check_shards(x.numel(), world, "mx_quantize_shards_reference")
     flat = x.detach().reshape(-1)
-    return torch.cat([mx_quantize_reference(flat[r * m:(r + 1) * m], 1) for r in range(int(world))])
+    return torch.cat([mx_quantize_reference(flat[r * m:(r + 1) * m], 1, wire=wire) for r in range(int(world))])
 
 
-def mx_dequantize_shards_reference(wire: torch.Tensor, shard_numel: int, dtype: torch.dtype = torch.float32,
-                                   world: int = 1) -> torch.Tensor:
+def mx_dequantize_shards_reference(w: torch.Tensor, /, shard_numel: int, dtype: torch.dtype = torch.float32,
+                                   world: int = 1, *, wire: str = "mxfp8_e4m3") -> torch.Tensor:
     """Plain-PyTorch :func:`mx_dequantize_shards` on a CPU wire."""
     _mx_check_dtype(dtype, "mx_dequantize_shards_reference")
+    pb, _, D = _mx_blocks_fns(wire, "mx_dequantize_shards_reference")
     m, world = int(shard_numel), int(world)
     _mx_check_shards(m * world, world, "mx_dequantize_shards_reference")
-    if wire.numel() != mx_shard_wire_bytes(m, world):
-        raise ValueError(f"the wire of {world} shards of {m} elements has {mx_shard_wire_bytes(m, world)} bytes, "
-                         f"got {wire.numel()}")
-    q, s = _mx_split(wire, world)
-    return _mx_dequantize_blocks(q, s).view(world, -1)[:, :m].reshape(-1).to(dtype)
+    if w.numel() != mx_shard_wire_bytes(m, world, wire=wire):
+        raise ValueError(f"the wire of {world} shards of {m} elements has "
+                         f"{mx_shard_wire_bytes(m, world, wire=wire)} bytes, got {w.numel()}")
+    q, s = _mx_split(w, world, pb)
+    return D(q, s).view(world, -1)[:, :m].reshape(-1).to(dtype)
 
 
-def mx_fold_reference(wire: torch.Tensor, nsrc: int, numel: int, dtype: torch.dtype = torch.float32,
-                      op: str = "sum") -> torch.Tensor:
+def mx_fold_reference(w: torch.Tensor, /, nsrc: int, numel: int, dtype: torch.dtype = torch.float32,
+                      op: str = "sum", *, wire: str = "mxfp8_e4m3") -> torch.Tensor:
     """Plain-PyTorch :func:`mx_fold` on a CPU wire."""
     if op not in ("sum", "avg"):
         raise ValueError(f"mx_fold_reference: op must be 'sum' or 'avg', got {op!r}")
     _mx_check_dtype(dtype, "mx_fold_reference")
+    pb, _, D = _mx_blocks_fns(wire, "mx_fold_reference")
     nsrc, numel = int(nsrc), int(numel)
-    if numel < 1 or wire.numel() != mx_shard_wire_bytes(numel, nsrc):
-        raise ValueError(f"{nsrc} chunk wires of {numel} elements have {mx_shard_wire_bytes(numel, nsrc)} bytes, "
-                         f"got {wire.numel()}")
-    q, s = _mx_split(wire, nsrc)
-    d = _mx_dequantize_blocks(q, s).view(nsrc, -1)
+    if numel < 1 or w.numel() != mx_shard_wire_bytes(numel, nsrc, wire=wire):
+        raise ValueError(f"{nsrc} chunk wires of {numel} elements have "
+                         f"{mx_shard_wire_bytes(numel, nsrc, wire=wire)} bytes, got {w.numel()}")
+    q, s = _mx_split(w, nsrc, pb)
+    d = D(q, s).view(nsrc, -1)
     acc = d[0].clone()
     for r in range(1, nsrc):
         acc = acc + d[r]
@@ -379,7 +455,7 @@ def mx_fold_reference(wire: torch.Tensor, nsrc: int, numel: int, dtype: torch.dt
 
 
 __all__ = ["reduce_nway", "reduce_nway_reference", "multi_copy", "pack", "unpack",
-           "mx_quantize", "mx_reduce", "mx_dequantize", "mx_chunk_blocks", "mx_wire_bytes",
+           "MX_WIRES", "mx_quantize", "mx_reduce", "mx_dequantize", "mx_chunk_blocks", "mx_wire_bytes",
            "mx_quantize_reference", "mx_reduce_reference", "mx_dequantize_reference",
            "mx_shard_blocks", "mx_shard_wire_bytes", "mx_quantize_shards", "mx_dequantize_shards", "mx_fold",
            "mx_quantize_shards_reference", "mx_dequantize_shards_reference", "mx_fold_reference"]

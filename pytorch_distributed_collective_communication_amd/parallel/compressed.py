@@ -1,10 +1,16 @@
-"""All-reduce, reduce-scatter and all-gather over a block-scaled FP8 wire (``mxfp8_e4m3``).
+"""All-reduce, reduce-scatter and all-gather over a block-scaled wire: ``mxfp8_e4m3`` or ``mxfp4_e2m1``.
 
 The tensor stays f32 / bf16 / f16; what crosses the links is 32-element blocks of
 ``float8_e4m3fn`` with one power-of-two scale byte each, and every sum is taken in f32
 (contract and error bound: docs/collectives.md "Compressed all-reduce"). For a 2-shot all-reduce
 that is ``2 * 33/32 * (W-1)/W * n`` bytes per rank instead of ``8 * (W-1)/W * n`` for f32 -- 3.9x
 fewer (1.94x for bf16).
+
+``wire="mxfp4_e2m1"`` (docs/collectives.md "The ``mxfp4_e2m1`` wire format") sends two e2m1 nibbles
+per byte: a block is 17 bytes instead of 33, 7.5x fewer than f32, 3.76x fewer than bf16 and 1.94x
+fewer than ``mxfp8_e4m3`` -- arithmetic on the layouts, not a measurement -- at an error bound five
+times coarser (``amax / 3`` per quantization). The sequences, the fold order and every rule below are
+the same for both formats; the single-quantization reduce-scatter is the intended use for gradients.
 
 No new cross-GPU protocol: three single-GPU kernels (``ops.mx_quantize`` / ``mx_reduce`` /
 ``mx_dequantize``) around two byte collectives the backend already has,
@@ -32,7 +38,7 @@ import torch.distributed as dist
 
 from .. import ops
 
-WIRES = ("mxfp8_e4m3",)
+WIRES = ("mxfp8_e4m3", "mxfp4_e2m1")
 MAX_GPU_WORLD = 8  # ops.mx_reduce folds up to 8 sources (one xGMI node)
 
 _side_streams = {}
@@ -74,22 +80,24 @@ def _sequence(tensor, opn, group, world, quantize, reduce, dequantize):
     dequantize(wire, n, world)
 
 
-def _run_gpu(tensor, opn, group, world):
-    _sequence(tensor, opn, group, world, ops.mx_quantize, ops.mx_reduce,
-              lambda w, n, W: ops.mx_dequantize(w, n, tensor.dtype, W, out=tensor))
+def _run_gpu(tensor, opn, group, world, wire):
+    _sequence(tensor, opn, group, world, lambda x, W: ops.mx_quantize(x, W, wire=wire),
+              lambda w, W, o: ops.mx_reduce(w, W, o, wire=wire),
+              lambda w, n, W: ops.mx_dequantize(w, n, tensor.dtype, W, out=tensor, wire=wire))
 
 
-def _run_cpu(tensor, opn, group, world):
+def _run_cpu(tensor, opn, group, world, wire):
     def store(w, n, W):
-        tensor.copy_(ops.mx_dequantize_reference(w, n, tensor.dtype, W).view_as(tensor))
+        tensor.copy_(ops.mx_dequantize_reference(w, n, tensor.dtype, W, wire=wire).view_as(tensor))
 
-    _sequence(tensor, opn, group, world, ops.mx_quantize_reference, ops.mx_reduce_reference, store)
+    _sequence(tensor, opn, group, world, lambda x, W: ops.mx_quantize_reference(x, W, wire=wire),
+              lambda w, W, o: ops.mx_reduce_reference(w, W, o, wire=wire), store)
 
 
 def all_reduce_compressed(tensor: torch.Tensor, op=dist.ReduceOp.SUM, group=None, wire: str = "mxfp8_e4m3",
                           async_op: bool = False):
-    """In-place SUM / AVG all-reduce of ``tensor`` (float32, bfloat16 or float16) over the
-    ``mxfp8_e4m3`` wire. Every rank ends with the same bits; at world 1 the tensor is left
+    """In-place SUM / AVG all-reduce of ``tensor`` (float32, bfloat16 or float16) over the wire
+    format ``wire`` (``mxfp8_e4m3`` or ``mxfp4_e2m1``). Every rank ends with the same bits; at world 1 the tensor is left
     unchanged (not even quantized). GPU tensors run on the current stream; with ``async_op=True``
     on a side stream that first waits for the current one, and the returned handle's ``wait()``
     makes the current stream wait for it. CPU tensors run synchronously (the handle is complete).
@@ -107,11 +115,11 @@ def all_reduce_compressed(tensor: torch.Tensor, op=dist.ReduceOp.SUM, group=None
         return CompressedWork() if async_op else None
     if not tensor.is_cuda:
         with torch.no_grad():
-            _run_cpu(tensor, opn, group, world)
+            _run_cpu(tensor, opn, group, world, wire)
         return CompressedWork() if async_op else None
     if world > MAX_GPU_WORLD:
         raise ValueError(f"all_reduce_compressed: GPU groups of up to {MAX_GPU_WORLD} ranks, got {world}")
-    return _issue_gpu(lambda: _run_gpu(tensor, opn, group, world), (tensor,), async_op)
+    return _issue_gpu(lambda: _run_gpu(tensor, opn, group, world, wire), (tensor,), async_op)
 
 
 def _issue_gpu(run, tensors, async_op):
@@ -174,7 +182,7 @@ def _done(async_op):
 def reduce_scatter_compressed(output: torch.Tensor, input: torch.Tensor, op=dist.ReduceOp.SUM, group=None,
                               wire: str = "mxfp8_e4m3", async_op: bool = False):
     """SUM / AVG reduce-scatter of ``input`` (``W * m`` elements; f32, bf16 or f16) into ``output`` (``m``
-    elements) over the ``mxfp8_e4m3`` wire: rank ``k`` ends with the f32 fold, in rank order, of every
+    elements) over the wire format ``wire``: rank ``k`` ends with the f32 fold, in rank order, of every
     rank's quantized shard ``k`` (its own included), rounded once to the dtype. The fold is not
     quantized again. At world 1 ``input`` is copied bit for bit. Streams and ``async_op`` as in
     :func:`all_reduce_compressed`."""
@@ -192,17 +200,17 @@ def reduce_scatter_compressed(output: torch.Tensor, input: torch.Tensor, op=dist
         return _done(async_op)
     if not input.is_cuda:
         with torch.no_grad():
-            w = ops.mx_quantize_shards_reference(input, world)
+            w = ops.mx_quantize_shards_reference(input, world, wire=wire)
             recv = torch.empty_like(w)
             dist.all_to_all_single(recv, w, group=group)
-            output.copy_(ops.mx_fold_reference(recv, world, m, output.dtype, opn).view_as(output))
+            output.copy_(ops.mx_fold_reference(recv, world, m, output.dtype, opn, wire=wire).view_as(output))
         return _done(async_op)
 
     def run():
-        w = ops.mx_quantize_shards(input, world)
+        w = ops.mx_quantize_shards(input, world, wire=wire)
         recv = torch.empty_like(w)
         dist.all_to_all_single(recv, w, group=group)  # chunk r of every rank -> rank r, in rank order
-        ops.mx_fold(recv, world, m, output.dtype, opn, out=output)
+        ops.mx_fold(recv, world, m, output.dtype, opn, out=output, wire=wire)
 
     return _issue_gpu(run, (output, input), async_op)
 
@@ -210,7 +218,7 @@ def reduce_scatter_compressed(output: torch.Tensor, input: torch.Tensor, op=dist
 def all_gather_compressed(output: torch.Tensor, input: torch.Tensor, group=None, wire: str = "mxfp8_e4m3",
                           async_op: bool = False):
     """All-gather of ``input`` (``m`` elements; f32, bf16 or f16) into ``output`` (``W * m`` elements)
-    over the ``mxfp8_e4m3`` wire: every rank ends with the same bits, the dequantized wire of every
+    over the wire format ``wire``: every rank ends with the same bits, the dequantized wire of every
     rank's shard -- its own slot included. At world 1 ``input`` is copied bit for bit. Streams and
     ``async_op`` as in :func:`all_reduce_compressed`."""
     who = "all_gather_compressed"
@@ -224,16 +232,16 @@ def all_gather_compressed(output: torch.Tensor, input: torch.Tensor, group=None,
         return _done(async_op)
     if not input.is_cuda:
         with torch.no_grad():
-            mine = ops.mx_quantize_reference(input, 1)
+            mine = ops.mx_quantize_reference(input, 1, wire=wire)
             every = torch.empty(mine.numel() * world, dtype=torch.uint8)
             dist.all_gather_into_tensor(every, mine, group=group)
-            output.copy_(ops.mx_dequantize_shards_reference(every, m, output.dtype, world).view_as(output))
+            output.copy_(ops.mx_dequantize_shards_reference(every, m, output.dtype, world, wire=wire).view_as(output))
         return _done(async_op)
 
     def run():
-        mine = ops.mx_quantize(input, 1)
+        mine = ops.mx_quantize(input, 1, wire=wire)
         every = torch.empty(mine.numel() * world, dtype=torch.uint8, device=mine.device)
         dist.all_gather_into_tensor(every, mine, group=group)
-        ops.mx_dequantize_shards(every, m, output.dtype, world, out=output)
+        ops.mx_dequantize_shards(every, m, output.dtype, world, out=output, wire=wire)
 
     return _issue_gpu(run, (output, input), async_op)

@@ -24,9 +24,10 @@ contract, MI355X-first:
   reduction of the accumulated gradients. A second backward before
   :meth:`finish` (outside ``no_sync``) raises instead of silently dropping a
   micro-batch;
-* ``wire="mxfp8_e4m3"``: every bucket goes through ``all_reduce_compressed`` (block-scaled FP8 on
-  the links, f32 sums, AVG; parallel/compressed.py) instead of ``dist.all_reduce``. The default
-  ``wire=None`` is the exact path above.
+* ``wire="mxfp8_e4m3"`` or ``wire="mxfp4_e2m1"``: every bucket goes through
+  ``all_reduce_compressed`` (block-scaled FP8 or FP4 on the links, f32 sums, AVG;
+  parallel/compressed.py) instead of ``dist.all_reduce``. The default ``wire=None`` is the exact
+  path above.
 
 ``broadcast_parameters`` and ``scatter_batch`` cover the other two uses.
 torch's own ``DistributedDataParallel`` also runs unchanged on this backend.

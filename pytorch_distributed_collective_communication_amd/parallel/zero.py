@@ -36,7 +36,9 @@ Compressed links: ``grad_wire="mxfp8_e4m3"`` sends every gradient bucket through
 ``reduce_scatter_compressed`` (AVG, divided inside the fold) and
 ``param_wire="mxfp8_e4m3"`` every parameter bucket through
 ``all_gather_compressed`` (parallel/compressed.py; 3.9x / 1.94x fewer bytes on
-the links for f32 / bf16). Master weights and optimizer state stay exact f32:
+the links for f32 / bf16). Either may be ``"mxfp4_e2m1"`` instead (7.5x / 3.76x
+fewer bytes, an error bound five times coarser), independently of the other:
+FP4 gradients with FP8 parameters is the ZeRO++ setting. Master weights and optimizer state stay exact f32:
 only the replicated copy used for forward and backward is the dequantized
 wire, the same bits on every rank. Spaces of other dtypes keep the uncompressed
 calls; the defaults (``None``) are the uncompressed path, call for call.
@@ -160,7 +162,7 @@ class ShardedOptimizer:
     bf16 parameters the optimizer math runs in fp32 and only the gathered
     parameters are bf16. ``overlap=False`` defers every reduce-scatter to
     :meth:`step`. ``grad_wire`` / ``param_wire`` (default ``None``: uncompressed;
-    ``"mxfp8_e4m3"``) pick the wire of the reduce-scatters / the all-gathers of
+    ``"mxfp8_e4m3"`` or ``"mxfp4_e2m1"``, each on its own) pick the wire of the reduce-scatters / the all-gathers of
     float32, bfloat16 and float16 parameters. One parameter group: the inner optimizer's hyper-parameters
     come from ``**opt_kwargs``.
     """
