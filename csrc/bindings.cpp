@@ -111,6 +111,17 @@ pdcc::kern::DType mx_dtype(const at::Tensor& t, const char* who) {
 void mx_check_wire(const at::Tensor& w, const char* who) {
   TORCH_CHECK(w.is_cuda() && w.scalar_type() == at::kByte && w.dim() == 1, who, ": the wire is a 1-d uint8 GPU tensor");
 }
+// An error-feedback residual (docs/collectives.md "Error feedback") is updated in place, so it cannot
+// go through a copy: float32, `numel` elements, contiguous, 16-byte aligned, on the data's GPU.
+float* mx_residual(const c10::optional<at::Tensor>& r, int64_t numel, const at::Device& dev, const char* who) {
+  if (!r) return nullptr;
+  TORCH_CHECK_TYPE(r->scalar_type() == at::kFloat, who, ": the residual must be float32, got ", r->scalar_type());
+  TORCH_CHECK_VALUE(r->numel() == numel, who, ": the residual has ", r->numel(), " elements, ", numel, " expected");
+  TORCH_CHECK_VALUE(r->device() == dev, who, ": the residual is on ", r->device(), ", the data on ", dev);
+  TORCH_CHECK_VALUE(r->is_contiguous(), who, ": the residual must be contiguous");
+  TORCH_CHECK_VALUE(al16(r->data_ptr()), who, ": the residual must be 16-byte aligned");
+  return r->data_ptr<float>();
+}
 using pdcc::kern::MxFormat;
 MxFormat mx_format(const std::string& wire, const char* who) {
   if (wire == "mxfp8_e4m3") return MxFormat::FP8_E4M3;
@@ -119,7 +130,8 @@ MxFormat mx_format(const std::string& wire, const char* who) {
   return MxFormat::FP8_E4M3;
 }
 
-at::Tensor mx_quantize(const at::Tensor& x, int world, const c10::optional<at::Tensor>& out, const std::string& fmt) {
+at::Tensor mx_quantize(const at::Tensor& x, int world, const c10::optional<at::Tensor>& out, const std::string& fmt,
+                       const c10::optional<at::Tensor>& residual) {
   const MxFormat f = mx_format(fmt, "mx_quantize");
   TORCH_CHECK(x.is_cuda(), "mx_quantize: GPU tensors only");
   TORCH_CHECK(world >= 1, "mx_quantize: world must be >= 1");
@@ -127,6 +139,7 @@ at::Tensor mx_quantize(const at::Tensor& x, int world, const c10::optional<at::T
   const size_t numel = (size_t)x.numel();
   const size_t cb = pdcc::kern::mx_chunk_blocks(f, numel, world);
   const int64_t bytes = (int64_t)pdcc::kern::mx_wire_bytes(f, cb, (size_t)world);
+  float* res = mx_residual(residual, x.numel(), x.device(), "mx_quantize");
   c10::hip::HIPGuardMasqueradingAsCUDA g(x.device());
   at::Tensor wire = out ? *out : at::empty({bytes}, x.options().dtype(at::kByte));
   mx_check_wire(wire, "mx_quantize");
@@ -134,14 +147,15 @@ at::Tensor mx_quantize(const at::Tensor& x, int world, const c10::optional<at::T
               x.device());
   at::Tensor src = mx_in(x), w = mx_out(wire);
   hipStream_t s = c10::hip::getCurrentHIPStreamMasqueradingAsCUDA(x.device().index()).stream();
-  hipError_t e = pdcc::kern::mx_quantize(src.data_ptr(), numel, d, w.data_ptr(), cb, (size_t)world, s, f);
+  hipError_t e = res ? pdcc::kern::mx_quantize_ef(src.data_ptr(), numel, d, res, w.data_ptr(), cb, (size_t)world, s, f)
+                     : pdcc::kern::mx_quantize(src.data_ptr(), numel, d, w.data_ptr(), cb, (size_t)world, s, f);
   TORCH_CHECK(e == hipSuccess, "mx_quantize launch failed: ", hipGetErrorString(e));
   if (!w.is_same(wire)) wire.copy_(w);
   return wire;
 }
 
 at::Tensor mx_reduce(const at::Tensor& wire, int nsrc, const std::string& op, const c10::optional<at::Tensor>& out,
-                     const std::string& fmt) {
+                     const std::string& fmt, const c10::optional<at::Tensor>& residual) {
   const MxFormat f = mx_format(fmt, "mx_reduce");
   mx_check_wire(wire, "mx_reduce");
   TORCH_CHECK(nsrc >= 1 && nsrc <= pdcc::kern::kMaxRanks, "mx_reduce: 1..8 sources");
@@ -151,13 +165,15 @@ at::Tensor mx_reduce(const at::Tensor& wire, int nsrc, const std::string& op, co
   TORCH_CHECK(chunk > 0 && chunk * nsrc == wire.numel() && chunk % (bw * 16) == 0, "mx_reduce: ", wire.numel(),
               " bytes are not ", nsrc, " chunk wires (", bw, " bytes per block, blocks in groups of 16)");
   const size_t cb = (size_t)(chunk / bw);
+  float* r = mx_residual(residual, (int64_t)cb * pdcc::kern::kMxBlock, wire.device(), "mx_reduce");
   c10::hip::HIPGuardMasqueradingAsCUDA g(wire.device());
   at::Tensor res = out ? *out : at::empty({chunk}, wire.options());
   mx_check_wire(res, "mx_reduce");
   TORCH_CHECK(res.device() == wire.device() && res.numel() == chunk, "mx_reduce: out must hold ", chunk, " bytes");
   at::Tensor in = mx_in(wire), o = mx_out(res);
   hipStream_t s = c10::hip::getCurrentHIPStreamMasqueradingAsCUDA(wire.device().index()).stream();
-  hipError_t e = pdcc::kern::mx_reduce(in.data_ptr(), nsrc, cb, kop(op), nsrc, o.data_ptr(), s, f);
+  hipError_t e = r ? pdcc::kern::mx_reduce_ef(in.data_ptr(), nsrc, cb, kop(op), nsrc, r, o.data_ptr(), s, f)
+                   : pdcc::kern::mx_reduce(in.data_ptr(), nsrc, cb, kop(op), nsrc, o.data_ptr(), s, f);
   TORCH_CHECK(e == hipSuccess, "mx_reduce launch failed: ", hipGetErrorString(e));
   if (!o.is_same(res)) res.copy_(o);
   return res;
@@ -184,7 +200,7 @@ void mx_dequantize(const at::Tensor& wire, int world, at::Tensor& out, const std
 
 // ---- the shard layout (kernels/mx_layout.h): chunk r is shard r of `numel / world` elements
 at::Tensor mx_quantize_shards(const at::Tensor& x, int world, const c10::optional<at::Tensor>& out,
-                              const std::string& fmt) {
+                              const std::string& fmt, const c10::optional<at::Tensor>& residual) {
   const MxFormat f = mx_format(fmt, "mx_quantize_shards");
   TORCH_CHECK(x.is_cuda(), "mx_quantize_shards: GPU tensors only");
   TORCH_CHECK(world >= 1 && world <= 65535, "mx_quantize_shards: world must be 1..65535");
@@ -194,6 +210,7 @@ at::Tensor mx_quantize_shards(const at::Tensor& x, int world, const c10::optiona
   const size_t m = (size_t)x.numel() / (size_t)world;
   const size_t cb = pdcc::kern::mx_shard_blocks(f, m);
   const int64_t bytes = (int64_t)pdcc::kern::mx_shard_wire_bytes(f, m, (size_t)world);
+  float* res = mx_residual(residual, x.numel(), x.device(), "mx_quantize_shards");
   c10::hip::HIPGuardMasqueradingAsCUDA g(x.device());
   at::Tensor wire = out ? *out : at::empty({bytes}, x.options().dtype(at::kByte));
   mx_check_wire(wire, "mx_quantize_shards");
@@ -201,7 +218,8 @@ at::Tensor mx_quantize_shards(const at::Tensor& x, int world, const c10::optiona
               " bytes on ", x.device());
   at::Tensor src = mx_in(x), w = mx_out(wire);
   hipStream_t s = c10::hip::getCurrentHIPStreamMasqueradingAsCUDA(x.device().index()).stream();
-  hipError_t e = pdcc::kern::mx_quantize_shards(src.data_ptr(), m, d, w.data_ptr(), cb, (size_t)world, s, f);
+  hipError_t e = res ? pdcc::kern::mx_quantize_shards_ef(src.data_ptr(), m, d, res, w.data_ptr(), cb, (size_t)world, s, f)
+                     : pdcc::kern::mx_quantize_shards(src.data_ptr(), m, d, w.data_ptr(), cb, (size_t)world, s, f);
   TORCH_CHECK(e == hipSuccess, "mx_quantize_shards launch failed: ", hipGetErrorString(e));
   if (!w.is_same(wire)) wire.copy_(w);
   return wire;
@@ -404,16 +422,19 @@ PYBIND11_MODULE(_C, m) {
         py::arg("ntl") = -1,
         "K2: one-launch multi-tensor copy (max_blocks/depth 0 = defaults)");
   m.def("mx_quantize", &mx_quantize, py::arg("x"), py::arg("world") = 1, py::arg("out") = py::none(),
-        py::arg("fmt") = "mxfp8_e4m3",
-        "tensor (f32 / bf16 / f16) -> mxfp8_e4m3 / mxfp4_e2m1 wire of `world` chunks, on the current stream");
+        py::arg("fmt") = "mxfp8_e4m3", py::arg("residual") = py::none(),
+        "tensor (f32 / bf16 / f16) -> mxfp8_e4m3 / mxfp4_e2m1 wire of `world` chunks, on the current stream; "
+        "`residual`: one float per element of error feedback, added before and updated in place");
   m.def("mx_reduce", &mx_reduce, py::arg("wire"), py::arg("nsrc"), py::arg("op") = "sum", py::arg("out") = py::none(),
-        py::arg("fmt") = "mxfp8_e4m3",
-        "nsrc chunk wires back to back -> one chunk wire (dequantize, fold in f32 in source order, requantize)");
+        py::arg("fmt") = "mxfp8_e4m3", py::arg("residual") = py::none(),
+        "nsrc chunk wires back to back -> one chunk wire (dequantize, fold in f32 in source order, requantize); "
+        "`residual`: 32 cb floats of error feedback, updated in place");
   m.def("mx_dequantize", &mx_dequantize, py::arg("wire"), py::arg("world"), py::arg("out"),
         py::arg("fmt") = "mxfp8_e4m3",
         "mxfp8_e4m3 / mxfp4_e2m1 wire of `world` chunks -> out (f32 / bf16 / f16), exactly out.numel() elements");
   m.def("mx_quantize_shards", &mx_quantize_shards, py::arg("x"), py::arg("world"), py::arg("out") = py::none(),
-        py::arg("fmt") = "mxfp8_e4m3", "tensor of `world` shards -> shard wire: chunk r is the wire of shard r alone");
+        py::arg("fmt") = "mxfp8_e4m3", py::arg("residual") = py::none(),
+        "tensor of `world` shards -> shard wire: chunk r is the wire of shard r alone; `residual` as in mx_quantize");
   m.def("mx_dequantize_shards", &mx_dequantize_shards, py::arg("wire"), py::arg("world"), py::arg("out"),
         py::arg("fmt") = "mxfp8_e4m3",
         "shard wire of `world` chunks -> out: chunk r fills out[r m, (r + 1) m), m = out.numel() / world");

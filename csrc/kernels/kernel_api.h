@@ -353,6 +353,18 @@ hipError_t mx_dequantize_shards(const void* wire, size_t cb, size_t nchunks, voi
 // then mx_dequantize compute, without the requantization in between.
 hipError_t mx_fold(const void* wire_in, int nsrc, size_t cb, RedOp op, int avg_div, void* dst, size_t numel, DType t,
                    hipStream_t stream, MxFormat fmt = MxFormat::FP8_E4M3);
+// Error feedback (docs/collectives.md "Error feedback"): the same kernels with an f32 residual,
+// 16-byte aligned and updated in place. Quantize: one float per element of the tensor (`numel`, or
+// nchunks * m for shards); what is quantized is v = f32(x) + residual, and the residual becomes
+// v - D(Q(v)) where that is finite, +0 elsewhere. `src` is not modified; `numel` == 0 touches no residual.
+hipError_t mx_quantize_ef(const void* src, size_t numel, DType t, float* residual, void* wire, size_t cb,
+                          size_t nchunks, hipStream_t stream, MxFormat fmt = MxFormat::FP8_E4M3);
+hipError_t mx_quantize_shards_ef(const void* src, size_t m, DType t, float* residual, void* wire, size_t cb,
+                                 size_t nchunks, hipStream_t stream, MxFormat fmt = MxFormat::FP8_E4M3);
+// Reduce: 32 cb floats, one per element of the chunk, added to the fold (after the AVG division) before
+// it is quantized again and replaced by what that quantization dropped.
+hipError_t mx_reduce_ef(const void* wire_in, int nsrc, size_t cb, RedOp op, int avg_div, float* residual,
+                        void* wire_out, hipStream_t stream, MxFormat fmt = MxFormat::FP8_E4M3);
 
 }  // namespace kern
 }  // namespace pdcc

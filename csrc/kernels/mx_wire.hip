@@ -8,6 +8,10 @@
 //   mx_fold        nsrc chunk wires -> f32 / bf16 / f16 tensor (dequantize, fold in f32, round once)
 //   mx_quantize_shards / mx_dequantize_shards: quantize / dequantize with one chunk per shard of m
 //                  elements (the SHARD instantiations of the same two kernels)
+//   mx_quantize_ef / mx_quantize_shards_ef / mx_reduce_ef: the EF instantiations of quantize and
+//                  reduce, which add an f32 residual before they quantize and leave what the
+//                  quantizer dropped in it (docs/collectives.md "Error feedback"); per f32 element
+//                  quantize then reads 8 and writes 4 + 33/32 bytes instead of reading 4
 //
 // All of them are streaming kernels: a lane moves 16 B on the wide side of its conversion (the tensor
 // for quantize / dequantize / fold, the payload for reduce), the lanes of a block sit next to each other
@@ -169,6 +173,15 @@ template <> struct MxFmt<MxFormat::FP4_E2M1> {
   }
 };
 
+// The new residual of an element: v - d, +0 where that is not finite. d is the product of a payload value
+// and a power of two: exact while it is finite, so a fused multiply-subtract gives the same bits
+// there; where the product overflowed (the top of the f32 range) or is NaN (scale byte 255) the
+// contract's v - d is not finite either, which the test on d itself catches whatever was fused.
+__device__ __forceinline__ float ef_residual(float v, float d) {
+  const float r = v - d;
+  return abs_bits(d) < 0x7f800000u && abs_bits(r) < 0x7f800000u ? r : 0.0f;
+}
+
 // B (2, 4, 8 or 16) wire bytes at p (B-aligned) <-> the low bytes of q[(B + 3) / 4]
 template <int B>
 __device__ __forceinline__ void ld_wire(const char* p, uint32_t* q) {
@@ -200,9 +213,16 @@ __device__ __forceinline__ void st_wire(char* p, const uint32_t* q) {
 // r * 32 cb on, and nothing at or past (r + 1) * m enters it. VEC = false (shards that do not start
 // 16-byte aligned) reads every element on its own. On the wire a lane stores QB = EPL (FP8) or
 // EPL / 2 (FP4) payload bytes.
-template <MxFormat F, DType DT, bool SHARD, bool VEC>
+//
+// EF (error feedback, docs/collectives.md "Error feedback"): what is quantized is v = x + res, and res
+// becomes v - D(Q(v)) where that is finite, +0 where it is not. `res` holds one float per element of
+// the tensor, at the element's own index, so a lane's EPL floats are one or two 16-B vectors that
+// are aligned whenever its 16 B of the tensor are; nothing at or past the chunk's end is read or
+// written. The dequantized values come from the lane's own packed dwords.
+template <MxFormat F, DType DT, bool SHARD, bool VEC, bool EF>
 __global__ __launch_bounds__(256) void k_mx_quantize(const char* __restrict__ src, size_t numel,
-                                                     char* __restrict__ wire, uint32_t cb, size_t m) {
+                                                     char* __restrict__ wire, uint32_t cb, size_t m,
+                                                     float* __restrict__ res) {
   using T = Tr<DT>;
   using S = typename T::S;
   constexpr int EPL = 16 / (int)sizeof(S);
@@ -219,6 +239,7 @@ __global__ __launch_bounds__(256) void k_mx_quantize(const char* __restrict__ sr
   const uint32_t pass = gridDim.x * 256u * kMxUnroll;
   for (uint32_t v0 = blockIdx.x * 256u * kMxUnroll + threadIdx.x; v0 < nvec; v0 += pass) {
     S s[kMxUnroll][EPL];
+    float r[EF ? kMxUnroll : 1][EPL];
 #pragma unroll
     for (int u = 0; u < kMxUnroll; ++u) {
       const uint32_t v = v0 + u * stride;
@@ -226,6 +247,13 @@ __global__ __launch_bounds__(256) void k_mx_quantize(const char* __restrict__ sr
       if (VEC && v < nvec && el + EPL <= end) {
         const uint4 x = *reinterpret_cast<const uint4*>(src + el * sizeof(S));
         __builtin_memcpy(s[u], &x, 16);
+        if constexpr (EF) {
+#pragma unroll
+          for (int j = 0; j < EPL / 4; ++j) {
+            const uint4 y = *reinterpret_cast<const uint4*>(res + el + 4 * j);
+            __builtin_memcpy(&r[u][4 * j], &y, 16);
+          }
+        }
       } else {
         // the last vector, or padding: elements past the end count as +0 and are never read
 #pragma unroll
@@ -234,6 +262,7 @@ __global__ __launch_bounds__(256) void k_mx_quantize(const char* __restrict__ sr
           __builtin_memset(&z, 0, sizeof(S));
           if (v < nvec && el + i < end) z = reinterpret_cast<const S*>(src)[el + i];
           s[u][i] = z;
+          if constexpr (EF) r[u][i] = v < nvec && el + i < end ? res[el + i] : 0.0f;
         }
       }
     }
@@ -246,6 +275,7 @@ __global__ __launch_bounds__(256) void k_mx_quantize(const char* __restrict__ sr
 #pragma unroll
       for (int i = 0; i < EPL; ++i) {
         f[i] = T::in(s[u][i]);
+        if constexpr (EF) f[i] += r[u][i];
         const uint32_t a = abs_bits(f[i]);
         am = a > am ? a : am;
       }
@@ -255,6 +285,25 @@ __global__ __launch_bounds__(256) void k_mx_quantize(const char* __restrict__ sr
       // FP8: payload byte e of the chunk is element e of the chunk; FP4: byte e holds elements 2e, 2e + 1
       st_wire<QB>(w + (size_t)v * QB, q);
       if (v % LPB == 0) w[kern::mx_scale_off(F, cb, v / LPB)] = (char)sc.byte;
+      if constexpr (EF) {
+        float d[EPL];
+        M::template unpack<EPL>(q, mx_scale_value(sc.byte), d);
+#pragma unroll
+        for (int i = 0; i < EPL; ++i) d[i] = ef_residual(f[i], d[i]);
+        const size_t el = el0 + (size_t)v * EPL;
+        if (VEC && el + EPL <= end) {
+#pragma unroll
+          for (int j = 0; j < EPL / 4; ++j) {
+            uint4 y;
+            __builtin_memcpy(&y, &d[4 * j], 16);
+            *reinterpret_cast<uint4*>(res + el + 4 * j) = y;
+          }
+        } else {
+#pragma unroll
+          for (int i = 0; i < EPL; ++i)
+            if (el + i < end) res[el + i] = d[i];
+        }
+      }
     }
   }
 }
@@ -325,9 +374,14 @@ __global__ __launch_bounds__(256) void k_mx_dequantize(const char* __restrict__ 
 // neighbouring lanes and the amax of the folded block is one exchange between them. FP4: 16 payload
 // bytes are a whole block (EPL = 32), so the lane holds its block's amax and there is no exchange;
 // the price is 32 accumulators per lane instead of 16.
-template <MxFormat F, int NSRC, bool AVG>
+//
+// EF: the owner residual (32 cb floats, one per element of the chunk) is added to the fold after the
+// AVG division and before the scale is taken, and becomes acc - D(Q(acc)) (+0 where not finite). A
+// lane's EPL floats are contiguous: they are loaded with the payloads and stored a payload dword's
+// elements at a time, straight from that dword.
+template <MxFormat F, int NSRC, bool AVG, bool EF>
 __global__ __launch_bounds__(256) void k_mx_reduce(const char* __restrict__ in, uint32_t cb, int avg_div,
-                                                   char* __restrict__ out) {
+                                                   char* __restrict__ out, float* __restrict__ res) {
   using M = MxFmt<F>;
   constexpr int EPL = 16 * kern::kMxBlock / M::kPayload;  // 16 or 32
   constexpr int LPB = kern::kMxBlock / EPL;               // 2 or 1
@@ -343,6 +397,11 @@ __global__ __launch_bounds__(256) void k_mx_reduce(const char* __restrict__ in, 
       p[r] = *reinterpret_cast<const uint4*>(c + (size_t)v * 16);
       sb[r] = (uint8_t)c[kern::mx_scale_off(F, cb, v / LPB)];
     }
+    uint4 rr[EF ? EPL / 4 : 1];
+    if constexpr (EF) {
+#pragma unroll
+      for (int j = 0; j < EPL / 4; ++j) rr[j] = *reinterpret_cast<const uint4*>(res + (size_t)v * EPL + 4 * j);
+    }
     float acc[EPL];
 #pragma unroll
     for (int r = 0; r < NSRC; ++r) {
@@ -357,6 +416,15 @@ __global__ __launch_bounds__(256) void k_mx_reduce(const char* __restrict__ in, 
 #pragma unroll
       for (int i = 0; i < EPL; ++i) acc[i] = acc[i] / (float)avg_div;
     }
+    if constexpr (EF) {
+#pragma unroll
+      for (int j = 0; j < EPL / 4; ++j) {
+        acc[4 * j] += __uint_as_float(rr[j].x);
+        acc[4 * j + 1] += __uint_as_float(rr[j].y);
+        acc[4 * j + 2] += __uint_as_float(rr[j].z);
+        acc[4 * j + 3] += __uint_as_float(rr[j].w);
+      }
+    }
     uint32_t am = 0;
 #pragma unroll
     for (int i = 0; i < EPL; ++i) {
@@ -368,6 +436,23 @@ __global__ __launch_bounds__(256) void k_mx_reduce(const char* __restrict__ in, 
     M::template pack<EPL>(acc, sc, q);
     *reinterpret_cast<uint4*>(out + (size_t)v * 16) = make_uint4(q[0], q[1], q[2], q[3]);
     if (v % LPB == 0) out[kern::mx_scale_off(F, cb, v / LPB)] = (char)sc.byte;
+    if constexpr (EF) {
+      constexpr int G = EPL / 4;  // elements of one payload dword: 4 or 8
+      const float scale = mx_scale_value(sc.byte);
+#pragma unroll
+      for (int w = 0; w < 4; ++w) {
+        float d[G];
+        M::template unpack<G>(q + w, scale, d);
+#pragma unroll
+        for (int i = 0; i < G; ++i) d[i] = ef_residual(acc[G * w + i], d[i]);
+#pragma unroll
+        for (int j = 0; j < G / 4; ++j) {
+          uint4 y;
+          __builtin_memcpy(&y, &d[4 * j], 16);
+          *reinterpret_cast<uint4*>(res + (size_t)v * EPL + G * w + 4 * j) = y;
+        }
+      }
+    }
   }
 }
 
@@ -478,12 +563,19 @@ dim3 mx_stream_grid(size_t cb, DType t, size_t nchunks) {
 }
 
 // quantize / dequantize of one format and dtype: the dealt kernel, or the shard one with or without vectors
+template <MxFormat F, DType DT, bool EF>
+void mx_quantize_ef_go(bool shard, bool vec, const dim3& grid, const char* s, size_t numel, char* w, uint32_t cb,
+                       size_t m, float* res, hipStream_t stream) {
+  if (!shard) hipLaunchKernelGGL((dev::k_mx_quantize<F, DT, false, true, EF>), grid, dim3(256), 0, stream, s, numel, w, cb, m, res);
+  else if (vec) hipLaunchKernelGGL((dev::k_mx_quantize<F, DT, true, true, EF>), grid, dim3(256), 0, stream, s, numel, w, cb, m, res);
+  else hipLaunchKernelGGL((dev::k_mx_quantize<F, DT, true, false, EF>), grid, dim3(256), 0, stream, s, numel, w, cb, m, res);
+}
+// (`res` null: the plain kernels; otherwise the error-feedback ones)
 template <MxFormat F, DType DT>
 void mx_quantize_go(bool shard, bool vec, const dim3& grid, const char* s, size_t numel, char* w, uint32_t cb, size_t m,
-                    hipStream_t stream) {
-  if (!shard) hipLaunchKernelGGL((dev::k_mx_quantize<F, DT, false, true>), grid, dim3(256), 0, stream, s, numel, w, cb, m);
-  else if (vec) hipLaunchKernelGGL((dev::k_mx_quantize<F, DT, true, true>), grid, dim3(256), 0, stream, s, numel, w, cb, m);
-  else hipLaunchKernelGGL((dev::k_mx_quantize<F, DT, true, false>), grid, dim3(256), 0, stream, s, numel, w, cb, m);
+                    float* res, hipStream_t stream) {
+  if (res) mx_quantize_ef_go<F, DT, true>(shard, vec, grid, s, numel, w, cb, m, res, stream);
+  else mx_quantize_ef_go<F, DT, false>(shard, vec, grid, s, numel, w, cb, m, res, stream);
 }
 template <MxFormat F, DType DT>
 void mx_dequantize_go(bool shard, bool vec, const dim3& grid, const char* w, uint32_t cb, char* d, size_t numel, size_t m,
@@ -509,12 +601,12 @@ void mx_dequantize_dt(DType t, A... a) {
   }
 }
 hipError_t mx_quantize_any(MxFormat fmt, DType t, bool shard, bool vec, const void* src, size_t numel, void* wire,
-                           size_t cb, size_t nchunks, size_t m, hipStream_t stream) {
+                           size_t cb, size_t nchunks, size_t m, hipStream_t stream, float* res = nullptr) {
   const dim3 grid = mx_stream_grid(cb, t, nchunks);
   const char* s = static_cast<const char*>(src);
   char* w = static_cast<char*>(wire);
-  if (fmt == MxFormat::FP4_E2M1) mx_quantize_dt<MxFormat::FP4_E2M1>(t, shard, vec, grid, s, numel, w, (uint32_t)cb, m, stream);
-  else mx_quantize_dt<MxFormat::FP8_E4M3>(t, shard, vec, grid, s, numel, w, (uint32_t)cb, m, stream);
+  if (fmt == MxFormat::FP4_E2M1) mx_quantize_dt<MxFormat::FP4_E2M1>(t, shard, vec, grid, s, numel, w, (uint32_t)cb, m, res, stream);
+  else mx_quantize_dt<MxFormat::FP8_E4M3>(t, shard, vec, grid, s, numel, w, (uint32_t)cb, m, res, stream);
   return hipGetLastError();
 }
 hipError_t mx_dequantize_any(MxFormat fmt, DType t, bool shard, bool vec, const void* wire, size_t cb, size_t nchunks,
@@ -555,6 +647,25 @@ hipError_t mx_quantize_shards(const void* src, size_t m, DType t, void* wire, si
   return mx_quantize_any(fmt, t, true, vec, src, m * nchunks, wire, cb, nchunks, m, stream);
 }
 
+hipError_t mx_quantize_ef(const void* src, size_t numel, DType t, float* residual, void* wire, size_t cb,
+                          size_t nchunks, hipStream_t stream, MxFormat fmt) {
+  if (!mx_fmt_ok(fmt) || !mx_dtype_ok(t)) return hipErrorInvalidValue;
+  if (!mx_cb_ok(cb) || nchunks == 0 || nchunks > 65535 || !mx_al16(wire) || (numel && !mx_al16(src)))
+    return hipErrorInvalidValue;
+  if (numel > cb * nchunks * kMxBlock || (numel && (!residual || !mx_al16(residual)))) return hipErrorInvalidValue;
+  // (no elements: no residual to update, the wire is all padding blocks)
+  return mx_quantize_any(fmt, t, false, true, src, numel, wire, cb, nchunks, 0, stream, numel ? residual : nullptr);
+}
+
+hipError_t mx_quantize_shards_ef(const void* src, size_t m, DType t, float* residual, void* wire, size_t cb,
+                                 size_t nchunks, hipStream_t stream, MxFormat fmt) {
+  if (!mx_fmt_ok(fmt) || !mx_dtype_ok(t)) return hipErrorInvalidValue;
+  if (!mx_shards_ok(m, cb, nchunks) || !mx_al16(wire) || !mx_al16(src) || !residual || !mx_al16(residual))
+    return hipErrorInvalidValue;
+  const bool vec = m * mx_esize(t) % 16 == 0;  // every shard, and its slice of the residual, starts 16-byte aligned
+  return mx_quantize_any(fmt, t, true, vec, src, m * nchunks, wire, cb, nchunks, m, stream, residual);
+}
+
 hipError_t mx_dequantize_shards(const void* wire, size_t cb, size_t nchunks, void* dst, size_t m, DType t,
                                 hipStream_t stream, MxFormat fmt) {
   if (!mx_fmt_ok(fmt) || !mx_dtype_ok(t)) return hipErrorInvalidValue;
@@ -564,36 +675,51 @@ hipError_t mx_dequantize_shards(const void* wire, size_t cb, size_t nchunks, voi
 }
 
 namespace {
-template <MxFormat F, bool AVG>
-hipError_t mx_reduce_go(const char* in, int nsrc, uint32_t cb, int avg_div, char* out, hipStream_t stream) {
+template <MxFormat F, bool AVG, bool EF>
+hipError_t mx_reduce_go(const char* in, int nsrc, uint32_t cb, int avg_div, char* out, float* res, hipStream_t stream) {
   constexpr int lpb = F == MxFormat::FP4_E2M1 ? 1 : 2;  // lanes per block: 16 payload bytes per lane
   const dim3 grid(dev::mx_grid_x((uint64_t)cb * lpb, 1, 1, dev::kMxGridReduce)), block(256);
   switch (nsrc) {
 #define PDCC_MX_N(N) \
-  case N: hipLaunchKernelGGL((dev::k_mx_reduce<F, N, AVG>), grid, block, 0, stream, in, cb, avg_div, out); break;
+  case N: hipLaunchKernelGGL((dev::k_mx_reduce<F, N, AVG, EF>), grid, block, 0, stream, in, cb, avg_div, out, res); break;
     PDCC_MX_N(1) PDCC_MX_N(2) PDCC_MX_N(3) PDCC_MX_N(4) PDCC_MX_N(5) PDCC_MX_N(6) PDCC_MX_N(7) PDCC_MX_N(8)
 #undef PDCC_MX_N
     default: return hipErrorInvalidValue;
   }
   return hipGetLastError();
 }
+// (`res` null: the plain kernels; otherwise the error-feedback ones)
 template <MxFormat F>
-hipError_t mx_reduce_op(const char* in, int nsrc, uint32_t cb, RedOp op, int avg_div, char* out, hipStream_t stream) {
-  return op == RedOp::AVG ? mx_reduce_go<F, true>(in, nsrc, cb, avg_div, out, stream)
-                          : mx_reduce_go<F, false>(in, nsrc, cb, avg_div, out, stream);
+hipError_t mx_reduce_op(const char* in, int nsrc, uint32_t cb, RedOp op, int avg_div, char* out, float* res,
+                        hipStream_t stream) {
+  if (res)
+    return op == RedOp::AVG ? mx_reduce_go<F, true, true>(in, nsrc, cb, avg_div, out, res, stream)
+                            : mx_reduce_go<F, false, true>(in, nsrc, cb, avg_div, out, res, stream);
+  return op == RedOp::AVG ? mx_reduce_go<F, true, false>(in, nsrc, cb, avg_div, out, res, stream)
+                          : mx_reduce_go<F, false, false>(in, nsrc, cb, avg_div, out, res, stream);
 }
-}  // namespace
-
-hipError_t mx_reduce(const void* wire_in, int nsrc, size_t cb, RedOp op, int avg_div, void* wire_out,
-                     hipStream_t stream, MxFormat fmt) {
+hipError_t mx_reduce_any(const void* wire_in, int nsrc, size_t cb, RedOp op, int avg_div, void* wire_out, float* res,
+                         hipStream_t stream, MxFormat fmt) {
   if (!mx_fmt_ok(fmt) || !mx_cb_ok(cb) || nsrc < 1 || nsrc > kMaxRanks || !mx_al16(wire_in) || !mx_al16(wire_out))
     return hipErrorInvalidValue;
   if (op != RedOp::SUM && op != RedOp::AVG) return hipErrorInvalidValue;
   if (op == RedOp::AVG && avg_div < 1) return hipErrorInvalidValue;
   const char* in = static_cast<const char*>(wire_in);
   char* out = static_cast<char*>(wire_out);
-  return fmt == MxFormat::FP4_E2M1 ? mx_reduce_op<MxFormat::FP4_E2M1>(in, nsrc, (uint32_t)cb, op, avg_div, out, stream)
-                                   : mx_reduce_op<MxFormat::FP8_E4M3>(in, nsrc, (uint32_t)cb, op, avg_div, out, stream);
+  return fmt == MxFormat::FP4_E2M1 ? mx_reduce_op<MxFormat::FP4_E2M1>(in, nsrc, (uint32_t)cb, op, avg_div, out, res, stream)
+                                   : mx_reduce_op<MxFormat::FP8_E4M3>(in, nsrc, (uint32_t)cb, op, avg_div, out, res, stream);
+}
+}  // namespace
+
+hipError_t mx_reduce(const void* wire_in, int nsrc, size_t cb, RedOp op, int avg_div, void* wire_out,
+                     hipStream_t stream, MxFormat fmt) {
+  return mx_reduce_any(wire_in, nsrc, cb, op, avg_div, wire_out, nullptr, stream, fmt);
+}
+
+hipError_t mx_reduce_ef(const void* wire_in, int nsrc, size_t cb, RedOp op, int avg_div, float* residual,
+                        void* wire_out, hipStream_t stream, MxFormat fmt) {
+  if (!residual || !mx_al16(residual)) return hipErrorInvalidValue;
+  return mx_reduce_any(wire_in, nsrc, cb, op, avg_div, wire_out, residual, stream, fmt);
 }
 
 namespace {

@@ -18,6 +18,9 @@
   byte and 32 ``float8_e4m3fn`` bytes each) and ``mxfp4_e2m1`` ("The ``mxfp4_e2m1`` wire format":
   16 bytes of two e2m1 nibbles instead), picked by the trailing keyword ``wire``.
   ``parallel/compressed.py`` builds ``all_reduce_compressed`` from them.
+  :func:`mx_quantize`, :func:`mx_quantize_shards` and :func:`mx_reduce` take ``residual=``: error feedback
+  (docs/collectives.md "Error feedback"), an f32 tensor added before the quantization and left holding
+  what it dropped, fused into the same kernel.
 * :func:`mx_quantize_shards`, :func:`mx_dequantize_shards`, :func:`mx_fold` -- the same wire with one
   chunk per shard (docs/collectives.md "Compressed reduce-scatter and all-gather") and the fold of
   chunk wires straight into a tensor; ``reduce_scatter_compressed`` / ``all_gather_compressed``.
@@ -186,24 +189,62 @@ def _mx_check_dtype(dt, who):
         raise TypeError(f"{who}: float32, bfloat16 or float16 tensors only, got {dt}")
 
 
+def mx_owner_residual_numel(numel: int, world: int = 1, *, wire: str = "mxfp8_e4m3") -> int:
+    """Elements of the owner residual of an all-reduce of ``numel`` elements over ``world`` ranks: one float
+    per element of a rank's chunk, padding blocks included -- ``32 * mx_chunk_blocks(numel, world)``."""
+    return MX_BLOCK * mx_chunk_blocks(numel, world, wire=wire)
+
+
+def _mx_check_residual(residual, numel: int, device, who: str) -> None:
+    """An error-feedback residual (docs/collectives.md "Error feedback") is updated in place, which rules
+    out the copy the other arguments may go through: float32, ``numel`` elements, on ``device``,
+    contiguous and 16-byte aligned."""
+    if residual is None:
+        return
+    if not isinstance(residual, torch.Tensor) or residual.dtype != torch.float32:
+        raise TypeError(f"{who}: the residual must be a float32 tensor, got "
+                        f"{residual.dtype if isinstance(residual, torch.Tensor) else type(residual).__name__}")
+    if residual.numel() != int(numel):
+        raise ValueError(f"{who}: the residual has {residual.numel()} elements, {int(numel)} expected")
+    if residual.device != device:
+        raise ValueError(f"{who}: the residual is on {residual.device}, the data on {device}")
+    if not residual.is_contiguous():
+        raise ValueError(f"{who}: the residual must be contiguous")
+    if residual.data_ptr() % 16:
+        raise ValueError(f"{who}: the residual must be 16-byte aligned")
+
+
 def mx_quantize(x: torch.Tensor, world: int = 1, out: torch.Tensor | None = None, *,
-                wire: str = "mxfp8_e4m3") -> torch.Tensor:
+                wire: str = "mxfp8_e4m3", residual: torch.Tensor | None = None) -> torch.Tensor:
     """``x`` (GPU; f32 / bf16 / f16) -> its wire in the format ``wire``: a uint8 tensor of ``world`` chunks
     of ``[32 cb payload bytes][cb scale bytes]`` (``mxfp4_e2m1``: 16 cb payload bytes, two elements to a
-    byte), padding blocks included (scale 127, payload 0)."""
+    byte), padding blocks included (scale 127, payload 0).
+
+    ``residual`` (float32, one element per element of ``x``; error feedback): what is quantized is
+    ``x.float() + residual``, and the residual becomes what the quantization dropped of that sum (+0
+    where that is not finite), in place and in the same launch. ``x`` is not modified."""
     _mx_check_dtype(x.dtype, "mx_quantize")
     _mx_payload(wire, "mx_quantize")
-    return _C().mx_quantize(x.detach().reshape(-1), int(world), out, wire)
+    if residual is None:
+        return _C().mx_quantize(x.detach().reshape(-1), int(world), out, wire)
+    _mx_check_residual(residual, x.numel(), x.device, "mx_quantize")
+    return _C().mx_quantize(x.detach().reshape(-1), int(world), out, wire, residual.detach())
 
 
 def mx_reduce(w: torch.Tensor, /, nsrc: int, op: str = "sum", out: torch.Tensor | None = None, *,
-              wire: str = "mxfp8_e4m3") -> torch.Tensor:
+              wire: str = "mxfp8_e4m3", residual: torch.Tensor | None = None) -> torch.Tensor:
     """``nsrc`` (1..8) chunk wires ``w`` back to back -> one chunk wire: every source dequantized, folded
-    in f32 in source order (``avg``: then divided by ``nsrc``), and quantized again."""
+    in f32 in source order (``avg``: then divided by ``nsrc``), and quantized again.
+
+    ``residual`` (float32, 32 elements per block of a chunk: the owner residual) is added to the fold
+    before it is quantized again and becomes what that quantization dropped, in place."""
     if op not in ("sum", "avg"):
         raise ValueError(f"mx_reduce: op must be 'sum' or 'avg', got {op!r}")
-    _mx_payload(wire, "mx_reduce")
-    return _C().mx_reduce(w, int(nsrc), op, out, wire)
+    pb = _mx_payload(wire, "mx_reduce")
+    if residual is None:
+        return _C().mx_reduce(w, int(nsrc), op, out, wire)
+    _mx_check_residual(residual, w.numel() // ((pb + 1) * max(1, int(nsrc))) * MX_BLOCK, w.device, "mx_reduce")
+    return _C().mx_reduce(w, int(nsrc), op, out, wire, residual.detach())
 
 
 def mx_dequantize(w: torch.Tensor, /, numel: int, dtype: torch.dtype = torch.float32, world: int = 1,
@@ -230,13 +271,17 @@ def _mx_check_shards(numel: int, world: int, who: str) -> int:
 
 
 def mx_quantize_shards(x: torch.Tensor, world: int, out: torch.Tensor | None = None, *,
-                       wire: str = "mxfp8_e4m3") -> torch.Tensor:
+                       wire: str = "mxfp8_e4m3", residual: torch.Tensor | None = None) -> torch.Tensor:
     """``x`` (GPU; ``world`` shards of ``m`` elements) -> its shard wire: chunk ``r`` is the wire of shard
-    ``r`` alone (``mx_shard_blocks(m)`` blocks; what lies past the shard's end counts as +0)."""
+    ``r`` alone (``mx_shard_blocks(m)`` blocks; what lies past the shard's end counts as +0).
+    ``residual``: as in :func:`mx_quantize`, one float per element of ``x``."""
     _mx_check_dtype(x.dtype, "mx_quantize_shards")
     _mx_payload(wire, "mx_quantize_shards")
     _mx_check_shards(x.numel(), world, "mx_quantize_shards")
-    return _C().mx_quantize_shards(x.detach().reshape(-1), int(world), out, wire)
+    if residual is None:
+        return _C().mx_quantize_shards(x.detach().reshape(-1), int(world), out, wire)
+    _mx_check_residual(residual, x.numel(), x.device, "mx_quantize_shards")
+    return _C().mx_quantize_shards(x.detach().reshape(-1), int(world), out, wire, residual.detach())
 
 
 def mx_dequantize_shards(w: torch.Tensor, /, shard_numel: int, dtype: torch.dtype = torch.float32, world: int = 1,
@@ -368,21 +413,36 @@ def _mx_join(q: torch.Tensor, s: torch.Tensor, nchunks: int) -> torch.Tensor:
     return torch.cat([q.reshape(nchunks, q.shape[1] * cb), s.reshape(nchunks, cb)], dim=1).reshape(-1).contiguous()
 
 
-def mx_quantize_reference(x: torch.Tensor, world: int = 1, *, wire: str = "mxfp8_e4m3") -> torch.Tensor:
-    """Plain-PyTorch :func:`mx_quantize` on a CPU tensor, bit for bit the documented contract."""
+def _mx_feed_back(v: torch.Tensor, d: torch.Tensor, residual: torch.Tensor) -> None:
+    """The contract's residual update: ``residual <- v - d`` where that is finite, +0 elsewhere."""
+    r = v - d
+    residual.detach().view(-1).copy_(torch.where(torch.isfinite(r), r, torch.zeros_like(r)))
+
+
+def mx_quantize_reference(x: torch.Tensor, world: int = 1, *, wire: str = "mxfp8_e4m3",
+                          residual: torch.Tensor | None = None) -> torch.Tensor:
+    """Plain-PyTorch :func:`mx_quantize` on a CPU tensor, bit for bit the documented contract (with
+    ``residual``: the contract of "Error feedback", the residual updated in place)."""
     _mx_check_dtype(x.dtype, "mx_quantize_reference")
-    _, Q, _ = _mx_blocks_fns(wire, "mx_quantize_reference")
+    _, Q, D = _mx_blocks_fns(wire, "mx_quantize_reference")
     world = max(1, int(world))
     flat = x.detach().reshape(-1).to(torch.float32)
-    total = mx_chunk_blocks(flat.numel(), world, wire=wire) * world
+    n = flat.numel()
+    if residual is not None:
+        _mx_check_residual(residual, n, x.device, "mx_quantize_reference")
+        flat = flat + residual.detach().view(-1)
+    total = mx_chunk_blocks(n, world, wire=wire) * world
     xb = torch.zeros(total * MX_BLOCK, dtype=torch.float32)
-    xb[:flat.numel()] = flat
+    xb[:n] = flat
     q, s = Q(xb.view(total, MX_BLOCK))
+    if residual is not None:
+        _mx_feed_back(flat, D(q, s).reshape(-1)[:n], residual)
     return _mx_join(q, s, world)
 
 
-def mx_reduce_reference(w: torch.Tensor, /, nsrc: int, op: str = "sum", *, wire: str = "mxfp8_e4m3") -> torch.Tensor:
-    """Plain-PyTorch :func:`mx_reduce` on a CPU wire."""
+def mx_reduce_reference(w: torch.Tensor, /, nsrc: int, op: str = "sum", *, wire: str = "mxfp8_e4m3",
+                        residual: torch.Tensor | None = None) -> torch.Tensor:
+    """Plain-PyTorch :func:`mx_reduce` on a CPU wire (``residual``: updated in place)."""
     if op not in ("sum", "avg"):
         raise ValueError(f"mx_reduce_reference: op must be 'sum' or 'avg', got {op!r}")
     pb, Q, D = _mx_blocks_fns(wire, "mx_reduce_reference")
@@ -394,7 +454,13 @@ def mx_reduce_reference(w: torch.Tensor, /, nsrc: int, op: str = "sum", *, wire:
         acc = acc + d[r]
     if op == "avg":
         acc = acc / torch.tensor(float(nsrc), dtype=torch.float32)
-    return _mx_join(*Q(acc), 1)
+    if residual is None:
+        return _mx_join(*Q(acc), 1)
+    _mx_check_residual(residual, cb * MX_BLOCK, w.device, "mx_reduce_reference")
+    acc = acc + residual.detach().view(cb, MX_BLOCK)
+    q, s = Q(acc)
+    _mx_feed_back(acc.reshape(-1), D(q, s).reshape(-1), residual)
+    return _mx_join(q, s, 1)
 
 
 def mx_dequantize_reference(w: torch.Tensor, /, numel: int, dtype: torch.dtype = torch.float32,
@@ -410,13 +476,22 @@ def mx_dequantize_reference(w: torch.Tensor, /, numel: int, dtype: torch.dtype =
     return D(q, s).reshape(-1)[:int(numel)].to(dtype)
 
 
-def mx_quantize_shards_reference(x: torch.Tensor, world: int, *, wire: str = "mxfp8_e4m3") -> torch.Tensor:
-    """Plain-PyTorch :func:`mx_quantize_shards` on a CPU tensor."""
+def mx_quantize_shards_reference(x: torch.Tensor, world: int, *, wire: str = "mxfp8_e4m3",
+                                 residual: torch.Tensor | None = None) -> torch.Tensor:
+    """Plain-PyTorch :func:`mx_quantize_shards` on a CPU tensor (``residual``: updated in place)."""
     _mx_check_dtype(x.dtype, "mx_quantize_shards_reference")
     _mx_payload(wire, "mx_quantize_shards_reference")
     m = _mx_check_shards(x.numel(), world, "mx_quantize_shards_reference")
     flat = x.detach().reshape(-1)
-    return torch.cat([mx_quantize_reference(flat[r * m:(r + 1) * m], 1, wire=wire) for r in range(int(world))])
+    if residual is None:
+        return torch.cat([mx_quantize_reference(flat[r * m:(r + 1) * m], 1, wire=wire) for r in range(int(world))])
+    _mx_check_residual(residual, flat.numel(), x.device, "mx_quantize_shards_reference")
+    out = []
+    for r in range(int(world)):  # (a shard's slice of the residual need not be aligned: it goes through a copy)
+        part = residual.detach().view(-1)[r * m:(r + 1) * m].clone()
+        out.append(mx_quantize_reference(flat[r * m:(r + 1) * m], 1, wire=wire, residual=part))
+        residual.detach().view(-1)[r * m:(r + 1) * m] = part
+    return torch.cat(out)
 
 
 def mx_dequantize_shards_reference(w: torch.Tensor, /, shard_numel: int, dtype: torch.dtype = torch.float32,
@@ -456,6 +531,7 @@ def mx_fold_reference(w: torch.Tensor, /, nsrc: int, numel: int, dtype: torch.dt
 
 __all__ = ["reduce_nway", "reduce_nway_reference", "multi_copy", "pack", "unpack",
            "MX_WIRES", "mx_quantize", "mx_reduce", "mx_dequantize", "mx_chunk_blocks", "mx_wire_bytes",
+           "mx_owner_residual_numel",
            "mx_quantize_reference", "mx_reduce_reference", "mx_dequantize_reference",
            "mx_shard_blocks", "mx_shard_wire_bytes", "mx_quantize_shards", "mx_dequantize_shards", "mx_fold",
            "mx_quantize_shards_reference", "mx_dequantize_shards_reference", "mx_fold_reference"]

@@ -80,29 +80,56 @@ def _sequence(tensor, opn, group, world, quantize, reduce, dequantize):
     dequantize(wire, n, world)
 
 
-def _run_gpu(tensor, opn, group, world, wire):
-    _sequence(tensor, opn, group, world, lambda x, W: ops.mx_quantize(x, W, wire=wire),
-              lambda w, W, o: ops.mx_reduce(w, W, o, wire=wire),
+def _run_gpu(tensor, opn, group, world, wire, residual=None, owner_residual=None):
+    _sequence(tensor, opn, group, world, lambda x, W: ops.mx_quantize(x, W, wire=wire, residual=residual),
+              lambda w, W, o: ops.mx_reduce(w, W, o, wire=wire, residual=owner_residual),
               lambda w, n, W: ops.mx_dequantize(w, n, tensor.dtype, W, out=tensor, wire=wire))
 
 
-def _run_cpu(tensor, opn, group, world, wire):
+def _run_cpu(tensor, opn, group, world, wire, residual=None, owner_residual=None):
     def store(w, n, W):
         tensor.copy_(ops.mx_dequantize_reference(w, n, tensor.dtype, W, wire=wire).view_as(tensor))
 
-    _sequence(tensor, opn, group, world, lambda x, W: ops.mx_quantize_reference(x, W, wire=wire),
-              lambda w, W, o: ops.mx_reduce_reference(w, W, o, wire=wire), store)
+    _sequence(tensor, opn, group, world, lambda x, W: ops.mx_quantize_reference(x, W, wire=wire, residual=residual),
+              lambda w, W, o: ops.mx_reduce_reference(w, W, o, wire=wire, residual=owner_residual), store)
+
+
+def _check_residual(who, name, res, numel, device):
+    """An error-feedback residual, checked before any communication: float32, ``numel`` elements, on the
+    tensor's device, contiguous and 16-byte aligned (it is updated in place, so it cannot be copied)."""
+    if res is None:
+        return
+    if not isinstance(res, torch.Tensor) or res.dtype != torch.float32:
+        raise TypeError(f"{who}: {name} must be a float32 tensor, got "
+                        f"{res.dtype if isinstance(res, torch.Tensor) else type(res).__name__}")
+    if res.numel() != numel:
+        raise ValueError(f"{who}: {name} has {res.numel()} elements, {numel} expected")
+    if res.device != device:
+        raise ValueError(f"{who}: {name} is on {res.device}, the tensor on {device}")
+    if not res.is_contiguous():
+        raise ValueError(f"{who}: {name} must be contiguous")
+    if res.data_ptr() % 16:
+        raise ValueError(f"{who}: {name} must be 16-byte aligned")
 
 
 def all_reduce_compressed(tensor: torch.Tensor, op=dist.ReduceOp.SUM, group=None, wire: str = "mxfp8_e4m3",
-                          async_op: bool = False):
+                          async_op: bool = False, *, residual: torch.Tensor | None = None,
+                          owner_residual: torch.Tensor | None = None):
     """In-place SUM / AVG all-reduce of ``tensor`` (float32, bfloat16 or float16) over the wire
     format ``wire`` (``mxfp8_e4m3`` or ``mxfp4_e2m1``). Every rank ends with the same bits; at world 1 the tensor is left
     unchanged (not even quantized). GPU tensors run on the current stream; with ``async_op=True``
     on a side stream that first waits for the current one, and the returned handle's ``wait()``
     makes the current stream wait for it. CPU tensors run synchronously (the handle is complete).
     Until ``wait()``, issue no other collective of the group from another stream (two collectives
-    of one group must not overlap on the device; :func:`order_after_compressed` is the fence)."""
+    of one group must not overlap on the device; :func:`order_after_compressed` is the fence).
+
+    Error feedback (docs/collectives.md "Error feedback"): ``residual`` (float32, ``tensor.numel()``
+    elements) is added to this rank's contribution before it is quantized and is left holding what the
+    quantization dropped; ``owner_residual`` (float32, ``ops.mx_owner_residual_numel(numel, W, wire=wire)``
+    elements) does the same for the requantization of the chunk this rank owns. Both are updated in place,
+    by the kernel that quantizes; either may be given alone, and every rank must make the same choice. Carry
+    them from call to call: the sum of what is sent then tracks the sum of the inputs to within one
+    bounded residual. At world 1 they are left untouched, like the tensor."""
     opn = _op_name(op)
     if opn is None:
         raise ValueError(f"all_reduce_compressed: only ReduceOp.SUM and ReduceOp.AVG are supported, got {op}")
@@ -111,15 +138,19 @@ def all_reduce_compressed(tensor: torch.Tensor, op=dist.ReduceOp.SUM, group=None
     if tensor.dtype not in ops.MX_DTYPES:
         raise TypeError(f"all_reduce_compressed: float32, bfloat16 or float16 tensors only, got {tensor.dtype}")
     world = dist.get_world_size(group)
+    _check_residual("all_reduce_compressed", "residual", residual, tensor.numel(), tensor.device)
+    _check_residual("all_reduce_compressed", "owner_residual", owner_residual,
+                    ops.mx_owner_residual_numel(tensor.numel(), world, wire=wire), tensor.device)
     if world == 1 or tensor.numel() == 0:
         return CompressedWork() if async_op else None
     if not tensor.is_cuda:
         with torch.no_grad():
-            _run_cpu(tensor, opn, group, world, wire)
+            _run_cpu(tensor, opn, group, world, wire, residual, owner_residual)
         return CompressedWork() if async_op else None
     if world > MAX_GPU_WORLD:
         raise ValueError(f"all_reduce_compressed: GPU groups of up to {MAX_GPU_WORLD} ranks, got {world}")
-    return _issue_gpu(lambda: _run_gpu(tensor, opn, group, world, wire), (tensor,), async_op)
+    held = tuple(t for t in (tensor, residual, owner_residual) if t is not None)
+    return _issue_gpu(lambda: _run_gpu(tensor, opn, group, world, wire, residual, owner_residual), held, async_op)
 
 
 def _issue_gpu(run, tensors, async_op):
@@ -180,17 +211,23 @@ def _done(async_op):
 
 
 def reduce_scatter_compressed(output: torch.Tensor, input: torch.Tensor, op=dist.ReduceOp.SUM, group=None,
-                              wire: str = "mxfp8_e4m3", async_op: bool = False):
+                              wire: str = "mxfp8_e4m3", async_op: bool = False, *,
+                              residual: torch.Tensor | None = None):
     """SUM / AVG reduce-scatter of ``input`` (``W * m`` elements; f32, bf16 or f16) into ``output`` (``m``
     elements) over the wire format ``wire``: rank ``k`` ends with the f32 fold, in rank order, of every
     rank's quantized shard ``k`` (its own included), rounded once to the dtype. The fold is not
     quantized again. At world 1 ``input`` is copied bit for bit. Streams and ``async_op`` as in
-    :func:`all_reduce_compressed`."""
+    :func:`all_reduce_compressed`.
+
+    ``residual`` (float32, ``input.numel()`` elements; error feedback as in :func:`all_reduce_compressed`) is
+    added to ``input`` before it is quantized and left holding what the quantization dropped; ``input`` itself is
+    not modified. The fold is not quantized, so there is no owner residual. Untouched at world 1."""
     who = "reduce_scatter_compressed"
     opn = _op_name(op)
     if opn is None:
         raise ValueError(f"{who}: only ReduceOp.SUM and ReduceOp.AVG are supported, got {op}")
     world = _check_pair(who, output, input, wire, group, input, output)
+    _check_residual(who, "residual", residual, input.numel(), input.device)
     m = output.numel()
     if m == 0:
         return _done(async_op)
@@ -200,19 +237,19 @@ def reduce_scatter_compressed(output: torch.Tensor, input: torch.Tensor, op=dist
         return _done(async_op)
     if not input.is_cuda:
         with torch.no_grad():
-            w = ops.mx_quantize_shards_reference(input, world, wire=wire)
+            w = ops.mx_quantize_shards_reference(input, world, wire=wire, residual=residual)
             recv = torch.empty_like(w)
             dist.all_to_all_single(recv, w, group=group)
             output.copy_(ops.mx_fold_reference(recv, world, m, output.dtype, opn, wire=wire).view_as(output))
         return _done(async_op)
 
     def run():
-        w = ops.mx_quantize_shards(input, world, wire=wire)
+        w = ops.mx_quantize_shards(input, world, wire=wire, residual=residual)
         recv = torch.empty_like(w)
         dist.all_to_all_single(recv, w, group=group)  # chunk r of every rank -> rank r, in rank order
         ops.mx_fold(recv, world, m, output.dtype, opn, out=output, wire=wire)
 
-    return _issue_gpu(run, (output, input), async_op)
+    return _issue_gpu(run, (output, input) if residual is None else (output, input, residual), async_op)
 
 
 def all_gather_compressed(output: torch.Tensor, input: torch.Tensor, group=None, wire: str = "mxfp8_e4m3",

@@ -27,7 +27,13 @@ contract, MI355X-first:
 * ``wire="mxfp8_e4m3"`` or ``wire="mxfp4_e2m1"``: every bucket goes through
   ``all_reduce_compressed`` (block-scaled FP8 or FP4 on the links, f32 sums, AVG;
   parallel/compressed.py) instead of ``dist.all_reduce``. The default ``wire=None`` is the exact
-  path above.
+  path above;
+* ``error_feedback=True`` (with a wire): every bucket keeps what the quantizer dropped of its
+  gradients -- a local residual for this rank's contribution and an owner residual for the chunk it
+  requantizes -- and adds it to the next step's, so the quantization error cancels over steps instead
+  of biasing every step the same way (docs/collectives.md "Error feedback"). The residuals are f32:
+  4 bytes per gradient element, plus ``4 * 32 * cb`` bytes per bucket (``cb =
+  ops.mx_chunk_blocks(bucket elements, world)``, about ``4 / world`` bytes per element more).
 
 ``broadcast_parameters`` and ``scatter_batch`` cover the other two uses.
 torch's own ``DistributedDataParallel`` also runs unchanged on this backend.
@@ -71,13 +77,23 @@ class _Bucket:
             off += p.numel()
         self.pending = 0
         self.work = None
+        self.residual = self.owner_residual = None  # error feedback (GradBucketer(error_feedback=True))
 
 
 class GradBucketer:
-    """Overlapped, bucketed gradient all-reduce (average) for one module."""
+    """Overlapped, bucketed gradient all-reduce (average) for one module.
+
+    ``error_feedback=True`` (needs ``wire``): each bucket owns a zero-initialised f32 local residual of
+    ``flat.numel()`` elements and an owner residual of ``ops.mx_owner_residual_numel(flat.numel(), world)``
+    and passes both to every ``all_reduce_compressed``. Memory: 4 bytes per gradient element plus
+    ``4 * 32 * cb`` bytes per bucket. Backward passes inside ``no_sync()`` send nothing and leave the
+    residuals alone. ``residuals`` lists them, ``reset_error_feedback()`` zeroes them."""
 
     def __init__(self, module: torch.nn.Module, group=None, bucket_bytes: int = 256 << 20,
-                 average: bool = True, wire: str | None = None):
+                 average: bool = True, wire: str | None = None, error_feedback: bool = False):
+        if error_feedback and wire is None:
+            raise ValueError("GradBucketer: error_feedback=True needs a compressed wire (wire=None sends exact "
+                             "gradients: there is no quantization error to feed back)")
         if wire is not None:
             from .compressed import WIRES
 
@@ -86,6 +102,7 @@ class GradBucketer:
             if not average:
                 raise ValueError("GradBucketer: a compressed wire averages (average=True)")
         self.wire = wire
+        self.error_feedback = bool(error_feedback)
         self.group = group
         self.average = average
         self.world = dist.get_world_size(group)
@@ -103,6 +120,13 @@ class GradBucketer:
             cur_bytes += nb
         if cur:
             self._add_bucket(cur)
+        if self.error_feedback:
+            from ..ops import mx_owner_residual_numel
+
+            for b in self.buckets:
+                b.residual = torch.zeros(b.numel, dtype=torch.float32, device=b.flat.device)
+                b.owner_residual = torch.zeros(mx_owner_residual_numel(b.numel, self.world, wire=wire),
+                                               dtype=torch.float32, device=b.flat.device)
         self._hooks = [p.register_post_accumulate_grad_hook(self._on_grad) for p in params]
         self._sync = True
         # (a compressed wire divides before it requantizes: always fused)
@@ -151,7 +175,8 @@ class GradBucketer:
         if self.wire is not None:
             from .compressed import all_reduce_compressed
 
-            return all_reduce_compressed(b.flat, dist.ReduceOp.AVG, group=self.group, wire=self.wire, async_op=True)
+            return all_reduce_compressed(b.flat, dist.ReduceOp.AVG, group=self.group, wire=self.wire, async_op=True,
+                                         residual=b.residual, owner_residual=b.owner_residual)
         return dist.all_reduce(b.flat, op=self._op, group=self.group, async_op=True)
 
     def finish(self) -> None:
@@ -170,6 +195,17 @@ class GradBucketer:
                 b.flat.div_(self.world)
             _unpack(b)
         self._reset()
+
+    @property
+    def residuals(self):
+        """[(local residual, owner residual)] per bucket, the live f32 tensors; empty without error feedback."""
+        return [(b.residual, b.owner_residual) for b in self.buckets] if self.error_feedback else []
+
+    def reset_error_feedback(self) -> None:
+        """Zero every residual (after a change of learning-rate regime, a loss-scale change, a restart)."""
+        for local, owner in self.residuals:
+            local.zero_()
+            owner.zero_()
 
     def remove(self) -> None:
         for h in self._hooks:

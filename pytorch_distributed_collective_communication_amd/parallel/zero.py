@@ -43,6 +43,14 @@ only the replicated copy used for forward and backward is the dequantized
 wire, the same bits on every rank. Spaces of other dtypes keep the uncompressed
 calls; the defaults (``None``) are the uncompressed path, call for call.
 
+``grad_error_feedback=True`` (with a ``grad_wire``): every space on the gradient wire keeps an f32
+residual of its flat gradient's size -- 4 bytes per gradient element -- that
+``reduce_scatter_compressed`` adds to this rank's gradients before it quantizes them and leaves
+holding what the quantizer dropped (docs/collectives.md "Error feedback"), so the error cancels over
+steps. The fold is not quantized again, so there is no owner residual; ``param_wire`` is untouched
+(parameters are not accumulated). ``state_dict()`` saves the residuals, ``load_state_dict()`` restores
+them (a checkpoint without them loads as zeros).
+
 ``state_dict()`` / ``load_state_dict()`` save and restore this rank's shard
 (sharded checkpoint: every rank writes its own file) and re-gather the
 parameters on load.
@@ -163,15 +171,22 @@ class ShardedOptimizer:
     parameters are bf16. ``overlap=False`` defers every reduce-scatter to
     :meth:`step`. ``grad_wire`` / ``param_wire`` (default ``None``: uncompressed;
     ``"mxfp8_e4m3"`` or ``"mxfp4_e2m1"``, each on its own) pick the wire of the reduce-scatters / the all-gathers of
-    float32, bfloat16 and float16 parameters. One parameter group: the inner optimizer's hyper-parameters
+    float32, bfloat16 and float16 parameters. ``grad_error_feedback=True`` (needs ``grad_wire``) carries the
+    quantization error of this rank's gradients from step to step in an f32 residual, 4 bytes per gradient
+    element, saved by :meth:`state_dict`. One parameter group: the inner optimizer's hyper-parameters
     come from ``**opt_kwargs``.
     """
 
     def __init__(self, params: Iterable[torch.nn.Parameter], optimizer_cls=torch.optim.SGD, group=None,
                  master_dtype: torch.dtype = torch.float32, broadcast_from: int | None = 0,
                  bucket_bytes: int = 256 << 20, overlap: bool = True, grad_wire: str | None = None,
-                 param_wire: str | None = None, **opt_kwargs):
+                 param_wire: str | None = None, grad_error_feedback: bool = False, **opt_kwargs):
         from .compressed import WIRES
+
+        if grad_error_feedback and grad_wire is None:
+            raise ValueError("ShardedOptimizer: grad_error_feedback=True needs a grad_wire (grad_wire=None sends "
+                             "exact gradients: there is no quantization error to feed back)")
+        self.grad_error_feedback = bool(grad_error_feedback)
 
         for name, w in (("grad_wire", grad_wire), ("param_wire", param_wire)):
             if w is not None and w not in WIRES:
@@ -193,6 +208,9 @@ class ShardedOptimizer:
             by_key.setdefault((str(p.device), p.dtype), []).append(p)
         self.spaces = [_FlatSpace(ps, self.world, self.rank, master_dtype, bucket_bytes) for ps in by_key.values()]
         self._space_of = {id(p): s for s in self.spaces for p in s.params}
+        for s in self.spaces:  # the error-feedback residual of the space's flat gradient, or None
+            s.grad_residual = (torch.zeros(s.padded, dtype=torch.float32, device=s.device)
+                               if self.grad_error_feedback and self._on_wire(s, grad_wire) else None)
         self.inner = optimizer_cls([s.master for s in self.spaces], **opt_kwargs)
         self._avg = self._fused_avg()
         self._op = dist.ReduceOp.AVG if self._avg else dist.ReduceOp.SUM
@@ -246,7 +264,9 @@ class ShardedOptimizer:
 
             b.work = reduce_scatter_compressed(s.grad_shard[b.soff:b.soff + b.shard], s.grad[b.off:b.off + b.padded],
                                                op=dist.ReduceOp.AVG, group=self.group, wire=self.grad_wire,
-                                               async_op=True)
+                                               async_op=True,
+                                               residual=None if s.grad_residual is None
+                                               else s.grad_residual[b.off:b.off + b.padded])
             return
         self._fence(s)
         b.work = dist.reduce_scatter_tensor(s.grad_shard[b.soff:b.soff + b.shard], s.grad[b.off:b.off + b.padded],
@@ -320,8 +340,15 @@ class ShardedOptimizer:
         return [(str(s.dtype), [(b.off, b.padded) for b in s.buckets]) for s in self.spaces]
 
     def state_dict(self) -> dict:
-        """This rank's shard: master weights + inner optimizer state (+ layout check)."""
+        """This rank's shard: master weights + inner optimizer state (+ layout check), and with
+        ``grad_error_feedback`` this rank's gradient residuals (``grad_residual``: per space a CPU clone, or None)."""
+        for s in self.spaces:  # (a reduce-scatter still in flight on the side stream is updating its residual)
+            if s.grad_residual is not None:
+                self._fence(s)
+        extra = {"grad_residual": [None if s.grad_residual is None else s.grad_residual.detach().cpu().clone()
+                                   for s in self.spaces]} if self.grad_error_feedback else {}
         return {
+            **extra,
             "world": self.world,
             "rank": self.rank,
             "layout": self._layout(),
@@ -339,6 +366,15 @@ class ShardedOptimizer:
         for s, m in zip(self.spaces, sd["master"]):
             s.master.copy_(m)
         self.inner.load_state_dict(sd["inner"])
+        saved = sd.get("grad_residual") or [None] * len(self.spaces)  # (an older checkpoint: zeros)
+        for s, r in zip(self.spaces, saved):
+            if s.grad_residual is None:
+                continue
+            self._fence(s)
+            if r is None:
+                s.grad_residual.zero_()
+            else:
+                s.grad_residual.copy_(r)
         self._gather()
 
     def sharded_state_bytes(self) -> int:
