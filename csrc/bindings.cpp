@@ -122,6 +122,12 @@ float* mx_residual(const c10::optional<at::Tensor>& r, int64_t numel, const at::
   TORCH_CHECK_VALUE(al16(r->data_ptr()), who, ": the residual must be 16-byte aligned");
   return r->data_ptr<float>();
 }
+// Stochastic rounding (docs/collectives.md "Stochastic rounding"): `sr` selects the kernels that round by the
+// words of (seed, stream, element index); with a residual it is refused (the two are alternatives).
+void mx_check_sr(bool sr, bool residual, int64_t stream, const char* who) {
+  TORCH_CHECK_VALUE(!(sr && residual), who, ": stochastic rounding and a residual are alternatives");
+  TORCH_CHECK_VALUE(stream >= 0 && stream <= 0xffffffffll, who, ": stream must be in [0, 2^32)");
+}
 using pdcc::kern::MxFormat;
 MxFormat mx_format(const std::string& wire, const char* who) {
   if (wire == "mxfp8_e4m3") return MxFormat::FP8_E4M3;
@@ -131,8 +137,10 @@ MxFormat mx_format(const std::string& wire, const char* who) {
 }
 
 at::Tensor mx_quantize(const at::Tensor& x, int world, const c10::optional<at::Tensor>& out, const std::string& fmt,
-                       const c10::optional<at::Tensor>& residual) {
+                       const c10::optional<at::Tensor>& residual, bool sr, uint64_t seed, int64_t sr_stream,
+                       uint64_t index_offset) {
   const MxFormat f = mx_format(fmt, "mx_quantize");
+  mx_check_sr(sr, residual.has_value(), sr_stream, "mx_quantize");
   TORCH_CHECK(x.is_cuda(), "mx_quantize: GPU tensors only");
   TORCH_CHECK(world >= 1, "mx_quantize: world must be >= 1");
   const auto d = mx_dtype(x, "mx_quantize");
@@ -147,16 +155,20 @@ at::Tensor mx_quantize(const at::Tensor& x, int world, const c10::optional<at::T
               x.device());
   at::Tensor src = mx_in(x), w = mx_out(wire);
   hipStream_t s = c10::hip::getCurrentHIPStreamMasqueradingAsCUDA(x.device().index()).stream();
-  hipError_t e = res ? pdcc::kern::mx_quantize_ef(src.data_ptr(), numel, d, res, w.data_ptr(), cb, (size_t)world, s, f)
-                     : pdcc::kern::mx_quantize(src.data_ptr(), numel, d, w.data_ptr(), cb, (size_t)world, s, f);
+  hipError_t e = sr    ? pdcc::kern::mx_quantize_sr(src.data_ptr(), numel, d, w.data_ptr(), cb, (size_t)world, seed,
+                                                    (uint32_t)sr_stream, index_offset, s, f)
+                 : res ? pdcc::kern::mx_quantize_ef(src.data_ptr(), numel, d, res, w.data_ptr(), cb, (size_t)world, s, f)
+                       : pdcc::kern::mx_quantize(src.data_ptr(), numel, d, w.data_ptr(), cb, (size_t)world, s, f);
   TORCH_CHECK(e == hipSuccess, "mx_quantize launch failed: ", hipGetErrorString(e));
   if (!w.is_same(wire)) wire.copy_(w);
   return wire;
 }
 
 at::Tensor mx_reduce(const at::Tensor& wire, int nsrc, const std::string& op, const c10::optional<at::Tensor>& out,
-                     const std::string& fmt, const c10::optional<at::Tensor>& residual) {
+                     const std::string& fmt, const c10::optional<at::Tensor>& residual, bool sr, uint64_t seed,
+                     int64_t sr_stream) {
   const MxFormat f = mx_format(fmt, "mx_reduce");
+  mx_check_sr(sr, residual.has_value(), sr_stream, "mx_reduce");
   mx_check_wire(wire, "mx_reduce");
   TORCH_CHECK(nsrc >= 1 && nsrc <= pdcc::kern::kMaxRanks, "mx_reduce: 1..8 sources");
   TORCH_CHECK_VALUE(op == "sum" || op == "avg", "mx_reduce: op must be 'sum' or 'avg', got '", op, "'");
@@ -172,8 +184,10 @@ at::Tensor mx_reduce(const at::Tensor& wire, int nsrc, const std::string& op, co
   TORCH_CHECK(res.device() == wire.device() && res.numel() == chunk, "mx_reduce: out must hold ", chunk, " bytes");
   at::Tensor in = mx_in(wire), o = mx_out(res);
   hipStream_t s = c10::hip::getCurrentHIPStreamMasqueradingAsCUDA(wire.device().index()).stream();
-  hipError_t e = r ? pdcc::kern::mx_reduce_ef(in.data_ptr(), nsrc, cb, kop(op), nsrc, r, o.data_ptr(), s, f)
-                   : pdcc::kern::mx_reduce(in.data_ptr(), nsrc, cb, kop(op), nsrc, o.data_ptr(), s, f);
+  hipError_t e = sr  ? pdcc::kern::mx_reduce_sr(in.data_ptr(), nsrc, cb, kop(op), nsrc, o.data_ptr(), seed,
+                                                (uint32_t)sr_stream, s, f)
+                 : r ? pdcc::kern::mx_reduce_ef(in.data_ptr(), nsrc, cb, kop(op), nsrc, r, o.data_ptr(), s, f)
+                     : pdcc::kern::mx_reduce(in.data_ptr(), nsrc, cb, kop(op), nsrc, o.data_ptr(), s, f);
   TORCH_CHECK(e == hipSuccess, "mx_reduce launch failed: ", hipGetErrorString(e));
   if (!o.is_same(res)) res.copy_(o);
   return res;
@@ -200,8 +214,10 @@ void mx_dequantize(const at::Tensor& wire, int world, at::Tensor& out, const std
 
 // ---- the shard layout (kernels/mx_layout.h): chunk r is shard r of `numel / world` elements
 at::Tensor mx_quantize_shards(const at::Tensor& x, int world, const c10::optional<at::Tensor>& out,
-                              const std::string& fmt, const c10::optional<at::Tensor>& residual) {
+                              const std::string& fmt, const c10::optional<at::Tensor>& residual, bool sr, uint64_t seed,
+                              int64_t sr_stream, uint64_t index_offset) {
   const MxFormat f = mx_format(fmt, "mx_quantize_shards");
+  mx_check_sr(sr, residual.has_value(), sr_stream, "mx_quantize_shards");
   TORCH_CHECK(x.is_cuda(), "mx_quantize_shards: GPU tensors only");
   TORCH_CHECK(world >= 1 && world <= 65535, "mx_quantize_shards: world must be 1..65535");
   const auto d = mx_dtype(x, "mx_quantize_shards");
@@ -218,8 +234,10 @@ at::Tensor mx_quantize_shards(const at::Tensor& x, int world, const c10::optiona
               " bytes on ", x.device());
   at::Tensor src = mx_in(x), w = mx_out(wire);
   hipStream_t s = c10::hip::getCurrentHIPStreamMasqueradingAsCUDA(x.device().index()).stream();
-  hipError_t e = res ? pdcc::kern::mx_quantize_shards_ef(src.data_ptr(), m, d, res, w.data_ptr(), cb, (size_t)world, s, f)
-                     : pdcc::kern::mx_quantize_shards(src.data_ptr(), m, d, w.data_ptr(), cb, (size_t)world, s, f);
+  hipError_t e = sr    ? pdcc::kern::mx_quantize_shards_sr(src.data_ptr(), m, d, w.data_ptr(), cb, (size_t)world, seed,
+                                                           (uint32_t)sr_stream, index_offset, s, f)
+                 : res ? pdcc::kern::mx_quantize_shards_ef(src.data_ptr(), m, d, res, w.data_ptr(), cb, (size_t)world, s, f)
+                       : pdcc::kern::mx_quantize_shards(src.data_ptr(), m, d, w.data_ptr(), cb, (size_t)world, s, f);
   TORCH_CHECK(e == hipSuccess, "mx_quantize_shards launch failed: ", hipGetErrorString(e));
   if (!w.is_same(wire)) wire.copy_(w);
   return wire;
@@ -422,19 +440,25 @@ PYBIND11_MODULE(_C, m) {
         py::arg("ntl") = -1,
         "K2: one-launch multi-tensor copy (max_blocks/depth 0 = defaults)");
   m.def("mx_quantize", &mx_quantize, py::arg("x"), py::arg("world") = 1, py::arg("out") = py::none(),
-        py::arg("fmt") = "mxfp8_e4m3", py::arg("residual") = py::none(),
+        py::arg("fmt") = "mxfp8_e4m3", py::arg("residual") = py::none(), py::arg("sr") = false, py::arg("seed") = 0,
+        py::arg("stream") = 0, py::arg("index_offset") = 0,
         "tensor (f32 / bf16 / f16) -> mxfp8_e4m3 / mxfp4_e2m1 wire of `world` chunks, on the current stream; "
-        "`residual`: one float per element of error feedback, added before and updated in place");
+        "`residual`: one float per element of error feedback, added before and updated in place; `sr`: stochastic "
+        "rounding by the words of (seed, stream, index_offset + element index)");
   m.def("mx_reduce", &mx_reduce, py::arg("wire"), py::arg("nsrc"), py::arg("op") = "sum", py::arg("out") = py::none(),
-        py::arg("fmt") = "mxfp8_e4m3", py::arg("residual") = py::none(),
+        py::arg("fmt") = "mxfp8_e4m3", py::arg("residual") = py::none(), py::arg("sr") = false, py::arg("seed") = 0,
+        py::arg("stream") = 0,
         "nsrc chunk wires back to back -> one chunk wire (dequantize, fold in f32 in source order, requantize); "
-        "`residual`: 32 cb floats of error feedback, updated in place");
+        "`residual`: 32 cb floats of error feedback, updated in place; `sr`: stochastic requantization by the "
+        "words of (seed, stream, index in the chunk)");
   m.def("mx_dequantize", &mx_dequantize, py::arg("wire"), py::arg("world"), py::arg("out"),
         py::arg("fmt") = "mxfp8_e4m3",
         "mxfp8_e4m3 / mxfp4_e2m1 wire of `world` chunks -> out (f32 / bf16 / f16), exactly out.numel() elements");
   m.def("mx_quantize_shards", &mx_quantize_shards, py::arg("x"), py::arg("world"), py::arg("out") = py::none(),
-        py::arg("fmt") = "mxfp8_e4m3", py::arg("residual") = py::none(),
-        "tensor of `world` shards -> shard wire: chunk r is the wire of shard r alone; `residual` as in mx_quantize");
+        py::arg("fmt") = "mxfp8_e4m3", py::arg("residual") = py::none(), py::arg("sr") = false, py::arg("seed") = 0,
+        py::arg("stream") = 0, py::arg("index_offset") = 0,
+        "tensor of `world` shards -> shard wire: chunk r is the wire of shard r alone; `residual` and `sr` as in "
+        "mx_quantize");
   m.def("mx_dequantize_shards", &mx_dequantize_shards, py::arg("wire"), py::arg("world"), py::arg("out"),
         py::arg("fmt") = "mxfp8_e4m3",
         "shard wire of `world` chunks -> out: chunk r fills out[r m, (r + 1) m), m = out.numel() / world");

@@ -365,6 +365,19 @@ hipError_t mx_quantize_shards_ef(const void* src, size_t m, DType t, float* resi
 // it is quantized again and replaced by what that quantization dropped.
 hipError_t mx_reduce_ef(const void* wire_in, int nsrc, size_t cb, RedOp op, int avg_div, float* residual,
                         void* wire_out, hipStream_t stream, MxFormat fmt = MxFormat::FP8_E4M3);
+// Stochastic rounding (docs/collectives.md "Stochastic rounding", mx_sr.h): the same kernels rounding
+// every payload element up or down by the counter-based word of (seed, sr_stream, element index);
+// scale bytes, layouts and the bytes moved are those of the plain kernels. Quantize: the index is
+// `index_offset` plus the element's index in the tensor, in both layouts (the sum must fit 64 bits).
+hipError_t mx_quantize_sr(const void* src, size_t numel, DType t, void* wire, size_t cb, size_t nchunks,
+                          uint64_t seed, uint32_t sr_stream, uint64_t index_offset, hipStream_t stream,
+                          MxFormat fmt = MxFormat::FP8_E4M3);
+hipError_t mx_quantize_shards_sr(const void* src, size_t m, DType t, void* wire, size_t cb, size_t nchunks,
+                                 uint64_t seed, uint32_t sr_stream, uint64_t index_offset, hipStream_t stream,
+                                 MxFormat fmt = MxFormat::FP8_E4M3);
+// Reduce: the index is the element's index in the chunk, 0 .. 32 cb - 1.
+hipError_t mx_reduce_sr(const void* wire_in, int nsrc, size_t cb, RedOp op, int avg_div, void* wire_out, uint64_t seed,
+                        uint32_t sr_stream, hipStream_t stream, MxFormat fmt = MxFormat::FP8_E4M3);
 
 }  // namespace kern
 }  // namespace pdcc

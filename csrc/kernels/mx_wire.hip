@@ -12,6 +12,9 @@
 //                  reduce, which add an f32 residual before they quantize and leave what the
 //                  quantizer dropped in it (docs/collectives.md "Error feedback"); per f32 element
 //                  quantize then reads 8 and writes 4 + 33/32 bytes instead of reading 4
+//   mx_quantize_sr / mx_quantize_shards_sr / mx_reduce_sr: the SR instantiations of quantize and
+//                  reduce, which round the payload stochastically (docs/collectives.md "Stochastic
+//                  rounding", mx_sr.h); they move the bytes of the plain kernels
 //
 // All of them are streaming kernels: a lane moves 16 B on the wide side of its conversion (the tensor
 // for quantize / dequantize / fold, the payload for reduce), the lanes of a block sit next to each other
@@ -35,6 +38,7 @@
 
 #include "dev_common.h"
 #include "mx_layout.h"
+#include "mx_sr.h"
 
 namespace pdcc {
 namespace dev {
@@ -144,6 +148,18 @@ template <> struct MxFmt<MxFormat::FP8_E4M3> {
       if (sc.blank) q[d] = 0u;
     }
   }
+  // stochastic rounding: element j takes the word `word(j)`; the integer rounding of mx_sr.h throughout
+  template <int N, class W> __device__ static __forceinline__ void pack_sr(const float* f, const MxScale& sc, uint32_t* q,
+                                                                          const W& word) {
+#pragma unroll
+    for (int d = 0; d < N / 4; ++d) {
+      uint32_t w = 0u;
+#pragma unroll
+      for (int j = 0; j < 4; ++j)
+        w |= kern::mx_sr_e4m3(__float_as_uint(f[4 * d + j] * sc.inv), word(4 * d + j)) << (8 * j);
+      q[d] = sc.blank ? 0u : w;
+    }
+  }
   template <int N> __device__ static __forceinline__ void unpack(const uint32_t* q, float scale, float* f) {
 #pragma unroll
     for (int d = 0; d < N / 4; ++d) widen4(q[d], scale, f + 4 * d);
@@ -159,6 +175,18 @@ template <> struct MxFmt<MxFormat::FP4_E2M1> {
       q[d] = fp4_narrow4(f[8 * d], f[8 * d + 1], f[8 * d + 2], f[8 * d + 3], sc.inv, 0u, false);
       if constexpr (N >= 8) q[d] = fp4_narrow4(f[8 * d + 4], f[8 * d + 5], f[8 * d + 6], f[8 * d + 7], sc.inv, q[d], true);
       if (sc.blank) q[d] = 0u;
+    }
+  }
+  template <int N, class W> __device__ static __forceinline__ void pack_sr(const float* f, const MxScale& sc, uint32_t* q,
+                                                                          const W& word) {
+    constexpr int G = N < 8 ? N : 8;  // elements of one dword
+#pragma unroll
+    for (int d = 0; d < (N + 7) / 8; ++d) {
+      uint32_t w = 0u;
+#pragma unroll
+      for (int j = 0; j < G; ++j)
+        w |= kern::mx_sr_e2m1(__float_as_uint(f[8 * d + j] * sc.inv), word(8 * d + j)) << (4 * j);
+      q[d] = sc.blank ? 0u : w;
     }
   }
   template <int N> __device__ static __forceinline__ void unpack(const uint32_t* q, float scale, float* f) {
@@ -181,6 +209,29 @@ __device__ __forceinline__ float ef_residual(float v, float d) {
   const float r = v - d;
   return abs_bits(d) < 0x7f800000u && abs_bits(r) < 0x7f800000u ? r : 0.0f;
 }
+
+// The random words of a lane's consecutive elements (mx_sr.h): element j has the index i0 + j. The
+// indices of one lane may straddle a multiple of 2^32, where the key changes; both keys are the call's
+// key itself while the index base and the tensor stay below 2^32.
+struct SrWords {
+  uint32_t lo, kh0, kh1;
+  __device__ __forceinline__ SrWords(uint32_t key, uint64_t i0, int n) {
+    lo = (uint32_t)i0;
+    const uint32_t h = (uint32_t)(i0 >> 32);
+    kh0 = kern::mx_sr_key_h(key, h);
+    kh1 = kh0;
+    if (lo + (uint32_t)(n - 1) < lo) kh1 = kern::mx_sr_key_h(key, h + 1u);
+  }
+  __device__ __forceinline__ uint32_t operator()(int j) const {
+    const uint32_t l = lo + (uint32_t)j;
+    return kern::mx_sr_word_lo(l < lo ? kh1 : kh0, l);
+  }
+};
+// ... and of a chunk's own elements (reduce): 32 cb <= 2^32 of them, so the key is the call's
+struct SrChunkWords {
+  uint32_t lo, key;
+  __device__ __forceinline__ uint32_t operator()(int j) const { return kern::mx_sr_word_lo(key, lo + (uint32_t)j); }
+};
 
 // B (2, 4, 8 or 16) wire bytes at p (B-aligned) <-> the low bytes of q[(B + 3) / 4]
 template <int B>
@@ -219,10 +270,15 @@ __device__ __forceinline__ void st_wire(char* p, const uint32_t* q) {
 // the tensor, at the element's own index, so a lane's EPL floats are one or two 16-B vectors that
 // are aligned whenever its 16 B of the tensor are; nothing at or past the chunk's end is read or
 // written. The dequantized values come from the lane's own packed dwords.
-template <MxFormat F, DType DT, bool SHARD, bool VEC, bool EF>
+//
+// SR (stochastic rounding, never together with EF): the payload is rounded up or down by the word of
+// the element's index, `sr_base` plus its index in the tensor -- the same in the dealt and the shard
+// layout. The lane computes its EPL words itself; the scale byte and everything else are unchanged.
+template <MxFormat F, DType DT, bool SHARD, bool VEC, bool EF, bool SR>
 __global__ __launch_bounds__(256) void k_mx_quantize(const char* __restrict__ src, size_t numel,
                                                      char* __restrict__ wire, uint32_t cb, size_t m,
-                                                     float* __restrict__ res) {
+                                                     float* __restrict__ res, uint32_t sr_key, uint64_t sr_base) {
+  static_assert(!(EF && SR), "error feedback and stochastic rounding are alternatives");
   using T = Tr<DT>;
   using S = typename T::S;
   constexpr int EPL = 16 / (int)sizeof(S);
@@ -281,7 +337,8 @@ __global__ __launch_bounds__(256) void k_mx_quantize(const char* __restrict__ sr
       }
       const MxScale sc = M::scale(group_max<LPB>(am));
       uint32_t q[QW];
-      M::template pack<EPL>(f, sc, q);
+      if constexpr (SR) M::template pack_sr<EPL>(f, sc, q, SrWords(sr_key, sr_base + el0 + (uint64_t)v * EPL, EPL));
+      else M::template pack<EPL>(f, sc, q);
       // FP8: payload byte e of the chunk is element e of the chunk; FP4: byte e holds elements 2e, 2e + 1
       st_wire<QB>(w + (size_t)v * QB, q);
       if (v % LPB == 0) w[kern::mx_scale_off(F, cb, v / LPB)] = (char)sc.byte;
@@ -379,9 +436,13 @@ __global__ __launch_bounds__(256) void k_mx_dequantize(const char* __restrict__ 
 // AVG division and before the scale is taken, and becomes acc - D(Q(acc)) (+0 where not finite). A
 // lane's EPL floats are contiguous: they are loaded with the payloads and stored a payload dword's
 // elements at a time, straight from that dword.
-template <MxFormat F, int NSRC, bool AVG, bool EF>
+//
+// SR (never together with EF): the fold is requantized with the words of its elements' indices in the
+// chunk, v EPL + i.
+template <MxFormat F, int NSRC, bool AVG, bool EF, bool SR>
 __global__ __launch_bounds__(256) void k_mx_reduce(const char* __restrict__ in, uint32_t cb, int avg_div,
-                                                   char* __restrict__ out, float* __restrict__ res) {
+                                                   char* __restrict__ out, float* __restrict__ res, uint32_t sr_key) {
+  static_assert(!(EF && SR), "error feedback and stochastic rounding are alternatives");
   using M = MxFmt<F>;
   constexpr int EPL = 16 * kern::kMxBlock / M::kPayload;  // 16 or 32
   constexpr int LPB = kern::kMxBlock / EPL;               // 2 or 1
@@ -433,7 +494,8 @@ __global__ __launch_bounds__(256) void k_mx_reduce(const char* __restrict__ in, 
     }
     const MxScale sc = M::scale(group_max<LPB>(am));
     uint32_t q[4];
-    M::template pack<EPL>(acc, sc, q);
+    if constexpr (SR) M::template pack_sr<EPL>(acc, sc, q, SrChunkWords{v * (uint32_t)EPL, sr_key});
+    else M::template pack<EPL>(acc, sc, q);
     *reinterpret_cast<uint4*>(out + (size_t)v * 16) = make_uint4(q[0], q[1], q[2], q[3]);
     if (v % LPB == 0) out[kern::mx_scale_off(F, cb, v / LPB)] = (char)sc.byte;
     if constexpr (EF) {
@@ -562,20 +624,26 @@ dim3 mx_stream_grid(size_t cb, DType t, size_t nchunks) {
   return dim3(dev::mx_grid_x((uint64_t)cb * lpb, dev::kMxUnroll, nchunks, dev::kMxGridStream), (uint32_t)nchunks);
 }
 
+// key and index base of a stochastic call (mx_sr.h); null: round to nearest
+struct MxSr {
+  uint32_t key;
+  uint64_t base;
+};
 // quantize / dequantize of one format and dtype: the dealt kernel, or the shard one with or without vectors
-template <MxFormat F, DType DT, bool EF>
+template <MxFormat F, DType DT, bool EF, bool SR>
 void mx_quantize_ef_go(bool shard, bool vec, const dim3& grid, const char* s, size_t numel, char* w, uint32_t cb,
-                       size_t m, float* res, hipStream_t stream) {
-  if (!shard) hipLaunchKernelGGL((dev::k_mx_quantize<F, DT, false, true, EF>), grid, dim3(256), 0, stream, s, numel, w, cb, m, res);
-  else if (vec) hipLaunchKernelGGL((dev::k_mx_quantize<F, DT, true, true, EF>), grid, dim3(256), 0, stream, s, numel, w, cb, m, res);
-  else hipLaunchKernelGGL((dev::k_mx_quantize<F, DT, true, false, EF>), grid, dim3(256), 0, stream, s, numel, w, cb, m, res);
+                       size_t m, float* res, uint32_t key, uint64_t base, hipStream_t stream) {
+  if (!shard) hipLaunchKernelGGL((dev::k_mx_quantize<F, DT, false, true, EF, SR>), grid, dim3(256), 0, stream, s, numel, w, cb, m, res, key, base);
+  else if (vec) hipLaunchKernelGGL((dev::k_mx_quantize<F, DT, true, true, EF, SR>), grid, dim3(256), 0, stream, s, numel, w, cb, m, res, key, base);
+  else hipLaunchKernelGGL((dev::k_mx_quantize<F, DT, true, false, EF, SR>), grid, dim3(256), 0, stream, s, numel, w, cb, m, res, key, base);
 }
-// (`res` null: the plain kernels; otherwise the error-feedback ones)
+// (`sr`: the stochastic kernels; else `res` null: the plain kernels; otherwise the error-feedback ones)
 template <MxFormat F, DType DT>
 void mx_quantize_go(bool shard, bool vec, const dim3& grid, const char* s, size_t numel, char* w, uint32_t cb, size_t m,
-                    float* res, hipStream_t stream) {
-  if (res) mx_quantize_ef_go<F, DT, true>(shard, vec, grid, s, numel, w, cb, m, res, stream);
-  else mx_quantize_ef_go<F, DT, false>(shard, vec, grid, s, numel, w, cb, m, res, stream);
+                    float* res, const MxSr* sr, hipStream_t stream) {
+  if (sr) mx_quantize_ef_go<F, DT, false, true>(shard, vec, grid, s, numel, w, cb, m, nullptr, sr->key, sr->base, stream);
+  else if (res) mx_quantize_ef_go<F, DT, true, false>(shard, vec, grid, s, numel, w, cb, m, res, 0u, 0u, stream);
+  else mx_quantize_ef_go<F, DT, false, false>(shard, vec, grid, s, numel, w, cb, m, res, 0u, 0u, stream);
 }
 template <MxFormat F, DType DT>
 void mx_dequantize_go(bool shard, bool vec, const dim3& grid, const char* w, uint32_t cb, char* d, size_t numel, size_t m,
@@ -601,12 +669,13 @@ void mx_dequantize_dt(DType t, A... a) {
   }
 }
 hipError_t mx_quantize_any(MxFormat fmt, DType t, bool shard, bool vec, const void* src, size_t numel, void* wire,
-                           size_t cb, size_t nchunks, size_t m, hipStream_t stream, float* res = nullptr) {
+                           size_t cb, size_t nchunks, size_t m, hipStream_t stream, float* res = nullptr,
+                           const MxSr* sr = nullptr) {
   const dim3 grid = mx_stream_grid(cb, t, nchunks);
   const char* s = static_cast<const char*>(src);
   char* w = static_cast<char*>(wire);
-  if (fmt == MxFormat::FP4_E2M1) mx_quantize_dt<MxFormat::FP4_E2M1>(t, shard, vec, grid, s, numel, w, (uint32_t)cb, m, res, stream);
-  else mx_quantize_dt<MxFormat::FP8_E4M3>(t, shard, vec, grid, s, numel, w, (uint32_t)cb, m, res, stream);
+  if (fmt == MxFormat::FP4_E2M1) mx_quantize_dt<MxFormat::FP4_E2M1>(t, shard, vec, grid, s, numel, w, (uint32_t)cb, m, res, sr, stream);
+  else mx_quantize_dt<MxFormat::FP8_E4M3>(t, shard, vec, grid, s, numel, w, (uint32_t)cb, m, res, sr, stream);
   return hipGetLastError();
 }
 hipError_t mx_dequantize_any(MxFormat fmt, DType t, bool shard, bool vec, const void* wire, size_t cb, size_t nchunks,
@@ -666,6 +735,27 @@ hipError_t mx_quantize_shards_ef(const void* src, size_t m, DType t, float* resi
   return mx_quantize_any(fmt, t, true, vec, src, m * nchunks, wire, cb, nchunks, m, stream, residual);
 }
 
+hipError_t mx_quantize_sr(const void* src, size_t numel, DType t, void* wire, size_t cb, size_t nchunks,
+                          uint64_t seed, uint32_t sr_stream, uint64_t index_offset, hipStream_t stream, MxFormat fmt) {
+  if (!mx_fmt_ok(fmt) || !mx_dtype_ok(t)) return hipErrorInvalidValue;
+  if (!mx_cb_ok(cb) || nchunks == 0 || nchunks > 65535 || !mx_al16(wire) || (numel && !mx_al16(src)))
+    return hipErrorInvalidValue;
+  if (numel > cb * nchunks * kMxBlock || index_offset + numel < index_offset) return hipErrorInvalidValue;
+  const MxSr sr{mx_sr_key(seed, sr_stream), index_offset};
+  return mx_quantize_any(fmt, t, false, true, src, numel, wire, cb, nchunks, 0, stream, nullptr, &sr);
+}
+
+hipError_t mx_quantize_shards_sr(const void* src, size_t m, DType t, void* wire, size_t cb, size_t nchunks,
+                                 uint64_t seed, uint32_t sr_stream, uint64_t index_offset, hipStream_t stream,
+                                 MxFormat fmt) {
+  if (!mx_fmt_ok(fmt) || !mx_dtype_ok(t)) return hipErrorInvalidValue;
+  if (!mx_shards_ok(m, cb, nchunks) || !mx_al16(wire) || !mx_al16(src)) return hipErrorInvalidValue;
+  if (index_offset + m * nchunks < index_offset) return hipErrorInvalidValue;
+  const bool vec = m * mx_esize(t) % 16 == 0;
+  const MxSr sr{mx_sr_key(seed, sr_stream), index_offset};
+  return mx_quantize_any(fmt, t, true, vec, src, m * nchunks, wire, cb, nchunks, m, stream, nullptr, &sr);
+}
+
 hipError_t mx_dequantize_shards(const void* wire, size_t cb, size_t nchunks, void* dst, size_t m, DType t,
                                 hipStream_t stream, MxFormat fmt) {
   if (!mx_fmt_ok(fmt) || !mx_dtype_ok(t)) return hipErrorInvalidValue;
@@ -675,39 +765,43 @@ hipError_t mx_dequantize_shards(const void* wire, size_t cb, size_t nchunks, voi
 }
 
 namespace {
-template <MxFormat F, bool AVG, bool EF>
-hipError_t mx_reduce_go(const char* in, int nsrc, uint32_t cb, int avg_div, char* out, float* res, hipStream_t stream) {
+template <MxFormat F, bool AVG, bool EF, bool SR>
+hipError_t mx_reduce_go(const char* in, int nsrc, uint32_t cb, int avg_div, char* out, float* res, uint32_t key,
+                        hipStream_t stream) {
   constexpr int lpb = F == MxFormat::FP4_E2M1 ? 1 : 2;  // lanes per block: 16 payload bytes per lane
   const dim3 grid(dev::mx_grid_x((uint64_t)cb * lpb, 1, 1, dev::kMxGridReduce)), block(256);
   switch (nsrc) {
 #define PDCC_MX_N(N) \
-  case N: hipLaunchKernelGGL((dev::k_mx_reduce<F, N, AVG, EF>), grid, block, 0, stream, in, cb, avg_div, out, res); break;
+  case N: hipLaunchKernelGGL((dev::k_mx_reduce<F, N, AVG, EF, SR>), grid, block, 0, stream, in, cb, avg_div, out, res, key); break;
     PDCC_MX_N(1) PDCC_MX_N(2) PDCC_MX_N(3) PDCC_MX_N(4) PDCC_MX_N(5) PDCC_MX_N(6) PDCC_MX_N(7) PDCC_MX_N(8)
 #undef PDCC_MX_N
     default: return hipErrorInvalidValue;
   }
   return hipGetLastError();
 }
-// (`res` null: the plain kernels; otherwise the error-feedback ones)
+// (`key`: the stochastic kernels; else `res` null: the plain kernels; otherwise the error-feedback ones)
 template <MxFormat F>
 hipError_t mx_reduce_op(const char* in, int nsrc, uint32_t cb, RedOp op, int avg_div, char* out, float* res,
-                        hipStream_t stream) {
+                        const uint32_t* key, hipStream_t stream) {
+  if (key)
+    return op == RedOp::AVG ? mx_reduce_go<F, true, false, true>(in, nsrc, cb, avg_div, out, nullptr, *key, stream)
+                            : mx_reduce_go<F, false, false, true>(in, nsrc, cb, avg_div, out, nullptr, *key, stream);
   if (res)
-    return op == RedOp::AVG ? mx_reduce_go<F, true, true>(in, nsrc, cb, avg_div, out, res, stream)
-                            : mx_reduce_go<F, false, true>(in, nsrc, cb, avg_div, out, res, stream);
-  return op == RedOp::AVG ? mx_reduce_go<F, true, false>(in, nsrc, cb, avg_div, out, res, stream)
-                          : mx_reduce_go<F, false, false>(in, nsrc, cb, avg_div, out, res, stream);
+    return op == RedOp::AVG ? mx_reduce_go<F, true, true, false>(in, nsrc, cb, avg_div, out, res, 0u, stream)
+                            : mx_reduce_go<F, false, true, false>(in, nsrc, cb, avg_div, out, res, 0u, stream);
+  return op == RedOp::AVG ? mx_reduce_go<F, true, false, false>(in, nsrc, cb, avg_div, out, res, 0u, stream)
+                          : mx_reduce_go<F, false, false, false>(in, nsrc, cb, avg_div, out, res, 0u, stream);
 }
 hipError_t mx_reduce_any(const void* wire_in, int nsrc, size_t cb, RedOp op, int avg_div, void* wire_out, float* res,
-                         hipStream_t stream, MxFormat fmt) {
+                         hipStream_t stream, MxFormat fmt, const uint32_t* key = nullptr) {
   if (!mx_fmt_ok(fmt) || !mx_cb_ok(cb) || nsrc < 1 || nsrc > kMaxRanks || !mx_al16(wire_in) || !mx_al16(wire_out))
     return hipErrorInvalidValue;
   if (op != RedOp::SUM && op != RedOp::AVG) return hipErrorInvalidValue;
   if (op == RedOp::AVG && avg_div < 1) return hipErrorInvalidValue;
   const char* in = static_cast<const char*>(wire_in);
   char* out = static_cast<char*>(wire_out);
-  return fmt == MxFormat::FP4_E2M1 ? mx_reduce_op<MxFormat::FP4_E2M1>(in, nsrc, (uint32_t)cb, op, avg_div, out, res, stream)
-                                   : mx_reduce_op<MxFormat::FP8_E4M3>(in, nsrc, (uint32_t)cb, op, avg_div, out, res, stream);
+  return fmt == MxFormat::FP4_E2M1 ? mx_reduce_op<MxFormat::FP4_E2M1>(in, nsrc, (uint32_t)cb, op, avg_div, out, res, key, stream)
+                                   : mx_reduce_op<MxFormat::FP8_E4M3>(in, nsrc, (uint32_t)cb, op, avg_div, out, res, key, stream);
 }
 }  // namespace
 
@@ -720,6 +814,12 @@ hipError_t mx_reduce_ef(const void* wire_in, int nsrc, size_t cb, RedOp op, int 
                         void* wire_out, hipStream_t stream, MxFormat fmt) {
   if (!residual || !mx_al16(residual)) return hipErrorInvalidValue;
   return mx_reduce_any(wire_in, nsrc, cb, op, avg_div, wire_out, residual, stream, fmt);
+}
+
+hipError_t mx_reduce_sr(const void* wire_in, int nsrc, size_t cb, RedOp op, int avg_div, void* wire_out, uint64_t seed,
+                        uint32_t sr_stream, hipStream_t stream, MxFormat fmt) {
+  const uint32_t key = mx_sr_key(seed, sr_stream);
+  return mx_reduce_any(wire_in, nsrc, cb, op, avg_div, wire_out, nullptr, stream, fmt, &key);
 }
 
 namespace {

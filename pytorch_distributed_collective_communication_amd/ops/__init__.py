@@ -18,7 +18,9 @@
   byte and 32 ``float8_e4m3fn`` bytes each) and ``mxfp4_e2m1`` ("The ``mxfp4_e2m1`` wire format":
   16 bytes of two e2m1 nibbles instead), picked by the trailing keyword ``wire``.
   ``parallel/compressed.py`` builds ``all_reduce_compressed`` from them.
-  :func:`mx_quantize`, :func:`mx_quantize_shards` and :func:`mx_reduce` take ``residual=``: error feedback
+  :func:`mx_quantize`, :func:`mx_quantize_shards` and :func:`mx_reduce` take ``rounding="stochastic"`` with
+  ``seed=`` and ``stream=``: unbiased, stateless rounding of the payload (docs/collectives.md "Stochastic
+  rounding"), and ``residual=``: error feedback
   (docs/collectives.md "Error feedback"), an f32 tensor added before the quantization and left holding
   what it dropped, fused into the same kernel.
 * :func:`mx_quantize_shards`, :func:`mx_dequantize_shards`, :func:`mx_fold` -- the same wire with one
@@ -214,17 +216,46 @@ def _mx_check_residual(residual, numel: int, device, who: str) -> None:
         raise ValueError(f"{who}: the residual must be 16-byte aligned")
 
 
+MX_ROUNDINGS = ("nearest", "stochastic")
+
+
+def _mx_check_rounding(rounding, seed, stream, index_offset, numel, residual, who: str) -> bool:
+    """The rounding arguments (docs/collectives.md "Stochastic rounding"); True for ``"stochastic"``. The seed,
+    the stream and the offset are checked whatever the rounding is, so a wrong call fails the same way with both."""
+    if not isinstance(rounding, str) or rounding not in MX_ROUNDINGS:
+        raise ValueError(f"{who}: unknown rounding {rounding!r} (supported: {', '.join(MX_ROUNDINGS)})")
+    for name, v, top in (("seed", seed, 1 << 64), ("stream", stream, 1 << 32), ("index_offset", index_offset, 1 << 64)):
+        if isinstance(v, bool) or not isinstance(v, int):
+            raise TypeError(f"{who}: {name} must be an int, got {type(v).__name__}")
+        if not 0 <= v < top:
+            raise ValueError(f"{who}: {name} must be in [0, 2^{top.bit_length() - 1}), got {v}")
+    if index_offset + int(numel) > 1 << 64:
+        raise ValueError(f"{who}: index_offset + numel must not exceed 2^64")
+    sr = rounding == "stochastic"
+    if sr and residual is not None:
+        raise ValueError(f"{who}: rounding='stochastic' and a residual are alternatives, not both")
+    return sr
+
+
 def mx_quantize(x: torch.Tensor, world: int = 1, out: torch.Tensor | None = None, *,
-                wire: str = "mxfp8_e4m3", residual: torch.Tensor | None = None) -> torch.Tensor:
+                wire: str = "mxfp8_e4m3", residual: torch.Tensor | None = None, rounding: str = "nearest",
+                seed: int = 0, stream: int = 0, index_offset: int = 0) -> torch.Tensor:
     """``x`` (GPU; f32 / bf16 / f16) -> its wire in the format ``wire``: a uint8 tensor of ``world`` chunks
     of ``[32 cb payload bytes][cb scale bytes]`` (``mxfp4_e2m1``: 16 cb payload bytes, two elements to a
     byte), padding blocks included (scale 127, payload 0).
 
     ``residual`` (float32, one element per element of ``x``; error feedback): what is quantized is
     ``x.float() + residual``, and the residual becomes what the quantization dropped of that sum (+0
-    where that is not finite), in place and in the same launch. ``x`` is not modified."""
+    where that is not finite), in place and in the same launch. ``x`` is not modified.
+
+    ``rounding="stochastic"`` (docs/collectives.md "Stochastic rounding"): every payload element is rounded up
+    or down with the probability of its distance, by the counter-based word of ``(seed, stream,
+    index_offset + its index in x)`` -- no state, the same arguments give the same bytes. Scale bytes and
+    layout are unchanged. Not together with ``residual``."""
     _mx_check_dtype(x.dtype, "mx_quantize")
     _mx_payload(wire, "mx_quantize")
+    if _mx_check_rounding(rounding, seed, stream, index_offset, x.numel(), residual, "mx_quantize"):
+        return _C().mx_quantize(x.detach().reshape(-1), int(world), out, wire, None, True, seed, stream, index_offset)
     if residual is None:
         return _C().mx_quantize(x.detach().reshape(-1), int(world), out, wire)
     _mx_check_residual(residual, x.numel(), x.device, "mx_quantize")
@@ -232,15 +263,21 @@ def mx_quantize(x: torch.Tensor, world: int = 1, out: torch.Tensor | None = None
 
 
 def mx_reduce(w: torch.Tensor, /, nsrc: int, op: str = "sum", out: torch.Tensor | None = None, *,
-              wire: str = "mxfp8_e4m3", residual: torch.Tensor | None = None) -> torch.Tensor:
+              wire: str = "mxfp8_e4m3", residual: torch.Tensor | None = None, rounding: str = "nearest",
+              seed: int = 0, stream: int = 0) -> torch.Tensor:
     """``nsrc`` (1..8) chunk wires ``w`` back to back -> one chunk wire: every source dequantized, folded
     in f32 in source order (``avg``: then divided by ``nsrc``), and quantized again.
 
     ``residual`` (float32, 32 elements per block of a chunk: the owner residual) is added to the fold
-    before it is quantized again and becomes what that quantization dropped, in place."""
+    before it is quantized again and becomes what that quantization dropped, in place.
+
+    ``rounding="stochastic"``: the fold is quantized again by the words of ``(seed, stream, index in the
+    chunk)``; a single finite source comes back as its own bytes. Not together with ``residual``."""
     if op not in ("sum", "avg"):
         raise ValueError(f"mx_reduce: op must be 'sum' or 'avg', got {op!r}")
     pb = _mx_payload(wire, "mx_reduce")
+    if _mx_check_rounding(rounding, seed, stream, 0, 0, residual, "mx_reduce"):
+        return _C().mx_reduce(w, int(nsrc), op, out, wire, None, True, seed, stream)
     if residual is None:
         return _C().mx_reduce(w, int(nsrc), op, out, wire)
     _mx_check_residual(residual, w.numel() // ((pb + 1) * max(1, int(nsrc))) * MX_BLOCK, w.device, "mx_reduce")
@@ -271,13 +308,19 @@ def _mx_check_shards(numel: int, world: int, who: str) -> int:
 
 
 def mx_quantize_shards(x: torch.Tensor, world: int, out: torch.Tensor | None = None, *,
-                       wire: str = "mxfp8_e4m3", residual: torch.Tensor | None = None) -> torch.Tensor:
+                       wire: str = "mxfp8_e4m3", residual: torch.Tensor | None = None, rounding: str = "nearest",
+                       seed: int = 0, stream: int = 0, index_offset: int = 0) -> torch.Tensor:
     """``x`` (GPU; ``world`` shards of ``m`` elements) -> its shard wire: chunk ``r`` is the wire of shard
     ``r`` alone (``mx_shard_blocks(m)`` blocks; what lies past the shard's end counts as +0).
-    ``residual``: as in :func:`mx_quantize`, one float per element of ``x``."""
+    ``residual``: as in :func:`mx_quantize`, one float per element of ``x``. ``rounding``, ``seed``,
+    ``stream``, ``index_offset``: as in :func:`mx_quantize` -- an element draws the word of its index in
+    ``x``, so it is rounded the same way in both layouts."""
     _mx_check_dtype(x.dtype, "mx_quantize_shards")
     _mx_payload(wire, "mx_quantize_shards")
     _mx_check_shards(x.numel(), world, "mx_quantize_shards")
+    if _mx_check_rounding(rounding, seed, stream, index_offset, x.numel(), residual, "mx_quantize_shards"):
+        return _C().mx_quantize_shards(x.detach().reshape(-1), int(world), out, wire, None, True, seed, stream,
+                                       index_offset)
     if residual is None:
         return _C().mx_quantize_shards(x.detach().reshape(-1), int(world), out, wire)
     _mx_check_residual(residual, x.numel(), x.device, "mx_quantize_shards")
@@ -392,6 +435,68 @@ def _mx4_dequantize_blocks(q: torch.Tensor, s: torch.Tensor) -> torch.Tensor:
     return v * _mx_scale_values(s)[:, None]  # 6 2^126 -> inf: one f32 product
 
 
+# ---- stochastic rounding (docs/collectives.md "Stochastic rounding"), integer arithmetic on int64 tensors
+_M32 = 0xFFFFFFFF
+# per payload size: mantissa bits, f32 exponent field of the smallest normal magnitude, the scale rule's
+# (exponent bias, switch point of frexp's mantissa, lower and upper clamp of e)
+_MX_SR_FORMAT = {32: (3, 121, 8, 0.875, -117, 120), 16: (1, 127, 2, 0.75, -125, 126)}
+
+
+def _mx_sr_mul(x: torch.Tensor, c: int) -> torch.Tensor:
+    """x * c mod 2^32 for 0 <= x < 2^32, without leaving int64."""
+    return (x * (c & 0xFFFF) + (((x * (c >> 16)) & 0xFFFF) << 16)) & _M32
+
+
+def _mx_sr_mix(x: torch.Tensor) -> torch.Tensor:
+    x = x ^ (x >> 16)
+    x = _mx_sr_mul(x, 0x7FEB352D)
+    x = x ^ (x >> 15)
+    x = _mx_sr_mul(x, 0x846CA68B)
+    return x ^ (x >> 16)
+
+
+def mx_sr_key(seed: int, stream: int = 0) -> int:
+    """The 32-bit key of a stochastic call from its 64-bit seed and its 32-bit stream."""
+    def mix(v):
+        return int(_mx_sr_mix(torch.tensor(v & _M32, dtype=torch.int64)))
+    return mix(mix(mix((seed & _M32) ^ 0x9E3779B9) + (seed >> 32)) + stream)
+
+
+def _mx_sr_words(key: int, first: int, count: int) -> torch.Tensor:
+    """The words of the element indices first .. first + count - 1 (below 2^64), as int64 in [0, 2^32)."""
+    l = (first & _M32) + torch.arange(count, dtype=torch.int64)
+    h = (first >> 32) + (l >> 32)
+    kh = torch.where(h == 0, torch.full_like(h, key), _mx_sr_mix((key + h) & _M32))
+    return _mx_sr_mix((l & _M32) ^ kh)
+
+
+def _mx_sr_quantize_blocks(xb: torch.Tensor, u: torch.Tensor, pb: int):
+    """(blocks, 32) f32 and (blocks, 32) words -> (payload, scale bytes): the contract's Q with the payload
+    rounded stochastically. The scale is the nearest path's; the code of |s| is that of the grid point below
+    it plus one where u < T, T = floor(t 2^32), read off the f32 bits of s."""
+    mb, fmin, bias, switch, emin, emax = _MX_SR_FORMAT[pb]
+    amax = xb.abs().amax(dim=1)
+    special = ~torch.isfinite(xb).all(dim=1)
+    zero = (amax == 0) & ~special
+    m, ex = torch.frexp(torch.where(special | zero, torch.ones_like(amax), amax))
+    e = ((ex.to(torch.int64) - 1) - bias + (m > switch).to(torch.int64)).clamp(emin, emax)
+    e[zero] = 0
+    bits = (xb * _mx_exp2(-e)[:, None]).view(torch.int32).to(torch.int64) & _M32  # one f32 product
+    a = bits & 0x7FFFFFFF
+    field, mant = a >> 23, (a & 0x7FFFFF) | 0x800000
+    normal = field >= fmin
+    sh = 23 - mb + (fmin - field).clamp(0, 40)
+    lo = torch.where(normal, (field - fmin) << mb, torch.zeros_like(a)) + (mant >> sh)
+    thr = ((mant & ((torch.ones_like(sh) << sh) - 1)) << 32) >> sh
+    code = (lo + (u < thr).to(torch.int64)) | ((bits >> 31) << (7 if pb == 32 else 3))
+    code[special | zero] = 0
+    code = code.to(torch.uint8)
+    q = code if pb == 32 else (code[:, 0::2] | (code[:, 1::2] << 4)).contiguous()
+    s = (e + 127).to(torch.uint8)
+    s[special] = 255
+    return q, s
+
+
 def _mx_blocks_fns(wire: str, who: str):
     """(payload bytes per block, Q, D) of a format."""
     pb = _mx_payload(wire, who)
@@ -420,14 +525,22 @@ def _mx_feed_back(v: torch.Tensor, d: torch.Tensor, residual: torch.Tensor) -> N
 
 
 def mx_quantize_reference(x: torch.Tensor, world: int = 1, *, wire: str = "mxfp8_e4m3",
-                          residual: torch.Tensor | None = None) -> torch.Tensor:
+                          residual: torch.Tensor | None = None, rounding: str = "nearest", seed: int = 0,
+                          stream: int = 0, index_offset: int = 0) -> torch.Tensor:
     """Plain-PyTorch :func:`mx_quantize` on a CPU tensor, bit for bit the documented contract (with
-    ``residual``: the contract of "Error feedback", the residual updated in place)."""
+    ``residual``: the contract of "Error feedback", the residual updated in place; with
+    ``rounding="stochastic"``: the contract of "Stochastic rounding")."""
     _mx_check_dtype(x.dtype, "mx_quantize_reference")
-    _, Q, D = _mx_blocks_fns(wire, "mx_quantize_reference")
+    pb, Q, D = _mx_blocks_fns(wire, "mx_quantize_reference")
     world = max(1, int(world))
     flat = x.detach().reshape(-1).to(torch.float32)
     n = flat.numel()
+    if _mx_check_rounding(rounding, seed, stream, index_offset, n, residual, "mx_quantize_reference"):
+        total = mx_chunk_blocks(n, world, wire=wire) * world
+        xb = torch.zeros(total * MX_BLOCK, dtype=torch.float32)
+        xb[:n] = flat
+        u = _mx_sr_words(mx_sr_key(seed, stream), index_offset, total * MX_BLOCK)
+        return _mx_join(*_mx_sr_quantize_blocks(xb.view(total, MX_BLOCK), u.view(total, MX_BLOCK), pb), world)
     if residual is not None:
         _mx_check_residual(residual, n, x.device, "mx_quantize_reference")
         flat = flat + residual.detach().view(-1)
@@ -441,8 +554,10 @@ def mx_quantize_reference(x: torch.Tensor, world: int = 1, *, wire: str = "mxfp8
 
 
 def mx_reduce_reference(w: torch.Tensor, /, nsrc: int, op: str = "sum", *, wire: str = "mxfp8_e4m3",
-                        residual: torch.Tensor | None = None) -> torch.Tensor:
-    """Plain-PyTorch :func:`mx_reduce` on a CPU wire (``residual``: updated in place)."""
+                        residual: torch.Tensor | None = None, rounding: str = "nearest", seed: int = 0,
+                        stream: int = 0) -> torch.Tensor:
+    """Plain-PyTorch :func:`mx_reduce` on a CPU wire (``residual``: updated in place; ``rounding``, ``seed``,
+    ``stream``: as in :func:`mx_reduce`)."""
     if op not in ("sum", "avg"):
         raise ValueError(f"mx_reduce_reference: op must be 'sum' or 'avg', got {op!r}")
     pb, Q, D = _mx_blocks_fns(wire, "mx_reduce_reference")
@@ -454,6 +569,9 @@ def mx_reduce_reference(w: torch.Tensor, /, nsrc: int, op: str = "sum", *, wire:
         acc = acc + d[r]
     if op == "avg":
         acc = acc / torch.tensor(float(nsrc), dtype=torch.float32)
+    if _mx_check_rounding(rounding, seed, stream, 0, 0, residual, "mx_reduce_reference"):
+        u = _mx_sr_words(mx_sr_key(seed, stream), 0, cb * MX_BLOCK).view(cb, MX_BLOCK)
+        return _mx_join(*_mx_sr_quantize_blocks(acc, u, pb), 1)
     if residual is None:
         return _mx_join(*Q(acc), 1)
     _mx_check_residual(residual, cb * MX_BLOCK, w.device, "mx_reduce_reference")
@@ -477,12 +595,19 @@ def mx_dequantize_reference(w: torch.Tensor, /, numel: int, dtype: torch.dtype =
 
 
 def mx_quantize_shards_reference(x: torch.Tensor, world: int, *, wire: str = "mxfp8_e4m3",
-                                 residual: torch.Tensor | None = None) -> torch.Tensor:
-    """Plain-PyTorch :func:`mx_quantize_shards` on a CPU tensor (``residual``: updated in place)."""
+                                 residual: torch.Tensor | None = None, rounding: str = "nearest", seed: int = 0,
+                                 stream: int = 0, index_offset: int = 0) -> torch.Tensor:
+    """Plain-PyTorch :func:`mx_quantize_shards` on a CPU tensor (``residual``: updated in place; ``rounding``,
+    ``seed``, ``stream``, ``index_offset``: as in :func:`mx_quantize_shards`)."""
     _mx_check_dtype(x.dtype, "mx_quantize_shards_reference")
     _mx_payload(wire, "mx_quantize_shards_reference")
     m = _mx_check_shards(x.numel(), world, "mx_quantize_shards_reference")
     flat = x.detach().reshape(-1)
+    if _mx_check_rounding(rounding, seed, stream, index_offset, flat.numel(), residual,
+                          "mx_quantize_shards_reference"):
+        return torch.cat([mx_quantize_reference(flat[r * m:(r + 1) * m], 1, wire=wire, rounding=rounding, seed=seed,
+                                                stream=stream, index_offset=index_offset + r * m)
+                          for r in range(int(world))])
     if residual is None:
         return torch.cat([mx_quantize_reference(flat[r * m:(r + 1) * m], 1, wire=wire) for r in range(int(world))])
     _mx_check_residual(residual, flat.numel(), x.device, "mx_quantize_shards_reference")
@@ -530,7 +655,8 @@ def mx_fold_reference(w: torch.Tensor, /, nsrc: int, numel: int, dtype: torch.dt
 
 
 __all__ = ["reduce_nway", "reduce_nway_reference", "multi_copy", "pack", "unpack",
-           "MX_WIRES", "mx_quantize", "mx_reduce", "mx_dequantize", "mx_chunk_blocks", "mx_wire_bytes",
+           "MX_WIRES", "MX_ROUNDINGS", "mx_sr_key",
+           "mx_quantize", "mx_reduce", "mx_dequantize", "mx_chunk_blocks", "mx_wire_bytes",
            "mx_owner_residual_numel",
            "mx_quantize_reference", "mx_reduce_reference", "mx_dequantize_reference",
            "mx_shard_blocks", "mx_shard_wire_bytes", "mx_quantize_shards", "mx_dequantize_shards", "mx_fold",

@@ -30,6 +30,16 @@ all-gather") use the shard layout -- one chunk per shard, blocks counted from th
 The fold's result stays on its owner, so it is not quantized again: one quantization per
 contribution. A reduce-scatter moves ``33/32 * (W-1) * m`` bytes per rank instead of ``4 * (W-1) * m``
 for f32 (3.9x fewer, 1.94x for bf16), a gather of bf16 shards 1.94x fewer.
+
+Every quantizer rounds to nearest unless told otherwise, which biases an element that rounds the same
+way at every step. The two remedies are alternatives (docs/collectives.md "Error feedback", "Stochastic
+rounding"): ``residual=`` carries what was dropped to the next call, at 4 bytes of state per element;
+``rounding="stochastic"`` with a ``seed=`` rounds up or down with the probability of the distance, so the
+expected value of what is sent is the input, with no state and the bytes of the plain kernels, at
+twice the worst-case error of one call. Rank ``r`` draws its words from stream ``2 r`` (its contribution)
+and ``2 r + 1`` (the chunk it requantizes), so ranks are independent even with one seed; varying the seed
+from call to call is the caller's job (``GradBucketer`` and ``ShardedOptimizer`` do it). Gradients are the
+intended use. Both are properties of the local kernels: the wire and the protocol do not change.
 """
 from __future__ import annotations
 
@@ -80,18 +90,41 @@ def _sequence(tensor, opn, group, world, quantize, reduce, dequantize):
     dequantize(wire, n, world)
 
 
-def _run_gpu(tensor, opn, group, world, wire, residual=None, owner_residual=None):
-    _sequence(tensor, opn, group, world, lambda x, W: ops.mx_quantize(x, W, wire=wire, residual=residual),
-              lambda w, W, o: ops.mx_reduce(w, W, o, wire=wire, residual=owner_residual),
+def _run_gpu(tensor, opn, group, world, wire, residual=None, owner_residual=None, sr=({}, {})):
+    _sequence(tensor, opn, group, world, lambda x, W: ops.mx_quantize(x, W, wire=wire, residual=residual, **sr[0]),
+              lambda w, W, o: ops.mx_reduce(w, W, o, wire=wire, residual=owner_residual, **sr[1]),
               lambda w, n, W: ops.mx_dequantize(w, n, tensor.dtype, W, out=tensor, wire=wire))
 
 
-def _run_cpu(tensor, opn, group, world, wire, residual=None, owner_residual=None):
+def _run_cpu(tensor, opn, group, world, wire, residual=None, owner_residual=None, sr=({}, {})):
     def store(w, n, W):
         tensor.copy_(ops.mx_dequantize_reference(w, n, tensor.dtype, W, wire=wire).view_as(tensor))
 
-    _sequence(tensor, opn, group, world, lambda x, W: ops.mx_quantize_reference(x, W, wire=wire, residual=residual),
-              lambda w, W, o: ops.mx_reduce_reference(w, W, o, wire=wire, residual=owner_residual), store)
+    _sequence(tensor, opn, group, world,
+              lambda x, W: ops.mx_quantize_reference(x, W, wire=wire, residual=residual, **sr[0]),
+              lambda w, W, o: ops.mx_reduce_reference(w, W, o, wire=wire, residual=owner_residual, **sr[1]), store)
+
+
+ROUNDINGS = ("nearest", "stochastic")
+
+
+def _rounding_args(who, rounding, seed, group, residuals=()):
+    """The rounding arguments of a collective, checked before any communication. Returns the keywords of this
+    rank's quantization and of its requantization: none for ``"nearest"`` (the plain calls), else the seed
+    with the streams ``2 rank`` and ``2 rank + 1``."""
+    if not isinstance(rounding, str) or rounding not in ROUNDINGS:
+        raise ValueError(f"{who}: unknown rounding {rounding!r} (supported: {', '.join(ROUNDINGS)})")
+    if isinstance(seed, bool) or not isinstance(seed, int):
+        raise TypeError(f"{who}: seed must be an int, got {type(seed).__name__}")
+    if not 0 <= seed < 1 << 64:
+        raise ValueError(f"{who}: seed must be in [0, 2^64), got {seed}")
+    if rounding == "nearest":
+        return {}, {}
+    if any(r is not None for r in residuals):
+        raise ValueError(f"{who}: rounding='stochastic' and a residual are alternatives, not both")
+    rank = dist.get_rank(group)
+    return (dict(rounding=rounding, seed=seed, stream=2 * rank),
+            dict(rounding=rounding, seed=seed, stream=2 * rank + 1))
 
 
 def _check_residual(who, name, res, numel, device):
@@ -114,7 +147,7 @@ def _check_residual(who, name, res, numel, device):
 
 def all_reduce_compressed(tensor: torch.Tensor, op=dist.ReduceOp.SUM, group=None, wire: str = "mxfp8_e4m3",
                           async_op: bool = False, *, residual: torch.Tensor | None = None,
-                          owner_residual: torch.Tensor | None = None):
+                          owner_residual: torch.Tensor | None = None, rounding: str = "nearest", seed: int = 0):
     """In-place SUM / AVG all-reduce of ``tensor`` (float32, bfloat16 or float16) over the wire
     format ``wire`` (``mxfp8_e4m3`` or ``mxfp4_e2m1``). Every rank ends with the same bits; at world 1 the tensor is left
     unchanged (not even quantized). GPU tensors run on the current stream; with ``async_op=True``
@@ -129,7 +162,13 @@ def all_reduce_compressed(tensor: torch.Tensor, op=dist.ReduceOp.SUM, group=None
     elements) does the same for the requantization of the chunk this rank owns. Both are updated in place,
     by the kernel that quantizes; either may be given alone, and every rank must make the same choice. Carry
     them from call to call: the sum of what is sent then tracks the sum of the inputs to within one
-    bounded residual. At world 1 they are left untouched, like the tensor."""
+    bounded residual. At world 1 they are left untouched, like the tensor.
+
+    Stochastic rounding (docs/collectives.md "Stochastic rounding"): ``rounding="stochastic"`` rounds this
+    rank's contribution by the words of ``(seed, 2 rank)`` and the chunk it owns by those of ``(seed,
+    2 rank + 1)``; the expected value of either quantization is its input. Ranks may use any seeds (their
+    errors are independent either way) and still end with the same bits; the same seeds give the same
+    bits again, so pass a new seed with every call. Not together with a residual (``ValueError``)."""
     opn = _op_name(op)
     if opn is None:
         raise ValueError(f"all_reduce_compressed: only ReduceOp.SUM and ReduceOp.AVG are supported, got {op}")
@@ -141,16 +180,17 @@ def all_reduce_compressed(tensor: torch.Tensor, op=dist.ReduceOp.SUM, group=None
     _check_residual("all_reduce_compressed", "residual", residual, tensor.numel(), tensor.device)
     _check_residual("all_reduce_compressed", "owner_residual", owner_residual,
                     ops.mx_owner_residual_numel(tensor.numel(), world, wire=wire), tensor.device)
+    sr = _rounding_args("all_reduce_compressed", rounding, seed, group, (residual, owner_residual))
     if world == 1 or tensor.numel() == 0:
         return CompressedWork() if async_op else None
     if not tensor.is_cuda:
         with torch.no_grad():
-            _run_cpu(tensor, opn, group, world, wire, residual, owner_residual)
+            _run_cpu(tensor, opn, group, world, wire, residual, owner_residual, sr)
         return CompressedWork() if async_op else None
     if world > MAX_GPU_WORLD:
         raise ValueError(f"all_reduce_compressed: GPU groups of up to {MAX_GPU_WORLD} ranks, got {world}")
     held = tuple(t for t in (tensor, residual, owner_residual) if t is not None)
-    return _issue_gpu(lambda: _run_gpu(tensor, opn, group, world, wire, residual, owner_residual), held, async_op)
+    return _issue_gpu(lambda: _run_gpu(tensor, opn, group, world, wire, residual, owner_residual, sr), held, async_op)
 
 
 def _issue_gpu(run, tensors, async_op):
@@ -212,7 +252,7 @@ def _done(async_op):
 
 def reduce_scatter_compressed(output: torch.Tensor, input: torch.Tensor, op=dist.ReduceOp.SUM, group=None,
                               wire: str = "mxfp8_e4m3", async_op: bool = False, *,
-                              residual: torch.Tensor | None = None):
+                              residual: torch.Tensor | None = None, rounding: str = "nearest", seed: int = 0):
     """SUM / AVG reduce-scatter of ``input`` (``W * m`` elements; f32, bf16 or f16) into ``output`` (``m``
     elements) over the wire format ``wire``: rank ``k`` ends with the f32 fold, in rank order, of every
     rank's quantized shard ``k`` (its own included), rounded once to the dtype. The fold is not
@@ -221,13 +261,18 @@ def reduce_scatter_compressed(output: torch.Tensor, input: torch.Tensor, op=dist
 
     ``residual`` (float32, ``input.numel()`` elements; error feedback as in :func:`all_reduce_compressed`) is
     added to ``input`` before it is quantized and left holding what the quantization dropped; ``input`` itself is
-    not modified. The fold is not quantized, so there is no owner residual. Untouched at world 1."""
+    not modified. The fold is not quantized, so there is no owner residual. Untouched at world 1.
+
+    ``rounding="stochastic"`` with ``seed`` (as in :func:`all_reduce_compressed`): this rank's shards are
+    rounded by the words of ``(seed, 2 rank)``, an element by its index in ``input``; the one quantization
+    of each contribution is then unbiased and the W errors of a sum are independent. Not with ``residual``."""
     who = "reduce_scatter_compressed"
     opn = _op_name(op)
     if opn is None:
         raise ValueError(f"{who}: only ReduceOp.SUM and ReduceOp.AVG are supported, got {op}")
     world = _check_pair(who, output, input, wire, group, input, output)
     _check_residual(who, "residual", residual, input.numel(), input.device)
+    sr, _ = _rounding_args(who, rounding, seed, group, (residual,))
     m = output.numel()
     if m == 0:
         return _done(async_op)
@@ -237,14 +282,14 @@ def reduce_scatter_compressed(output: torch.Tensor, input: torch.Tensor, op=dist
         return _done(async_op)
     if not input.is_cuda:
         with torch.no_grad():
-            w = ops.mx_quantize_shards_reference(input, world, wire=wire, residual=residual)
+            w = ops.mx_quantize_shards_reference(input, world, wire=wire, residual=residual, **sr)
             recv = torch.empty_like(w)
             dist.all_to_all_single(recv, w, group=group)
             output.copy_(ops.mx_fold_reference(recv, world, m, output.dtype, opn, wire=wire).view_as(output))
         return _done(async_op)
 
     def run():
-        w = ops.mx_quantize_shards(input, world, wire=wire, residual=residual)
+        w = ops.mx_quantize_shards(input, world, wire=wire, residual=residual, **sr)
         recv = torch.empty_like(w)
         dist.all_to_all_single(recv, w, group=group)  # chunk r of every rank -> rank r, in rank order
         ops.mx_fold(recv, world, m, output.dtype, opn, out=output, wire=wire)
@@ -253,13 +298,19 @@ def reduce_scatter_compressed(output: torch.Tensor, input: torch.Tensor, op=dist
 
 
 def all_gather_compressed(output: torch.Tensor, input: torch.Tensor, group=None, wire: str = "mxfp8_e4m3",
-                          async_op: bool = False):
+                          async_op: bool = False, *, rounding: str = "nearest", seed: int = 0):
     """All-gather of ``input`` (``m`` elements; f32, bf16 or f16) into ``output`` (``W * m`` elements)
     over the wire format ``wire``: every rank ends with the same bits, the dequantized wire of every
     rank's shard -- its own slot included. At world 1 ``input`` is copied bit for bit. Streams and
-    ``async_op`` as in :func:`all_reduce_compressed`."""
+    ``async_op`` as in :func:`all_reduce_compressed`.
+
+    ``rounding="stochastic"`` with ``seed``: accepted because the gather shares the quantizer -- this rank's
+    shard is rounded by the words of ``(seed, 2 rank)``, and every rank still ends with the same bits. It is
+    meant for gradients; values that are not summed or averaged afterwards (parameters) gain nothing
+    from it and pay twice the worst-case error."""
     who = "all_gather_compressed"
     world = _check_pair(who, output, input, wire, group, output, input)
+    sr, _ = _rounding_args(who, rounding, seed, group)
     m = input.numel()
     if m == 0:
         return _done(async_op)
@@ -269,14 +320,14 @@ def all_gather_compressed(output: torch.Tensor, input: torch.Tensor, group=None,
         return _done(async_op)
     if not input.is_cuda:
         with torch.no_grad():
-            mine = ops.mx_quantize_reference(input, 1, wire=wire)
+            mine = ops.mx_quantize_reference(input, 1, wire=wire, **sr)
             every = torch.empty(mine.numel() * world, dtype=torch.uint8)
             dist.all_gather_into_tensor(every, mine, group=group)
             output.copy_(ops.mx_dequantize_shards_reference(every, m, output.dtype, world, wire=wire).view_as(output))
         return _done(async_op)
 
     def run():
-        mine = ops.mx_quantize(input, 1, wire=wire)
+        mine = ops.mx_quantize(input, 1, wire=wire, **sr)
         every = torch.empty(mine.numel() * world, dtype=torch.uint8, device=mine.device)
         dist.all_gather_into_tensor(every, mine, group=group)
         ops.mx_dequantize_shards(every, m, output.dtype, world, out=output, wire=wire)

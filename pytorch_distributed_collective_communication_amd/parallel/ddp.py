@@ -33,7 +33,12 @@ contract, MI355X-first:
   requantizes -- and adds it to the next step's, so the quantization error cancels over steps instead
   of biasing every step the same way (docs/collectives.md "Error feedback"). The residuals are f32:
   4 bytes per gradient element, plus ``4 * 32 * cb`` bytes per bucket (``cb =
-  ops.mx_chunk_blocks(bucket elements, world)``, about ``4 / world`` bytes per element more).
+  ops.mx_chunk_blocks(bucket elements, world)``, about ``4 / world`` bytes per element more);
+* ``rounding="stochastic"`` (with a wire, instead of error feedback): every quantization of a bucket
+  rounds up or down with the probability of the distance, so what is sent is right on average and the
+  error of a step is independent of the last one's, with no state at all (docs/collectives.md
+  "Stochastic rounding"). Bucket ``b`` of synchronised step ``n`` uses the seed
+  ``(seed + n * nbuckets + b) mod 2^64``.
 
 ``broadcast_parameters`` and ``scatter_batch`` cover the other two uses.
 torch's own ``DistributedDataParallel`` also runs unchanged on this backend.
@@ -87,10 +92,28 @@ class GradBucketer:
     ``flat.numel()`` elements and an owner residual of ``ops.mx_owner_residual_numel(flat.numel(), world)``
     and passes both to every ``all_reduce_compressed``. Memory: 4 bytes per gradient element plus
     ``4 * 32 * cb`` bytes per bucket. Backward passes inside ``no_sync()`` send nothing and leave the
-    residuals alone. ``residuals`` lists them, ``reset_error_feedback()`` zeroes them."""
+    residuals alone. ``residuals`` lists them, ``reset_error_feedback()`` zeroes them.
+
+    ``rounding="stochastic"`` (needs ``wire``, excludes ``error_feedback``): every ``all_reduce_compressed``
+    rounds stochastically, bucket ``b`` of synchronised step ``n`` (``rounding_step``, counted by
+    :meth:`finish`) with the seed ``(seed + n * len(buckets) + b) mod 2^64``. A backward inside
+    ``no_sync()`` is no step."""
 
     def __init__(self, module: torch.nn.Module, group=None, bucket_bytes: int = 256 << 20,
-                 average: bool = True, wire: str | None = None, error_feedback: bool = False):
+                 average: bool = True, wire: str | None = None, error_feedback: bool = False,
+                 rounding: str = "nearest", seed: int = 0):
+        from .compressed import ROUNDINGS
+
+        if rounding not in ROUNDINGS:
+            raise ValueError(f"GradBucketer: unknown rounding {rounding!r} (supported: {', '.join(ROUNDINGS)})")
+        if isinstance(seed, bool) or not isinstance(seed, int) or not 0 <= seed < 1 << 64:
+            raise ValueError(f"GradBucketer: seed must be an int in [0, 2^64), got {seed!r}")
+        if rounding == "stochastic" and wire is None:
+            raise ValueError("GradBucketer: rounding='stochastic' needs a compressed wire (wire=None sends exact "
+                             "gradients: nothing is rounded)")
+        if rounding == "stochastic" and error_feedback:
+            raise ValueError("GradBucketer: rounding='stochastic' and error_feedback=True are alternatives, not both")
+        self.rounding, self.seed, self.rounding_step = rounding, seed, 0
         if error_feedback and wire is None:
             raise ValueError("GradBucketer: error_feedback=True needs a compressed wire (wire=None sends exact "
                              "gradients: there is no quantization error to feed back)")
@@ -175,6 +198,11 @@ class GradBucketer:
         if self.wire is not None:
             from .compressed import all_reduce_compressed
 
+            if self.rounding == "stochastic":
+                nb = len(self.buckets)
+                seed = (self.seed + self.rounding_step * nb + self.buckets.index(b)) % (1 << 64)
+                return all_reduce_compressed(b.flat, dist.ReduceOp.AVG, group=self.group, wire=self.wire,
+                                             async_op=True, rounding="stochastic", seed=seed)
             return all_reduce_compressed(b.flat, dist.ReduceOp.AVG, group=self.group, wire=self.wire, async_op=True,
                                          residual=b.residual, owner_residual=b.owner_residual)
         return dist.all_reduce(b.flat, op=self._op, group=self.group, async_op=True)
@@ -194,6 +222,7 @@ class GradBucketer:
             if self.average and self.world > 1 and not self._fused_avg:
                 b.flat.div_(self.world)
             _unpack(b)
+        self.rounding_step += 1
         self._reset()
 
     @property

@@ -51,6 +51,12 @@ steps. The fold is not quantized again, so there is no owner residual; ``param_w
 (parameters are not accumulated). ``state_dict()`` saves the residuals, ``load_state_dict()`` restores
 them (a checkpoint without them loads as zeros).
 
+``grad_rounding="stochastic"`` (with a ``grad_wire``, instead of ``grad_error_feedback``): the
+reduce-scatters round this rank's gradients stochastically (docs/collectives.md "Stochastic rounding"):
+unbiased, no state but a step counter. Gradient bucket ``b`` (counted over all spaces) of synchronised
+step ``n`` uses the seed ``(grad_seed + n * nbuckets + b) mod 2^64``; ``state_dict()`` saves ``n`` as
+``grad_rounding_step`` (a checkpoint without it loads as 0). ``param_wire`` stays nearest.
+
 ``state_dict()`` / ``load_state_dict()`` save and restore this rank's shard
 (sharded checkpoint: every rank writes its own file) and re-gather the
 parameters on load.
@@ -173,15 +179,31 @@ class ShardedOptimizer:
     ``"mxfp8_e4m3"`` or ``"mxfp4_e2m1"``, each on its own) pick the wire of the reduce-scatters / the all-gathers of
     float32, bfloat16 and float16 parameters. ``grad_error_feedback=True`` (needs ``grad_wire``) carries the
     quantization error of this rank's gradients from step to step in an f32 residual, 4 bytes per gradient
-    element, saved by :meth:`state_dict`. One parameter group: the inner optimizer's hyper-parameters
+    element, saved by :meth:`state_dict`. ``grad_rounding="stochastic"`` with ``grad_seed`` (needs ``grad_wire``,
+    excludes ``grad_error_feedback``) rounds the gradients on the wire stochastically, a fresh seed per bucket
+    and step; :meth:`state_dict` saves the step counter. One parameter group: the inner optimizer's hyper-parameters
     come from ``**opt_kwargs``.
     """
 
     def __init__(self, params: Iterable[torch.nn.Parameter], optimizer_cls=torch.optim.SGD, group=None,
                  master_dtype: torch.dtype = torch.float32, broadcast_from: int | None = 0,
                  bucket_bytes: int = 256 << 20, overlap: bool = True, grad_wire: str | None = None,
-                 param_wire: str | None = None, grad_error_feedback: bool = False, **opt_kwargs):
-        from .compressed import WIRES
+                 param_wire: str | None = None, grad_error_feedback: bool = False, grad_rounding: str = "nearest",
+                 grad_seed: int = 0, **opt_kwargs):
+        from .compressed import ROUNDINGS, WIRES
+
+        if grad_rounding not in ROUNDINGS:
+            raise ValueError(f"ShardedOptimizer: unknown grad_rounding {grad_rounding!r} "
+                             f"(supported: {', '.join(ROUNDINGS)})")
+        if isinstance(grad_seed, bool) or not isinstance(grad_seed, int) or not 0 <= grad_seed < 1 << 64:
+            raise ValueError(f"ShardedOptimizer: grad_seed must be an int in [0, 2^64), got {grad_seed!r}")
+        if grad_rounding == "stochastic" and grad_wire is None:
+            raise ValueError("ShardedOptimizer: grad_rounding='stochastic' needs a grad_wire (grad_wire=None sends "
+                             "exact gradients: nothing is rounded)")
+        if grad_rounding == "stochastic" and grad_error_feedback:
+            raise ValueError("ShardedOptimizer: grad_rounding='stochastic' and grad_error_feedback=True are "
+                             "alternatives, not both")
+        self.grad_rounding, self.grad_seed, self.grad_rounding_step = grad_rounding, grad_seed, 0
 
         if grad_error_feedback and grad_wire is None:
             raise ValueError("ShardedOptimizer: grad_error_feedback=True needs a grad_wire (grad_wire=None sends "
@@ -208,6 +230,7 @@ class ShardedOptimizer:
             by_key.setdefault((str(p.device), p.dtype), []).append(p)
         self.spaces = [_FlatSpace(ps, self.world, self.rank, master_dtype, bucket_bytes) for ps in by_key.values()]
         self._space_of = {id(p): s for s in self.spaces for p in s.params}
+        self._bucket_no = {id(b): i for i, b in enumerate(b for s in self.spaces for b in s.buckets)}
         for s in self.spaces:  # the error-feedback residual of the space's flat gradient, or None
             s.grad_residual = (torch.zeros(s.padded, dtype=torch.float32, device=s.device)
                                if self.grad_error_feedback and self._on_wire(s, grad_wire) else None)
@@ -262,6 +285,14 @@ class ShardedOptimizer:
         if self._on_wire(s, self.grad_wire):
             from .compressed import reduce_scatter_compressed
 
+            if self.grad_rounding == "stochastic":
+                seed = (self.grad_seed + self.grad_rounding_step * len(self._bucket_no)
+                        + self._bucket_no[id(b)]) % (1 << 64)
+                b.work = reduce_scatter_compressed(s.grad_shard[b.soff:b.soff + b.shard],
+                                                   s.grad[b.off:b.off + b.padded], op=dist.ReduceOp.AVG,
+                                                   group=self.group, wire=self.grad_wire, async_op=True,
+                                                   rounding="stochastic", seed=seed)
+                return
             b.work = reduce_scatter_compressed(s.grad_shard[b.soff:b.soff + b.shard], s.grad[b.off:b.off + b.padded],
                                                op=dist.ReduceOp.AVG, group=self.group, wire=self.grad_wire,
                                                async_op=True,
@@ -307,6 +338,7 @@ class ShardedOptimizer:
             if not self._avg and self.world > 1 and not self._on_wire(s, self.grad_wire):  # (a wire divides inside)
                 g = g / self.world
             s.master.grad = g
+        self.grad_rounding_step += 1
         self.inner.step()
         self._gather()
 
@@ -347,6 +379,8 @@ class ShardedOptimizer:
                 self._fence(s)
         extra = {"grad_residual": [None if s.grad_residual is None else s.grad_residual.detach().cpu().clone()
                                    for s in self.spaces]} if self.grad_error_feedback else {}
+        if self.grad_rounding == "stochastic":
+            extra["grad_rounding_step"] = self.grad_rounding_step
         return {
             **extra,
             "world": self.world,
@@ -366,6 +400,7 @@ class ShardedOptimizer:
         for s, m in zip(self.spaces, sd["master"]):
             s.master.copy_(m)
         self.inner.load_state_dict(sd["inner"])
+        self.grad_rounding_step = int(sd.get("grad_rounding_step", 0))  # (a checkpoint without it: 0)
         saved = sd.get("grad_residual") or [None] * len(self.spaces)  # (an older checkpoint: zeros)
         for s, r in zip(self.spaces, saved):
             if s.grad_residual is None:

@@ -1,11 +1,11 @@
-"""Registers and scratch of the error-feedback kernels (csrc/kernels/mx_wire.hip), from the compiler.
+"""Registers and scratch of the stochastic-rounding kernels (csrc/kernels/mx_wire.hip), from the compiler.
 
 Compiles mx_wire.hip for gfx950 with ``-Rpass-analysis=kernel-resource-usage`` (no GPU needed) and
-writes one line per instantiation of ``k_mx_quantize`` / ``k_mx_reduce`` -- the error-feedback ones
-and, for comparison, the plain ones -- to profiles/mx/mx_ef_resources.txt. Exits non-zero if an
-error-feedback instantiation uses scratch memory.
+writes one line per instantiation of ``k_mx_quantize`` / ``k_mx_reduce`` -- the stochastic-rounding
+ones and, for comparison, the plain ones -- to profiles/mx/mx_sr_resources.txt, with the LDS bytes of
+each. Exits non-zero if a stochastic-rounding instantiation uses scratch memory or LDS.
 
-    python scripts/mx_ef_resources.py [--out profiles/mx/mx_ef_resources.txt]
+    python scripts/mx_sr_resources.py [--out profiles/mx/mx_sr_resources.txt]
 """
 import argparse
 import os
@@ -27,7 +27,7 @@ REDUCE = re.compile(r"k_mx_reduceILNS\w+?8MxFormatE(\d)ELi(\d+)ELb(\d)ELb(\d)ELb
 
 def main():
     ap = argparse.ArgumentParser(description=__doc__)
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "mx", "mx_ef_resources.txt"))
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "mx", "mx_sr_resources.txt"))
     a = ap.parse_args()
     hipcc = shutil.which("hipcc") or os.path.join(os.environ.get("ROCM_PATH", "/opt/rocm"), "bin", "hipcc")
     with tempfile.TemporaryDirectory() as tmp:
@@ -61,27 +61,27 @@ def main():
                 continue
             f, n, avg, ef, sr = m.groups()
             what = f"reduce {FMT[f]} nsrc={n} {'avg' if avg == '1' else 'sum'}"
-        if sr == "1":  # the stochastic-rounding instantiations: scripts/mx_sr_resources.py
+        if ef == "1":  # the error-feedback instantiations: scripts/mx_ef_resources.py
             continue
-        ef = ef == "1"
+        ef = sr == "1"
         rows.append((what, ef, k))
-        if ef and k.get("scratch", 0):
+        if ef and (k.get("scratch", 0) or k.get("lds", 0)):
             bad.append(what)
     rows.sort(key=lambda r: (r[0].split()[0], r[0], r[1]))
     os.makedirs(os.path.dirname(a.out), exist_ok=True)
     with open(a.out, "w") as f:
         f.write("# hipcc --offload-arch=gfx950 -O3 -Rpass-analysis=kernel-resource-usage, csrc/kernels/mx_wire.hip\n")
-        f.write("# (scripts/mx_ef_resources.py; compiler output, not a measurement). residual = the error-feedback\n")
-        f.write("# instantiation; scratch in bytes per lane; occupancy in waves per SIMD.\n")
-        f.write(f"{'kernel':<52} {'residual':>8} {'vgpr':>5} {'agpr':>5} {'sgpr':>5} {'scratch':>8} {'occupancy':>9}\n")
+        f.write("# (scripts/mx_sr_resources.py; compiler output, not a measurement). sr = the stochastic-rounding\n")
+        f.write("# instantiation; scratch in bytes per lane; lds in bytes per block; occupancy in waves per SIMD.\n")
+        f.write(f"{'kernel':<52} {'sr':>8} {'vgpr':>5} {'agpr':>5} {'sgpr':>5} {'scratch':>8} {'lds':>5} {'occupancy':>9}\n")
         for what, ef, k in rows:
             f.write(f"{what:<52} {'yes' if ef else 'no':>8} {k.get('vgpr', -1):>5} {k.get('agpr', -1):>5} "
-                    f"{k.get('sgpr', -1):>5} {k.get('scratch', -1):>8} {k.get('occupancy', -1):>9}\n")
+                    f"{k.get('sgpr', -1):>5} {k.get('scratch', -1):>8} {k.get('lds', -1):>5} {k.get('occupancy', -1):>9}\n")
         n_ef = sum(ef for _, ef, _ in rows)
-        f.write(f"# {n_ef} error-feedback instantiations, {len(bad)} of them with scratch\n")
-    print(f"{a.out}: {len(rows)} kernels, {n_ef} with a residual, {len(bad)} of those use scratch")
+        f.write(f"# {n_ef} stochastic-rounding instantiations, {len(bad)} of them with scratch or LDS\n")
+    print(f"{a.out}: {len(rows)} kernels, {n_ef} stochastic, {len(bad)} of those use scratch or LDS")
     if bad:
-        sys.exit("scratch in: " + ", ".join(bad))
+        sys.exit("scratch or LDS in: " + ", ".join(bad))
 
 
 if __name__ == "__main__":
