@@ -91,7 +91,7 @@ void multi_copy(const std::vector<at::Tensor>& srcs, const std::vector<at::Tenso
   TORCH_CHECK(e == hipSuccess, "multi_copy launch failed: ", hipGetErrorString(e));
 }
 
-// ---- block-scaled wires, mxfp8_e4m3 and mxfp4_e2m1 (kernels/mx_wire.hip). The kernels want contiguous, 16-byte aligned
+// ---- block-scaled wires, mxfp8_e4m3, mxfp4_e2m1 and mxfp6_e2m3 (kernels/mx_wire.hip). The kernels want contiguous, 16-byte aligned
 // buffers: any other tensor goes through a contiguous copy (inputs) or is filled from one (outputs).
 at::Tensor mx_in(const at::Tensor& t) {
   if (t.is_contiguous() && al16(t.data_ptr())) return t;
@@ -132,7 +132,8 @@ using pdcc::kern::MxFormat;
 MxFormat mx_format(const std::string& wire, const char* who) {
   if (wire == "mxfp8_e4m3") return MxFormat::FP8_E4M3;
   if (wire == "mxfp4_e2m1") return MxFormat::FP4_E2M1;
-  TORCH_CHECK_VALUE(false, who, ": unknown wire format '", wire, "' (supported: mxfp8_e4m3, mxfp4_e2m1)");
+  if (wire == "mxfp6_e2m3") return MxFormat::FP6_E2M3;
+  TORCH_CHECK_VALUE(false, who, ": unknown wire format '", wire, "' (supported: mxfp8_e4m3, mxfp4_e2m1, mxfp6_e2m3)");
   return MxFormat::FP8_E4M3;
 }
 
@@ -173,7 +174,7 @@ at::Tensor mx_reduce(const at::Tensor& wire, int nsrc, const std::string& op, co
   TORCH_CHECK(nsrc >= 1 && nsrc <= pdcc::kern::kMaxRanks, "mx_reduce: 1..8 sources");
   TORCH_CHECK_VALUE(op == "sum" || op == "avg", "mx_reduce: op must be 'sum' or 'avg', got '", op, "'");
   const int64_t chunk = wire.numel() / nsrc;
-  const int64_t bw = (int64_t)pdcc::kern::mx_block_wire(f);  // 33 or 17
+  const int64_t bw = (int64_t)pdcc::kern::mx_block_wire(f);  // 33, 17 or 25
   TORCH_CHECK(chunk > 0 && chunk * nsrc == wire.numel() && chunk % (bw * 16) == 0, "mx_reduce: ", wire.numel(),
               " bytes are not ", nsrc, " chunk wires (", bw, " bytes per block, blocks in groups of 16)");
   const size_t cb = (size_t)(chunk / bw);
@@ -442,7 +443,7 @@ PYBIND11_MODULE(_C, m) {
   m.def("mx_quantize", &mx_quantize, py::arg("x"), py::arg("world") = 1, py::arg("out") = py::none(),
         py::arg("fmt") = "mxfp8_e4m3", py::arg("residual") = py::none(), py::arg("sr") = false, py::arg("seed") = 0,
         py::arg("stream") = 0, py::arg("index_offset") = 0,
-        "tensor (f32 / bf16 / f16) -> mxfp8_e4m3 / mxfp4_e2m1 wire of `world` chunks, on the current stream; "
+        "tensor (f32 / bf16 / f16) -> mxfp8_e4m3 / mxfp4_e2m1 / mxfp6_e2m3 wire of `world` chunks, on the current stream; "
         "`residual`: one float per element of error feedback, added before and updated in place; `sr`: stochastic "
         "rounding by the words of (seed, stream, index_offset + element index)");
   m.def("mx_reduce", &mx_reduce, py::arg("wire"), py::arg("nsrc"), py::arg("op") = "sum", py::arg("out") = py::none(),
@@ -453,7 +454,7 @@ PYBIND11_MODULE(_C, m) {
         "words of (seed, stream, index in the chunk)");
   m.def("mx_dequantize", &mx_dequantize, py::arg("wire"), py::arg("world"), py::arg("out"),
         py::arg("fmt") = "mxfp8_e4m3",
-        "mxfp8_e4m3 / mxfp4_e2m1 wire of `world` chunks -> out (f32 / bf16 / f16), exactly out.numel() elements");
+        "mxfp8_e4m3 / mxfp4_e2m1 / mxfp6_e2m3 wire of `world` chunks -> out (f32 / bf16 / f16), exactly out.numel() elements");
   m.def("mx_quantize_shards", &mx_quantize_shards, py::arg("x"), py::arg("world"), py::arg("out") = py::none(),
         py::arg("fmt") = "mxfp8_e4m3", py::arg("residual") = py::none(), py::arg("sr") = false, py::arg("seed") = 0,
         py::arg("stream") = 0, py::arg("index_offset") = 0,

@@ -324,11 +324,12 @@ using IpcCall = IpcCallT<RawPtr>;
 size_t ipc_signal_bytes();
 hipError_t ipc_launch(const IpcView& view, const IpcCall& call, hipStream_t stream);
 
-// ---------------------------------------------------------------- block-scaled wires (mxfp8_e4m3, mxfp4_e2m1)
-// Layout: mx_layout.h; contract: docs/collectives.md "Compressed all-reduce" and "The `mxfp4_e2m1`
-// wire format". Single-GPU streaming kernels (mx_wire.hip). `wire` buffers and the tensors are 16-byte
+// ---------------------------------------------------------------- block-scaled wires (mxfp8_e4m3, mxfp4_e2m1, mxfp6_e2m3)
+// Layout: mx_layout.h; contract: docs/collectives.md "Compressed all-reduce", "The `mxfp4_e2m1`
+// wire format" and "The `mxfp6_e2m3` wire format". Single-GPU streaming kernels (mx_wire.hip). `wire` buffers and the tensors are 16-byte
 // aligned; `cb` (blocks per chunk) is a multiple of 16; `fmt` picks the payload (32 float8_e4m3fn
-// bytes or 16 bytes of e2m1 nibbles per block) and with it the chunk size (33 cb or 17 cb bytes).
+// bytes, 16 bytes of e2m1 nibbles or 24 bytes of 6-bit e2m3 codes per block) and with it the chunk size
+// (33 cb, 17 cb or 25 cb bytes).
 // Tensor (`t` in F32 / BF16 / F16, `numel` <= 32 cb nchunks elements) -> nchunks chunk wires. Every
 // block of every chunk is written (padding: scale 127, payload 0); nothing past src + numel is read.
 hipError_t mx_quantize(const void* src, size_t numel, DType t, void* wire, size_t cb, size_t nchunks,

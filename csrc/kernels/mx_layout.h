@@ -1,9 +1,10 @@
 // Layout of the block-scaled wire formats `mxfp8_e4m3` (docs/collectives.md, "Compressed
-// all-reduce") and `mxfp4_e2m1` ("The `mxfp4_e2m1` wire format"). Host and device, no HIP runtime call: the kernels (mx_wire.hip), the bindings and
+// all-reduce"), `mxfp4_e2m1` ("The `mxfp4_e2m1` wire format") and `mxfp6_e2m3` ("The `mxfp6_e2m3` wire
+// format"). Host and device, no HIP runtime call: the kernels (mx_wire.hip), the bindings and
 // tests/native/mx_layout_check.cpp all read the one definition.
 //
 // A block is 32 consecutive elements: 32 float8_e4m3fn payload bytes and one E8M0 scale byte (FP4:
-// 16 payload bytes; read 16 for every 32 payload bytes below). The
+// 16 payload bytes, FP6: 24; read 16 or 24 for every 32 payload bytes below). The
 // blocks of a tensor are dealt to `nchunks` chunks of `cb` blocks (one chunk per rank of an
 // all-reduce); a chunk on the wire is
 //     [32 * cb payload bytes][cb scale bytes]
@@ -37,16 +38,24 @@ constexpr size_t kMxBigChunk = size_t(1) << 20;  // from this chunk wire size on
 constexpr size_t kMxBigAlign = 4096;             // ... cb is a multiple of 4096 blocks (whole 4-KiB tiles)
 
 // The wire formats. They differ in the payload of a block only: 32 float8_e4m3fn bytes, or 16 bytes
-// of two e2m1 nibbles each (element 2j in the low nibble of byte j, element 2j + 1 in the high one).
+// of two e2m1 nibbles each (element 2j in the low nibble of byte j, element 2j + 1 in the high one),
+// or 24 bytes that are a little-endian stream of 32 e2m3 codes of 6 bits (element j in bits 6j .. 6j + 5
+// of the block's 192; bit n of the stream is bit n % 8 of byte n / 8).
 // The functions below without a format argument are the FP8 case of the ones that take one.
-enum class MxFormat : int { FP8_E4M3 = 0, FP4_E2M1 = 1 };
+enum class MxFormat : int { FP8_E4M3 = 0, FP4_E2M1 = 1, FP6_E2M3 = 2 };
 
 PDCC_MX_HD inline size_t mx_round_up(size_t x, size_t m) { return (x + m - 1) / m * m; }
 
 PDCC_MX_HD inline size_t mx_blocks(size_t numel) { return (numel + kMxBlock - 1) / kMxBlock; }
 
 // payload bytes and wire bytes (payload + one scale byte) of a block
-PDCC_MX_HD constexpr size_t mx_block_payload(MxFormat f) { return f == MxFormat::FP4_E2M1 ? 16 : 32; }
+PDCC_MX_HD constexpr size_t mx_block_payload(MxFormat f) {
+  switch (f) {
+    case MxFormat::FP4_E2M1: return 16;
+    case MxFormat::FP6_E2M3: return 24;
+    default: return 32;
+  }
+}
 PDCC_MX_HD constexpr size_t mx_block_wire(MxFormat f) { return mx_block_payload(f) + 1; }
 
 // blocks per chunk when `numel` elements are dealt to `world` chunks (at least one group of 16). The
@@ -86,7 +95,8 @@ PDCC_MX_HD inline size_t mx_shard_wire_bytes(size_t m, size_t world) {
   return mx_shard_wire_bytes(MxFormat::FP8_E4M3, m, world);
 }
 // wire byte of the payload of element i (of world * m; FP4: the byte that holds its nibble, the high
-// one for an odd position in the shard) and of the scale of its block
+// one for an odd position in the shard; FP6: the byte that holds the lowest bit of its code) and of the
+// scale of its block
 PDCC_MX_HD inline size_t mx_shard_payload_byte(MxFormat f, size_t m, size_t i) {
   const size_t r = i / m;
   return r * mx_chunk_bytes(f, mx_shard_blocks(f, m)) + (i - r * m) * mx_block_payload(f) / kMxBlock;

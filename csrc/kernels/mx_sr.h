@@ -5,19 +5,20 @@
 // Two things live here, both plain integer arithmetic:
 //   * the counter-based random words: mx_sr_mix, the key of a call, the word of an element index;
 //   * the rounding of one scaled value s = x 2^-e (an f32, given as its bits) with one 32-bit word u
-//     to an e4m3 byte or an e2m1 code: with lo <= |s| < hi the neighbouring magnitudes of the format's
+//     to an e4m3 byte, an e2m1 code or an e2m3 code: with lo <= |s| < hi the neighbouring magnitudes of the format's
 //     grid, t = (|s| - lo) / (hi - lo) and T = floor(t 2^32), the magnitude is hi iff u < T.
 //
-// Both grids are ordered like their codes (sign bit aside), so hi is code(lo) + 1, and both are a
+// The grids are ordered like their codes (sign bit aside), so hi is code(lo) + 1, and each is a
 // floating-point grid with MB mantissa bits whose smallest normal magnitude has the f32 exponent field
-// FMIN: e4m3 has MB = 3 and FMIN = 121 (2^-6), e2m1 has MB = 1 and FMIN = 127 (1). With M the 24-bit
+// FMIN: e4m3 has MB = 3 and FMIN = 121 (2^-6), e2m1 has MB = 1 and FMIN = 127 (1), e2m3 has MB = 3 and
+// FMIN = 127. With M the 24-bit
 // significand of |s| and d = max(0, FMIN - field), the grid step at |s| is 2^sh units of M's last
 // place, sh = 23 - MB + d: lo's code is ((field - FMIN) << MB for a normal, 0 below) + (M >> sh), and
-// t is the sh bits under it. In the normal binades sh = 20 (e4m3) or 22 (e2m1), so T = frac << (32 - sh)
+// t is the sh bits under it. In the normal binades sh = 20 (e4m3, e2m3) or 22 (e2m1), so T = frac << (32 - sh)
 // holds t exactly; further down T is the floor of a longer fraction and 0 from 2^-33 of a step on.
 // An f32 subnormal lands there whatever its significand is taken to be.
 //
-// |s| must not exceed the format's largest magnitude (448, 6): the block scale sees to that, and the
+// |s| must not exceed the format's largest magnitude (448, 6, 7.5): the block scale sees to that, and the
 // largest magnitude itself is on the grid, so nothing ever rounds past it.
 #pragma once
 #include <stdint.h>
@@ -83,6 +84,13 @@ PDCC_SR_HD uint32_t mx_sr_e2m1(uint32_t s_bits, uint32_t u) {
   uint32_t lo, T;
   mx_sr_split<1, 127>(s_bits & 0x7fffffffu, lo, T);
   return (((s_bits >> 31) << 3) | (lo + (u < T ? 1u : 0u))) & 0xfu;
+}
+
+// s (f32 bits, |s| <= 7.5) and a word -> e2m3 code, the sign in bit 5
+PDCC_SR_HD uint32_t mx_sr_e2m3(uint32_t s_bits, uint32_t u) {
+  uint32_t lo, T;
+  mx_sr_split<3, 127>(s_bits & 0x7fffffffu, lo, T);
+  return (((s_bits >> 31) << 5) | (lo + (u < T ? 1u : 0u))) & 0x3fu;
 }
 
 }  // namespace kern

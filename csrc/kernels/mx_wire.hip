@@ -1,6 +1,6 @@
-// The local kernels of the block-scaled wire formats `mxfp8_e4m3` and `mxfp4_e2m1` (layout:
+// The local kernels of the block-scaled wire formats `mxfp8_e4m3`, `mxfp4_e2m1` and `mxfp6_e2m3` (layout:
 // mx_layout.h, contract: docs/collectives.md "Compressed all-reduce", "Compressed reduce-scatter and
-// all-gather" and "The `mxfp4_e2m1` wire format"):
+// all-gather", "The `mxfp4_e2m1` wire format" and "The `mxfp6_e2m3` wire format"):
 //
 //   mx_quantize    f32 / bf16 / f16 tensor -> wire           (reads 4n or 2n, writes 33n/32 or 17n/32)
 //   mx_reduce      nsrc chunk wires -> one chunk wire         (dequantize, fold in f32, requantize)
@@ -34,6 +34,15 @@
 // v_cvt_scalef32_pk_f32_fp4 with a unit scale operand: the product with 2^-e (2^e) is the same f32
 // multiply as on the FP8 path, so the scale byte 255 -> NaN and the inf at the very top of the range
 // come out of ordinary f32 arithmetic. e is clamped to [-125, 126] there.
+//
+// The FP6 payload is a bit stream: a lane's 4 or 8 codes are 24 or 48 bits, so on the tensor-side lane
+// layout (quantize, dequantize, fold) the lanes of a quad (f32) or of a pair (bf16 / f16) own 96 bits = 3
+// aligned dwords between them and trade the straddling bits with one DPP move; every payload access is
+// an aligned dword and a wave's accesses are contiguous. Reduce takes a whole block per lane (24 bytes
+// as three aligned 8-byte accesses), as FP4 does. The codes go through the FP8 converts: e2m3 is e4m3
+// with the exponent field cut to two bits, so the e4m3 byte of s / 64 has bits 5 and 6 clear for
+// |s| <= 7.5 and the code is its low five bits and its sign (MxFmt<FP6_E2M3> below). e is clamped to
+// [-123, 126].
 #include <algorithm>
 
 #include "dev_common.h"
@@ -133,12 +142,58 @@ __device__ __forceinline__ MxScale mx4_scale(uint32_t amax) {
   return r;
 }
 
+__device__ __forceinline__ MxScale mx6_scale(uint32_t amax) {
+  // the smallest e with amax 2^-e <= 7.5 = 1.875 2^2 is k - 2 for m <= 1.875 and k - 1 above; the lower
+  // clamp keeps 0.125 2^e a normal f32, the upper one is never reached (k <= 127)
+  int e = (int)(amax >> 23) - 127 - 2 + ((amax & 0x7fffffu) > 0x700000u ? 1 : 0);
+  e = e < -123 ? -123 : (e > 126 ? 126 : e);
+  const bool special = amax >= 0x7f800000u;
+  if (amax == 0) e = 0;
+  MxScale r;
+  r.byte = special ? 255u : (uint32_t)(e + 127);
+  r.inv = __uint_as_float((uint32_t)(127 - e) << 23);
+  r.blank = special || amax == 0;
+  return r;
+}
+// e2m3 through the FP8 converts. Four scaled values s / 64 -> four e4m3 bytes -> 24 bits of codes (element
+// j in bits 6j .. 6j + 5), and back: 24 bits -> four e4m3 bytes -> four values of s / 64.
+__device__ __forceinline__ uint32_t fp6_narrow4(float a, float b, float c, float d, float inv64) {
+  const uint32_t w = narrow4(a, b, c, d, inv64);                      // bits 5 and 6 of every byte are clear
+  const uint32_t c4 = (w & 0x1f1f1f1fu) | ((w >> 2) & 0x20202020u);  // the sign from bit 7 to bit 5
+  return (c4 & 0x3fu) | ((c4 >> 2) & 0xfc0u) | ((c4 >> 4) & 0x3f000u) | ((c4 >> 6) & 0xfc0000u);
+}
+__device__ __forceinline__ void fp6_widen4(uint32_t k, float scale, float* f) {
+  const uint32_t c4 = (k & 0x3fu) | ((k << 2) & 0x3f00u) | ((k << 4) & 0x3f0000u) | ((k << 6) & 0x3f000000u);
+  const uint32_t w = (c4 & 0x1f1f1f1fu) | ((c4 & 0x20202020u) << 2);
+  const f32x2 lo = F8::widen<false>(w), hi = F8::widen<true>(w);
+  // value / 64 is exact in f32, so is the product with 64; 2^(e + 6) itself is no f32 for e > 121
+  f[0] = lo[0] * 64.0f * scale; f[1] = lo[1] * 64.0f * scale; f[2] = hi[0] * 64.0f * scale; f[3] = hi[1] * 64.0f * scale;
+}
+// bits [pos, pos + n) of the little-endian bit stream held in the dwords q (pos and n constants, n <= 32)
+__device__ __forceinline__ void bits_put(uint32_t* q, int pos, int n, uint32_t x) {
+  const int w = pos / 32, o = pos % 32;
+  q[w] |= x << o;
+  if (o + n > 32) q[w + 1] |= x >> (32 - o);
+}
+__device__ __forceinline__ uint32_t bits_get(const uint32_t* q, int pos, int n) {
+  const int w = pos / 32, o = pos % 32;
+  uint32_t x = q[w] >> o;
+  if (o + n > 32) x |= q[w + 1] << (32 - o);
+  return x;  // (bits past n are the stream's next ones: the callers mask)
+}
+
 // What the kernels need of a format: payload bytes per block, the scale of a block, and N elements
 // (4, 8, 16 or 32) to and from their N * kPayload / 32 payload bytes, held in dwords (kWords<N> of
 // them; FP4 with N = 4 fills the low half of one). pack writes zeros for a blank block.
+//
+// kLanes: the payload of the tensor-side lanes (EPL = 4 or 8 elements) is no whole number of dwords, so
+// the lanes that share 3 dwords exchange bits: ld_lanes (a lane's aligned dword loads), gather (the
+// exchange that leaves the lane's own codes in q, called with every lower lane of the group active) and
+// st_lanes (exchange and aligned dword stores, called with the whole group active) replace ld_wire / st_wire.
 template <MxFormat F> struct MxFmt;
 template <> struct MxFmt<MxFormat::FP8_E4M3> {
   static constexpr int kPayload = 32;
+  static constexpr bool kLanes = false;
   template <int N> static constexpr int kWords = N / 4;
   __device__ static __forceinline__ MxScale scale(uint32_t amax) { return mx_scale(amax); }
   template <int N> __device__ static __forceinline__ void pack(const float* f, const MxScale& sc, uint32_t* q) {
@@ -167,6 +222,7 @@ template <> struct MxFmt<MxFormat::FP8_E4M3> {
 };
 template <> struct MxFmt<MxFormat::FP4_E2M1> {
   static constexpr int kPayload = 16;
+  static constexpr bool kLanes = false;
   template <int N> static constexpr int kWords = (N + 7) / 8;
   __device__ static __forceinline__ MxScale scale(uint32_t amax) { return mx4_scale(amax); }
   template <int N> __device__ static __forceinline__ void pack(const float* f, const MxScale& sc, uint32_t* q) {
@@ -197,6 +253,92 @@ template <> struct MxFmt<MxFormat::FP4_E2M1> {
     } else {
 #pragma unroll
       for (int d = 0; d < N / 8; ++d) fp4_widen8(q[d], scale, f + 8 * d);
+    }
+  }
+};
+
+// quad_perm [1,2,3,0], [0,0,1,2]: the next / the previous lane of a quad; [1,1,3,3], [0,0,2,2]: the odd /
+// the even lane of a pair
+constexpr int kDppQuadNext = 0x39, kDppQuadPrev = 0x90, kDppPairOdd = 0xF5, kDppPairEven = 0xA0;
+template <int CTRL>
+__device__ __forceinline__ uint32_t dpp_mov(uint32_t x) {
+  return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, CTRL, 0xf, 0xf, true);
+}
+template <> struct MxFmt<MxFormat::FP6_E2M3> {
+  static constexpr int kPayload = 24;
+  static constexpr bool kLanes = true;
+  template <int N> static constexpr int kWords = (6 * N + 31) / 32;  // 4: 24 bits, 8: 48, 16: 96, 32: 192
+  __device__ static __forceinline__ MxScale scale(uint32_t amax) { return mx6_scale(amax); }
+  template <int N> __device__ static __forceinline__ void pack(const float* f, const MxScale& sc, uint32_t* q) {
+    // 2^-(e + 6) from the scale byte e + 127: a subnormal for e > 120, where every |x| that does not round
+    // to 0 still has a normal, exact product
+    const int t = 248 - (int)sc.byte;
+    const float inv64 = __uint_as_float(t >= 1 ? (uint32_t)t << 23 : 1u << (22 + (t < -22 ? -22 : t)));
+#pragma unroll
+    for (int d = 0; d < kWords<N>; ++d) q[d] = 0u;
+#pragma unroll
+    for (int g = 0; g < N / 4; ++g)
+      bits_put(q, 24 * g, 24, fp6_narrow4(f[4 * g], f[4 * g + 1], f[4 * g + 2], f[4 * g + 3], inv64));
+    if (sc.blank) {
+#pragma unroll
+      for (int d = 0; d < kWords<N>; ++d) q[d] = 0u;
+    }
+  }
+  template <int N, class W> __device__ static __forceinline__ void pack_sr(const float* f, const MxScale& sc, uint32_t* q,
+                                                                          const W& word) {
+#pragma unroll
+    for (int d = 0; d < kWords<N>; ++d) q[d] = 0u;
+#pragma unroll
+    for (int j = 0; j < N; ++j) bits_put(q, 6 * j, 6, kern::mx_sr_e2m3(__float_as_uint(f[j] * sc.inv), word(j)));
+    if (sc.blank) {
+#pragma unroll
+      for (int d = 0; d < kWords<N>; ++d) q[d] = 0u;
+    }
+  }
+  template <int N> __device__ static __forceinline__ void unpack(const uint32_t* q, float scale, float* f) {
+#pragma unroll
+    for (int g = 0; g < N / 4; ++g) fp6_widen4(bits_get(q, 24 * g, 24), scale, f + 4 * g);
+  }
+  // `pay`: the chunk's payload, v: the lane's vector in the chunk (its low bits are the lane's place in
+  // its quad / pair: spans start at multiples of 64). EPL = 4: lane i of a quad owns bits 24 i .. 24 i + 23
+  // of the quad's 96 and moves dword i of its three (lane 3: none), at byte 12 (v / 4) + 4 i = 3 v + i.
+  // EPL = 8: lane p of a pair owns bits 48 p .. 48 p + 47; lane 0 moves dwords 0 and 1, lane 1 dword 2.
+  template <int EPL> __device__ static __forceinline__ void ld_lanes(const char* pay, uint32_t v, uint32_t* q) {
+    if constexpr (EPL == 4) {
+      const uint32_t i = v & 3u;
+      q[0] = i < 3u ? *reinterpret_cast<const uint32_t*>(pay + 3 * (size_t)v + i) : 0u;
+    } else {
+      const uint32_t p = v & 1u;
+      const char* at = pay + 12 * (size_t)(v >> 1);
+      q[0] = *reinterpret_cast<const uint32_t*>(at + 8 * p);
+      q[1] = p ? 0u : *reinterpret_cast<const uint32_t*>(at + 4);
+    }
+  }
+  template <int EPL> __device__ static __forceinline__ void gather(uint32_t v, uint32_t* q) {
+    if constexpr (EPL == 4) {
+      const uint32_t i = v & 3u;
+      const uint32_t prev = dpp_mov<kDppQuadPrev>(q[0]);  // dword i - 1 of the quad
+      q[0] = (uint32_t)((((uint64_t)q[0] << 32) | prev) >> (32u - 8u * i));
+    } else {
+      const uint32_t mid = dpp_mov<kDppPairEven>(q[1]);  // dword 1 of the pair
+      if (v & 1u) {
+        const uint32_t d2 = q[0];
+        q[0] = (mid >> 16) | (d2 << 16);
+        q[1] = d2 >> 16;
+      }
+    }
+  }
+  template <int EPL> __device__ static __forceinline__ void st_lanes(char* pay, uint32_t v, const uint32_t* q) {
+    if constexpr (EPL == 4) {
+      const uint32_t i = v & 3u;
+      const uint32_t next = dpp_mov<kDppQuadNext>(q[0]);  // the 24 bits of lane i + 1
+      if (i < 3u) *reinterpret_cast<uint32_t*>(pay + 3 * (size_t)v + i) = (q[0] >> (8u * i)) | (next << (24u - 8u * i));
+    } else {
+      const uint32_t p = v & 1u;
+      const uint32_t next = dpp_mov<kDppPairOdd>(q[0]);  // the low 32 bits of lane 1
+      char* at = pay + 12 * (size_t)(v >> 1);
+      *reinterpret_cast<uint32_t*>(at + 8 * p) = p ? (q[0] >> 16) | (q[1] << 16) : q[0];
+      if (!p) *reinterpret_cast<uint32_t*>(at + 4) = (q[1] & 0xffffu) | (next << 16);
     }
   }
 };
@@ -233,7 +375,8 @@ struct SrChunkWords {
   __device__ __forceinline__ uint32_t operator()(int j) const { return kern::mx_sr_word_lo(key, lo + (uint32_t)j); }
 };
 
-// B (2, 4, 8 or 16) wire bytes at p (B-aligned) <-> the low bytes of q[(B + 3) / 4]
+// B (2, 4, 8 or 16) wire bytes at p (B-aligned) <-> the low bytes of q[(B + 3) / 4]; B = 24: p is 8-byte
+// aligned and the bytes move as three 8-byte accesses
 template <int B>
 __device__ __forceinline__ void ld_wire(const char* p, uint32_t* q) {
   if constexpr (B == 2) {
@@ -244,6 +387,10 @@ __device__ __forceinline__ void ld_wire(const char* p, uint32_t* q) {
     const uint2 x = *reinterpret_cast<const uint2*>(p);
     q[0] = x.x;
     q[1] = x.y;
+  } else if constexpr (B == 24) {
+    ld_wire<8>(p, q);
+    ld_wire<8>(p + 8, q + 2);
+    ld_wire<8>(p + 16, q + 4);
   } else {
     const uint4 x = *reinterpret_cast<const uint4*>(p);
     q[0] = x.x; q[1] = x.y; q[2] = x.z; q[3] = x.w;
@@ -254,7 +401,11 @@ __device__ __forceinline__ void st_wire(char* p, const uint32_t* q) {
   if constexpr (B == 2) *reinterpret_cast<uint16_t*>(p) = (uint16_t)q[0];
   else if constexpr (B == 4) *reinterpret_cast<uint32_t*>(p) = q[0];
   else if constexpr (B == 8) *reinterpret_cast<uint2*>(p) = make_uint2(q[0], q[1]);
-  else *reinterpret_cast<uint4*>(p) = make_uint4(q[0], q[1], q[2], q[3]);
+  else if constexpr (B == 24) {
+    st_wire<8>(p, q);
+    st_wire<8>(p + 8, q + 2);
+    st_wire<8>(p + 16, q + 4);
+  } else *reinterpret_cast<uint4*>(p) = make_uint4(q[0], q[1], q[2], q[3]);
 }
 
 // ---------------------------------------------------------------------------- quantize
@@ -263,7 +414,7 @@ __device__ __forceinline__ void st_wire(char* p, const uint32_t* q) {
 // SHARD: chunk r is the `m` elements from r * m on (numel = nchunks * m) instead of the 32 cb from
 // r * 32 cb on, and nothing at or past (r + 1) * m enters it. VEC = false (shards that do not start
 // 16-byte aligned) reads every element on its own. On the wire a lane stores QB = EPL (FP8) or
-// EPL / 2 (FP4) payload bytes.
+// EPL / 2 (FP4) payload bytes; FP6: 3 EPL / 4 bytes, as the aligned dwords of MxFmt's st_lanes.
 //
 // EF (error feedback, docs/collectives.md "Error feedback"): what is quantized is v = x + res, and res
 // becomes v - D(Q(v)) where that is finite, +0 where it is not. `res` holds one float per element of
@@ -340,7 +491,8 @@ __global__ __launch_bounds__(256) void k_mx_quantize(const char* __restrict__ sr
       if constexpr (SR) M::template pack_sr<EPL>(f, sc, q, SrWords(sr_key, sr_base + el0 + (uint64_t)v * EPL, EPL));
       else M::template pack<EPL>(f, sc, q);
       // FP8: payload byte e of the chunk is element e of the chunk; FP4: byte e holds elements 2e, 2e + 1
-      st_wire<QB>(w + (size_t)v * QB, q);
+      if constexpr (M::kLanes) M::template st_lanes<EPL>(w, v, q);
+      else st_wire<QB>(w + (size_t)v * QB, q);
       if (v % LPB == 0) w[kern::mx_scale_off(F, cb, v / LPB)] = (char)sc.byte;
       if constexpr (EF) {
         float d[EPL];
@@ -397,9 +549,16 @@ __global__ __launch_bounds__(256) void k_mx_dequantize(const char* __restrict__ 
 #pragma unroll
       for (int d = 0; d < QW; ++d) q[u][d] = 0u;
       if (v < nvec) {
-        ld_wire<QB>(w + (size_t)v * QB, q[u]);
+        if constexpr (M::kLanes) M::template ld_lanes<EPL>(w, v, q[u]);
+        else ld_wire<QB>(w + (size_t)v * QB, q[u]);
         sb[u] = (uint8_t)w[kern::mx_scale_off(F, cb, v / LPB)];
       }
+    }
+    if constexpr (M::kLanes) {  // (a lane in range has every lower lane of its quad / pair in range with it)
+      // v % 4 is the lane's place in its hardware quad only while every span and step is whole quads
+      static_assert(stride % 4 == 0 && (256u * kMxUnroll) % 64 == 0, "gather takes the quad lane from v");
+#pragma unroll
+      for (int u = 0; u < kMxUnroll; ++u) M::template gather<EPL>(v0 + u * stride, q[u]);
     }
 #pragma unroll
     for (int u = 0; u < kMxUnroll; ++u) {
@@ -427,10 +586,10 @@ __global__ __launch_bounds__(256) void k_mx_dequantize(const char* __restrict__ 
 }
 
 // ---------------------------------------------------------------------------- reduce
-// A lane takes 16 payload bytes of every source. FP8: that is half a block, so a block is two
-// neighbouring lanes and the amax of the folded block is one exchange between them. FP4: 16 payload
-// bytes are a whole block (EPL = 32), so the lane holds its block's amax and there is no exchange;
-// the price is 32 accumulators per lane instead of 16.
+// A lane takes PB = 16 payload bytes of every source (FP6: 24). FP8: that is half a block, so a block is
+// two neighbouring lanes and the amax of the folded block is one exchange between them. FP4, FP6: PB
+// payload bytes are a whole block (EPL = 32), so the lane holds its block's amax and there is no
+// exchange; the price is 32 accumulators per lane instead of 16.
 //
 // EF: the owner residual (32 cb floats, one per element of the chunk) is added to the fold after the
 // AVG division and before the scale is taken, and becomes acc - D(Q(acc)) (+0 where not finite). A
@@ -444,18 +603,19 @@ __global__ __launch_bounds__(256) void k_mx_reduce(const char* __restrict__ in, 
                                                    char* __restrict__ out, float* __restrict__ res, uint32_t sr_key) {
   static_assert(!(EF && SR), "error feedback and stochastic rounding are alternatives");
   using M = MxFmt<F>;
-  constexpr int EPL = 16 * kern::kMxBlock / M::kPayload;  // 16 or 32
-  constexpr int LPB = kern::kMxBlock / EPL;               // 2 or 1
+  constexpr int PB = M::kPayload == 24 ? 24 : 16, PW = PB / 4;  // payload bytes / dwords of a lane
+  constexpr int EPL = PB * kern::kMxBlock / M::kPayload;        // 16 or 32
+  constexpr int LPB = kern::kMxBlock / EPL;                     // 2 or 1
   const size_t cbytes = kern::mx_chunk_bytes(F, cb);
   const uint32_t nvec = cb * (uint32_t)LPB;
   const uint32_t stride = gridDim.x * 256u;
   for (uint32_t v = blockIdx.x * 256u + threadIdx.x; v < nvec; v += stride) {
-    uint4 p[NSRC];
+    uint32_t p[NSRC][PW];
     uint32_t sb[NSRC];
 #pragma unroll
     for (int r = 0; r < NSRC; ++r) {
       const char* c = in + (size_t)r * cbytes;
-      p[r] = *reinterpret_cast<const uint4*>(c + (size_t)v * 16);
+      ld_wire<PB>(c + (size_t)v * PB, p[r]);
       sb[r] = (uint8_t)c[kern::mx_scale_off(F, cb, v / LPB)];
     }
     uint4 rr[EF ? EPL / 4 : 1];
@@ -467,9 +627,8 @@ __global__ __launch_bounds__(256) void k_mx_reduce(const char* __restrict__ in, 
 #pragma unroll
     for (int r = 0; r < NSRC; ++r) {
       const float scale = mx_scale_value(sb[r]);
-      const uint32_t w[4] = {p[r].x, p[r].y, p[r].z, p[r].w};
       float f[EPL];
-      M::template unpack<EPL>(w, scale, f);
+      M::template unpack<EPL>(p[r], scale, f);
 #pragma unroll
       for (int i = 0; i < EPL; ++i) acc[i] = r == 0 ? f[i] : acc[i] + f[i];  // rank order
     }
@@ -493,18 +652,19 @@ __global__ __launch_bounds__(256) void k_mx_reduce(const char* __restrict__ in, 
       am = a > am ? a : am;
     }
     const MxScale sc = M::scale(group_max<LPB>(am));
-    uint32_t q[4];
+    uint32_t q[PW];
     if constexpr (SR) M::template pack_sr<EPL>(acc, sc, q, SrChunkWords{v * (uint32_t)EPL, sr_key});
     else M::template pack<EPL>(acc, sc, q);
-    *reinterpret_cast<uint4*>(out + (size_t)v * 16) = make_uint4(q[0], q[1], q[2], q[3]);
+    st_wire<PB>(out + (size_t)v * PB, q);
     if (v % LPB == 0) out[kern::mx_scale_off(F, cb, v / LPB)] = (char)sc.byte;
     if constexpr (EF) {
-      constexpr int G = EPL / 4;  // elements of one payload dword: 4 or 8
+      // elements and payload dwords of one step: a dword's 4 or 8, or the 16 of three FP6 dwords
+      constexpr int G = M::kLanes ? 16 : EPL / 4, GW = M::kLanes ? 3 : 1;
       const float scale = mx_scale_value(sc.byte);
 #pragma unroll
-      for (int w = 0; w < 4; ++w) {
+      for (int w = 0; w < EPL / G; ++w) {
         float d[G];
-        M::template unpack<G>(q + w, scale, d);
+        M::template unpack<G>(q + GW * w, scale, d);
 #pragma unroll
         for (int i = 0; i < G; ++i) d[i] = ef_residual(acc[G * w + i], d[i]);
 #pragma unroll
@@ -553,9 +713,18 @@ __global__ __launch_bounds__(256) void k_mx_fold(const char* __restrict__ in, ui
         for (int d = 0; d < QW; ++d) q[u][r][d] = 0u;
         if (v < nvec) {
           const char* c = in + (size_t)r * cbytes;
-          ld_wire<QB>(c + (size_t)v * QB, q[u][r]);
+          if constexpr (M::kLanes) M::template ld_lanes<EPL>(c, v, q[u][r]);
+          else ld_wire<QB>(c + (size_t)v * QB, q[u][r]);
           sb[u][r] = (uint8_t)c[kern::mx_scale_off(F, cb, v / LPB)];
         }
+      }
+    }
+    if constexpr (M::kLanes) {  // (as in dequantize: 256 lanes a step, whole quads)
+      static_assert((256u * U) % 64 == 0, "gather takes the quad lane from v");
+#pragma unroll
+      for (int u = 0; u < U; ++u) {
+#pragma unroll
+        for (int r = 0; r < NSRC; ++r) M::template gather<EPL>(v0 + u * 256u, q[u][r]);
       }
     }
 #pragma unroll
@@ -612,7 +781,7 @@ namespace {
 bool mx_al16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 // cb: a multiple of 16, and a chunk's lanes are counted in 32 bits
 bool mx_cb_ok(size_t cb) { return cb > 0 && cb % kMxScaleAlign == 0 && cb <= (size_t(1) << 27); }
-bool mx_fmt_ok(MxFormat f) { return f == MxFormat::FP8_E4M3 || f == MxFormat::FP4_E2M1; }
+bool mx_fmt_ok(MxFormat f) { return f == MxFormat::FP8_E4M3 || f == MxFormat::FP4_E2M1 || f == MxFormat::FP6_E2M3; }
 size_t mx_esize(DType t) { return t == DType::F32 ? 4 : 2; }
 bool mx_dtype_ok(DType t) { return t == DType::F32 || t == DType::BF16 || t == DType::F16; }
 // the shard arguments: m elements per shard fit the chunk, and the whole tensor's size is a size_t
@@ -675,6 +844,7 @@ hipError_t mx_quantize_any(MxFormat fmt, DType t, bool shard, bool vec, const vo
   const char* s = static_cast<const char*>(src);
   char* w = static_cast<char*>(wire);
   if (fmt == MxFormat::FP4_E2M1) mx_quantize_dt<MxFormat::FP4_E2M1>(t, shard, vec, grid, s, numel, w, (uint32_t)cb, m, res, sr, stream);
+  else if (fmt == MxFormat::FP6_E2M3) mx_quantize_dt<MxFormat::FP6_E2M3>(t, shard, vec, grid, s, numel, w, (uint32_t)cb, m, res, sr, stream);
   else mx_quantize_dt<MxFormat::FP8_E4M3>(t, shard, vec, grid, s, numel, w, (uint32_t)cb, m, res, sr, stream);
   return hipGetLastError();
 }
@@ -684,6 +854,7 @@ hipError_t mx_dequantize_any(MxFormat fmt, DType t, bool shard, bool vec, const 
   const char* w = static_cast<const char*>(wire);
   char* d = static_cast<char*>(dst);
   if (fmt == MxFormat::FP4_E2M1) mx_dequantize_dt<MxFormat::FP4_E2M1>(t, shard, vec, grid, w, (uint32_t)cb, d, numel, m, stream);
+  else if (fmt == MxFormat::FP6_E2M3) mx_dequantize_dt<MxFormat::FP6_E2M3>(t, shard, vec, grid, w, (uint32_t)cb, d, numel, m, stream);
   else mx_dequantize_dt<MxFormat::FP8_E4M3>(t, shard, vec, grid, w, (uint32_t)cb, d, numel, m, stream);
   return hipGetLastError();
 }
@@ -768,7 +939,7 @@ namespace {
 template <MxFormat F, bool AVG, bool EF, bool SR>
 hipError_t mx_reduce_go(const char* in, int nsrc, uint32_t cb, int avg_div, char* out, float* res, uint32_t key,
                         hipStream_t stream) {
-  constexpr int lpb = F == MxFormat::FP4_E2M1 ? 1 : 2;  // lanes per block: 16 payload bytes per lane
+  constexpr int lpb = F == MxFormat::FP8_E4M3 ? 2 : 1;  // lanes per block: 16 (FP6: 24) payload bytes per lane
   const dim3 grid(dev::mx_grid_x((uint64_t)cb * lpb, 1, 1, dev::kMxGridReduce)), block(256);
   switch (nsrc) {
 #define PDCC_MX_N(N) \
@@ -800,6 +971,7 @@ hipError_t mx_reduce_any(const void* wire_in, int nsrc, size_t cb, RedOp op, int
   if (op == RedOp::AVG && avg_div < 1) return hipErrorInvalidValue;
   const char* in = static_cast<const char*>(wire_in);
   char* out = static_cast<char*>(wire_out);
+  if (fmt == MxFormat::FP6_E2M3) return mx_reduce_op<MxFormat::FP6_E2M3>(in, nsrc, (uint32_t)cb, op, avg_div, out, res, key, stream);
   return fmt == MxFormat::FP4_E2M1 ? mx_reduce_op<MxFormat::FP4_E2M1>(in, nsrc, (uint32_t)cb, op, avg_div, out, res, key, stream)
                                    : mx_reduce_op<MxFormat::FP8_E4M3>(in, nsrc, (uint32_t)cb, op, avg_div, out, res, key, stream);
 }
@@ -868,6 +1040,7 @@ hipError_t mx_fold(const void* wire_in, int nsrc, size_t cb, RedOp op, int avg_d
   if (op == RedOp::AVG && avg_div < 1) return hipErrorInvalidValue;
   const char* in = static_cast<const char*>(wire_in);
   char* d = static_cast<char*>(dst);
+  if (fmt == MxFormat::FP6_E2M3) return mx_fold_dt<MxFormat::FP6_E2M3>(t, in, nsrc, (uint32_t)cb, op, avg_div, d, numel, stream);
   return fmt == MxFormat::FP4_E2M1 ? mx_fold_dt<MxFormat::FP4_E2M1>(t, in, nsrc, (uint32_t)cb, op, avg_div, d, numel, stream)
                                    : mx_fold_dt<MxFormat::FP8_E4M3>(t, in, nsrc, (uint32_t)cb, op, avg_div, d, numel, stream);
 }

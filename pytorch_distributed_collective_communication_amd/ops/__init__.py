@@ -15,8 +15,9 @@
 
 * :func:`mx_quantize`, :func:`mx_reduce`, :func:`mx_dequantize` -- the block-scaled wire formats
   ``mxfp8_e4m3`` (docs/collectives.md "Compressed all-reduce": 32-element blocks, one E8M0 scale
-  byte and 32 ``float8_e4m3fn`` bytes each) and ``mxfp4_e2m1`` ("The ``mxfp4_e2m1`` wire format":
-  16 bytes of two e2m1 nibbles instead), picked by the trailing keyword ``wire``.
+  byte and 32 ``float8_e4m3fn`` bytes each), ``mxfp4_e2m1`` ("The ``mxfp4_e2m1`` wire format":
+  16 bytes of two e2m1 nibbles instead) and ``mxfp6_e2m3`` ("The ``mxfp6_e2m3`` wire format": 24 bytes,
+  a bit stream of 32 six-bit e2m3 codes), picked by the trailing keyword ``wire``.
   ``parallel/compressed.py`` builds ``all_reduce_compressed`` from them.
   :func:`mx_quantize`, :func:`mx_quantize_shards` and :func:`mx_reduce` take ``rounding="stochastic"`` with
   ``seed=`` and ``stream=``: unbiased, stateless rounding of the payload (docs/collectives.md "Stochastic
@@ -141,13 +142,13 @@ def unpack(flat: torch.Tensor, tensors: Sequence[torch.Tensor]) -> None:
     multi_copy(srcs, [_byte_view(t) for t in tensors])
 
 
-# ------------------------------------------------------- block-scaled wires (mxfp8_e4m3, mxfp4_e2m1)
+# ------------------------------------------ block-scaled wires (mxfp8_e4m3, mxfp4_e2m1, mxfp6_e2m3)
 # Every function below takes the format as the trailing keyword ``wire``. Where the first argument is the
 # wire tensor itself it is positional-only (``w``), so the keyword is free for the format's name.
 MX_BLOCK = 32
 MX_DTYPES = (torch.float32, torch.bfloat16, torch.float16)
-MX_WIRES = ("mxfp8_e4m3", "mxfp4_e2m1")
-_MX_PAYLOAD = {"mxfp8_e4m3": 32, "mxfp4_e2m1": 16}  # payload bytes per block; one scale byte follows
+MX_WIRES = ("mxfp8_e4m3", "mxfp4_e2m1", "mxfp6_e2m3")
+_MX_PAYLOAD = {"mxfp8_e4m3": 32, "mxfp4_e2m1": 16, "mxfp6_e2m3": 24}  # payload bytes per block; one scale byte follows
 
 
 def _mx_payload(wire, who: str) -> int:
@@ -159,7 +160,7 @@ def _mx_payload(wire, who: str) -> int:
 
 def mx_chunk_blocks(numel: int, world: int = 1, *, wire: str = "mxfp8_e4m3") -> int:
     """Blocks per chunk when ``numel`` elements are dealt to ``world`` chunks (csrc/kernels/mx_layout.h):
-    a multiple of 16, and of 4096 once a chunk's wire (33 or 17 bytes per block) reaches 1 MiB."""
+    a multiple of 16, and of 4096 once a chunk's wire (33, 17 or 25 bytes per block) reaches 1 MiB."""
     bw = _mx_payload(wire, "mx_chunk_blocks") + 1
     world = max(1, int(world))
     blocks = (int(numel) + MX_BLOCK - 1) // MX_BLOCK
@@ -171,7 +172,7 @@ def mx_chunk_blocks(numel: int, world: int = 1, *, wire: str = "mxfp8_e4m3") -> 
 
 def mx_wire_bytes(numel: int, world: int = 1, *, wire: str = "mxfp8_e4m3") -> int:
     """Bytes of the wire of ``numel`` elements in ``world`` chunks: ``world`` x (32 cb payload + cb scales);
-    16 cb payload bytes for ``mxfp4_e2m1``."""
+    16 cb payload bytes for ``mxfp4_e2m1``, 24 cb for ``mxfp6_e2m3``."""
     return (_mx_payload(wire, "mx_wire_bytes") + 1) * mx_chunk_blocks(numel, world, wire=wire) * max(1, int(world))
 
 
@@ -242,7 +243,7 @@ def mx_quantize(x: torch.Tensor, world: int = 1, out: torch.Tensor | None = None
                 seed: int = 0, stream: int = 0, index_offset: int = 0) -> torch.Tensor:
     """``x`` (GPU; f32 / bf16 / f16) -> its wire in the format ``wire``: a uint8 tensor of ``world`` chunks
     of ``[32 cb payload bytes][cb scale bytes]`` (``mxfp4_e2m1``: 16 cb payload bytes, two elements to a
-    byte), padding blocks included (scale 127, payload 0).
+    byte; ``mxfp6_e2m3``: 24 cb payload bytes, six bits to an element), padding blocks included (scale 127, payload 0).
 
     ``residual`` (float32, one element per element of ``x``; error feedback): what is quantized is
     ``x.float() + residual``, and the residual becomes what the quantization dropped of that sum (+0
@@ -435,11 +436,57 @@ def _mx4_dequantize_blocks(q: torch.Tensor, s: torch.Tensor) -> torch.Tensor:
     return v * _mx_scale_values(s)[:, None]  # 6 2^126 -> inf: one f32 product
 
 
+def _mx6_pack(code: torch.Tensor) -> torch.Tensor:
+    """(blocks, 32) six-bit codes -> (blocks, 24) payload bytes: the code of element j in bits 6j .. 6j + 5 of
+    the block's little-endian bit stream, so four codes fill three bytes."""
+    c = code.to(torch.int32).view(code.shape[0], 8, 4)
+    k = c[:, :, 0] | (c[:, :, 1] << 6) | (c[:, :, 2] << 12) | (c[:, :, 3] << 18)
+    return torch.stack([k & 255, (k >> 8) & 255, k >> 16], dim=2).reshape(code.shape[0], 24).to(torch.uint8)
+
+
+def _mx6_unpack(q: torch.Tensor) -> torch.Tensor:
+    """(blocks, 24) payload bytes -> (blocks, 32) six-bit codes (int32)."""
+    b = q.to(torch.int32).view(q.shape[0], 8, 3)
+    k = b[:, :, 0] | (b[:, :, 1] << 8) | (b[:, :, 2] << 16)
+    return torch.stack([k & 63, (k >> 6) & 63, (k >> 12) & 63, (k >> 18) & 63], dim=2).reshape(q.shape[0], 32)
+
+
+def _mx6_quantize_blocks(xb: torch.Tensor):
+    """(blocks, 32) f32 -> ((blocks, 24) uint8 payload, (blocks,) uint8 scales), the FP6 contract's Q."""
+    amax = xb.abs().amax(dim=1)
+    special = ~torch.isfinite(xb).all(dim=1)
+    zero = (amax == 0) & ~special
+    m, ex = torch.frexp(torch.where(special | zero, torch.ones_like(amax), amax))
+    e = (ex.to(torch.int64) - 1) - 2 + (m > 0.9375).to(torch.int64)  # m here is half the contract's m
+    e = e.clamp(-123, 126)
+    e[zero] = 0
+    # e2m3 is e4m3 with the exponent field cut to two bits: for |s| <= 7.5 the float8_e4m3fn byte of s / 64
+    # (nearest even; both products exact, or far below half a grid step where they are subnormal) has bits 5
+    # and 6 clear, and the code is its low five bits with its sign in bit 5
+    b = ((xb * _mx_exp2(-e)[:, None]) * 0.015625).to(torch.float8_e4m3fn).view(torch.uint8).to(torch.int32)
+    code = (b & 31) | ((b >> 7) << 5)
+    code[special | zero] = 0
+    s = (e + 127).to(torch.uint8)
+    s[special] = 255
+    return _mx6_pack(code), s
+
+
+def _mx6_dequantize_blocks(q: torch.Tensor, s: torch.Tensor) -> torch.Tensor:
+    """The FP6 contract's D: (blocks, 24) payload bytes and (blocks,) scale bytes -> (blocks, 32) f32."""
+    code = _mx6_unpack(q)
+    mant, ex = (code & 7).to(torch.float32), (code >> 3) & 3
+    v = torch.where(ex == 0, mant / 8, (1 + mant / 8) * _mx_exp2(torch.clamp(ex - 1, min=0)))
+    v = torch.where((code & 32) != 0, -v, v)
+    return v * _mx_scale_values(s)[:, None]  # 4 2^126 and above -> inf: one f32 product
+
+
 # ---- stochastic rounding (docs/collectives.md "Stochastic rounding"), integer arithmetic on int64 tensors
 _M32 = 0xFFFFFFFF
 # per payload size: mantissa bits, f32 exponent field of the smallest normal magnitude, the scale rule's
 # (exponent bias, switch point of frexp's mantissa, lower and upper clamp of e)
-_MX_SR_FORMAT = {32: (3, 121, 8, 0.875, -117, 120), 16: (1, 127, 2, 0.75, -125, 126)}
+_MX_SR_FORMAT = {32: (3, 121, 8, 0.875, -117, 120), 16: (1, 127, 2, 0.75, -125, 126),
+                 24: (3, 127, 2, 0.9375, -123, 126)}
+_MX_SR_SIGN = {32: 7, 16: 3, 24: 5}  # the sign's bit in a code
 
 
 def _mx_sr_mul(x: torch.Tensor, c: int) -> torch.Tensor:
@@ -488,10 +535,10 @@ def _mx_sr_quantize_blocks(xb: torch.Tensor, u: torch.Tensor, pb: int):
     sh = 23 - mb + (fmin - field).clamp(0, 40)
     lo = torch.where(normal, (field - fmin) << mb, torch.zeros_like(a)) + (mant >> sh)
     thr = ((mant & ((torch.ones_like(sh) << sh) - 1)) << 32) >> sh
-    code = (lo + (u < thr).to(torch.int64)) | ((bits >> 31) << (7 if pb == 32 else 3))
+    code = (lo + (u < thr).to(torch.int64)) | ((bits >> 31) << _MX_SR_SIGN[pb])
     code[special | zero] = 0
     code = code.to(torch.uint8)
-    q = code if pb == 32 else (code[:, 0::2] | (code[:, 1::2] << 4)).contiguous()
+    q = code if pb == 32 else (_mx6_pack(code) if pb == 24 else (code[:, 0::2] | (code[:, 1::2] << 4)).contiguous())
     s = (e + 127).to(torch.uint8)
     s[special] = 255
     return q, s
@@ -500,8 +547,8 @@ def _mx_sr_quantize_blocks(xb: torch.Tensor, u: torch.Tensor, pb: int):
 def _mx_blocks_fns(wire: str, who: str):
     """(payload bytes per block, Q, D) of a format."""
     pb = _mx_payload(wire, who)
-    return (pb, _mx_quantize_blocks, _mx_dequantize_blocks) if pb == 32 else (pb, _mx4_quantize_blocks,
-                                                                             _mx4_dequantize_blocks)
+    return {32: (pb, _mx_quantize_blocks, _mx_dequantize_blocks), 16: (pb, _mx4_quantize_blocks, _mx4_dequantize_blocks),
+            24: (pb, _mx6_quantize_blocks, _mx6_dequantize_blocks)}[pb]
 
 
 def _mx_split(w: torch.Tensor, nchunks: int, pb: int = 32):

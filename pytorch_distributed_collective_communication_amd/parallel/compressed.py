@@ -1,4 +1,4 @@
-"""All-reduce, reduce-scatter and all-gather over a block-scaled wire: ``mxfp8_e4m3`` or ``mxfp4_e2m1``.
+"""All-reduce, reduce-scatter and all-gather over a block-scaled wire: ``mxfp8_e4m3``, ``mxfp4_e2m1`` or ``mxfp6_e2m3``.
 
 The tensor stays f32 / bf16 / f16; what crosses the links is 32-element blocks of
 ``float8_e4m3fn`` with one power-of-two scale byte each, and every sum is taken in f32
@@ -48,7 +48,7 @@ import torch.distributed as dist
 
 from .. import ops
 
-WIRES = ("mxfp8_e4m3", "mxfp4_e2m1")
+WIRES = ("mxfp8_e4m3", "mxfp4_e2m1", "mxfp6_e2m3")
 MAX_GPU_WORLD = 8  # ops.mx_reduce folds up to 8 sources (one xGMI node)
 
 _side_streams = {}
@@ -149,7 +149,7 @@ def all_reduce_compressed(tensor: torch.Tensor, op=dist.ReduceOp.SUM, group=None
                           async_op: bool = False, *, residual: torch.Tensor | None = None,
                           owner_residual: torch.Tensor | None = None, rounding: str = "nearest", seed: int = 0):
     """In-place SUM / AVG all-reduce of ``tensor`` (float32, bfloat16 or float16) over the wire
-    format ``wire`` (``mxfp8_e4m3`` or ``mxfp4_e2m1``). Every rank ends with the same bits; at world 1 the tensor is left
+    format ``wire`` (``mxfp8_e4m3``, ``mxfp4_e2m1`` or ``mxfp6_e2m3``). Every rank ends with the same bits; at world 1 the tensor is left
     unchanged (not even quantized). GPU tensors run on the current stream; with ``async_op=True``
     on a side stream that first waits for the current one, and the returned handle's ``wait()``
     makes the current stream wait for it. CPU tensors run synchronously (the handle is complete).

@@ -24,8 +24,8 @@ contract, MI355X-first:
   reduction of the accumulated gradients. A second backward before
   :meth:`finish` (outside ``no_sync``) raises instead of silently dropping a
   micro-batch;
-* ``wire="mxfp8_e4m3"`` or ``wire="mxfp4_e2m1"``: every bucket goes through
-  ``all_reduce_compressed`` (block-scaled FP8 or FP4 on the links, f32 sums, AVG;
+* ``wire="mxfp8_e4m3"``, ``wire="mxfp4_e2m1"`` or ``wire="mxfp6_e2m3"``: every bucket goes through
+  ``all_reduce_compressed`` (block-scaled FP8, FP4 or FP6 on the links, f32 sums, AVG;
   parallel/compressed.py) instead of ``dist.all_reduce``. The default ``wire=None`` is the exact
   path above;
 * ``error_feedback=True`` (with a wire): every bucket keeps what the quantizer dropped of its

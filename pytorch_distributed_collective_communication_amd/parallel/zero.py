@@ -176,7 +176,7 @@ class ShardedOptimizer:
     bf16 parameters the optimizer math runs in fp32 and only the gathered
     parameters are bf16. ``overlap=False`` defers every reduce-scatter to
     :meth:`step`. ``grad_wire`` / ``param_wire`` (default ``None``: uncompressed;
-    ``"mxfp8_e4m3"`` or ``"mxfp4_e2m1"``, each on its own) pick the wire of the reduce-scatters / the all-gathers of
+    ``"mxfp8_e4m3"``, ``"mxfp4_e2m1"`` or ``"mxfp6_e2m3"``, each on its own) pick the wire of the reduce-scatters / the all-gathers of
     float32, bfloat16 and float16 parameters. ``grad_error_feedback=True`` (needs ``grad_wire``) carries the
     quantization error of this rank's gradients from step to step in an f32 residual, 4 bytes per gradient
     element, saved by :meth:`state_dict`. ``grad_rounding="stochastic"`` with ``grad_seed`` (needs ``grad_wire``,

@@ -1,0 +1,138 @@
+#!/usr/bin/env python3
+"""The mxfp6_e2m3 wire kernels next to their mxfp8_e4m3 and mxfp4_e2m1 twins, in one run and on the same
+tensors (interleaved rounds, medians; nothing here is a pass / fail gate).
+
+One process, GPU 0. For every tensor size (--mib, MiB of the tensor itself) and dtype (f32, bf16):
+  * mx_quantize plain, with a residual (error feedback) and stochastic; mx_dequantize (1 chunk);
+  * mx_reduce of 2 and 8 chunk wires (f32 sizes only: the kernel never sees the tensor's dtype);
+  * mx_fold of 2 and 8 chunk wires into the tensor.
+An FP6 kernel reads or writes the same tensor bytes as its twins and 25 wire bytes per block against 33
+(FP8) and 17 (FP4), so the expectation for the plain kernels is "between the two, no slower than FP8"; the
+yardstick is the FP8 kernel as measured in this same run, the three alternating inside every round. Times are
+device events around back-to-back calls after a warm-up call; per case the file holds the median, minimum and
+maximum over the rounds in microseconds, the GB/s of the median over the bytes the kernel must read and
+write, the ratio of the FP6 median to each twin's, and whether the FP6 kernel is slower than its FP8 twin
+beyond the run's own spread (its fastest round above the twin's slowest).
+
+The collectives themselves are not measured here: nothing cross-GPU has been measured for any wire.
+
+    python scripts/mx6_bench.py [--rounds 7] [--mib 64 1024] [--out profiles/mx/mx6_kernels.json]
+"""
+import argparse
+import json
+import os
+import statistics
+import sys
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+WIRES = {"fp8": "mxfp8_e4m3", "fp6": "mxfp6_e2m3", "fp4": "mxfp4_e2m1"}
+
+
+def timeit(fn, iters):
+    import torch
+
+    s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    fn()
+    s.record()
+    for _ in range(iters):
+        fn()
+    e.record()
+    torch.cuda.synchronize()
+    return s.elapsed_time(e) / iters / 1e3
+
+
+def cases_for(mib, dtn, ops, torch, dev):
+    """{case: {wire key: (fn, bytes)}} for one tensor size and dtype; the buffers live in the closures."""
+    dt = {"f32": torch.float32, "bf16": torch.bfloat16}[dtn]
+    esize = 4 if dtn == "f32" else 2
+    n = (mib << 20) // esize
+    x = torch.randn(n, device=dev).to(dt)
+    back = torch.empty(n, dtype=dt, device=dev)
+    res = torch.zeros(n, dtype=torch.float32, device=dev)
+    out = {}
+
+    def add(name, key, fn, nbytes):
+        out.setdefault(f"{name}_{dtn}_{mib}MiB", {})[key] = (fn, nbytes)
+
+    for key, wire in WIRES.items():
+        w1 = torch.empty(ops.mx_wire_bytes(n, 1, wire=wire), dtype=torch.uint8, device=dev)
+        add("mx_quantize", key, lambda w1=w1, wire=wire: ops.mx_quantize(x, 1, out=w1, wire=wire), esize * n + w1.numel())
+        add("mx_quantize_ef", key, lambda w1=w1, wire=wire: ops.mx_quantize(x, 1, out=w1, wire=wire, residual=res),
+            esize * n + 8 * n + w1.numel())
+        add("mx_quantize_sr", key, lambda w1=w1, wire=wire: ops.mx_quantize(x, 1, out=w1, wire=wire, rounding="stochastic",
+                                                                            seed=1234), esize * n + w1.numel())
+        add("mx_dequantize", key, lambda w1=w1, wire=wire: ops.mx_dequantize(w1, n, dt, 1, out=back, wire=wire),
+            esize * n + w1.numel())
+        chunk = ops.mx_shard_wire_bytes(n, 1, wire=wire)
+        win = torch.empty(chunk * 8, dtype=torch.uint8, device=dev)
+        for r in range(8):
+            ops.mx_quantize(x * float(r + 1), 1, out=win[chunk * r:chunk * (r + 1)], wire=wire)
+        mid = torch.empty(chunk, dtype=torch.uint8, device=dev)
+        for nsrc in (2, 8):
+            src = win[:chunk * nsrc]
+            if dtn == "f32":
+                add(f"mx_reduce_{nsrc}", key, lambda src=src, nsrc=nsrc, mid=mid, wire=wire:
+                    ops.mx_reduce(src, nsrc, "sum", out=mid, wire=wire), src.numel() + chunk)
+            add(f"mx_fold_{nsrc}", key, lambda src=src, nsrc=nsrc, wire=wire:
+                ops.mx_fold(src, nsrc, n, dt, "sum", out=back, wire=wire), src.numel() + esize * n)
+    return out
+
+
+def main():
+    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument("--rounds", type=int, default=7)
+    ap.add_argument("--mib", type=int, nargs="+", default=[64, 1024])
+    ap.add_argument("--out", default=os.path.join("profiles", "mx", "mx6_kernels.json"))
+    a = ap.parse_args()
+
+    import torch
+
+    from pytorch_distributed_collective_communication_amd import ops
+
+    assert torch.cuda.is_available(), "mx6_bench.py measures on a GPU; there is no fallback"
+    dev = torch.device("cuda", 0)
+    raw, nbytes = {}, {}
+    for mib in a.mib:
+        iters = max(8, min(200, 16384 // mib))
+        for dtn in ("f32", "bf16"):
+            cases = cases_for(mib, dtn, ops, torch, dev)
+            for _ in range(a.rounds):
+                for name, trio in cases.items():
+                    for key in WIRES:  # the twins alternate inside every round
+                        fn, nb = trio[key]
+                        raw.setdefault(name, {}).setdefault(key, []).append(timeit(fn, iters))
+                        nbytes.setdefault(name, {})[key] = nb
+            del cases
+            torch.cuda.empty_cache()
+
+    rows = {}
+    for name in sorted(raw):
+        row = {}
+        for key in WIRES:
+            us = [t * 1e6 for t in raw[name][key]]
+            row[key] = {"us_median": round(statistics.median(us), 2), "us_min": round(min(us), 2),
+                        "us_max": round(max(us), 2), "bytes": nbytes[name][key],
+                        "gbps_median": round(nbytes[name][key] / statistics.median(raw[name][key]) / 1e9, 1),
+                        "us_rounds": [round(u, 2) for u in us]}
+        row["time_ratio_fp6_over_fp8"] = round(row["fp6"]["us_median"] / row["fp8"]["us_median"], 3)
+        row["time_ratio_fp6_over_fp4"] = round(row["fp6"]["us_median"] / row["fp4"]["us_median"], 3)
+        row["byte_ratio_fp6_over_fp8"] = round(row["fp6"]["bytes"] / row["fp8"]["bytes"], 3)
+        row["fp6_slower_than_fp8_beyond_the_spread"] = row["fp6"]["us_min"] > row["fp8"]["us_max"]
+        rows[name] = row
+    doc = {
+        "what": "the mxfp6_e2m3 kernels next to the mxfp8_e4m3 and mxfp4_e2m1 kernels in the same run on the same "
+                "tensors: device-event microseconds per call (median, min, max over interleaved rounds), GB/s of the "
+                "median over the bytes the kernel must read and write, and the ratios of the medians",
+        "rounds": a.rounds, "device": torch.cuda.get_device_name(0), "rows": rows,
+    }
+    os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+    with open(a.out, "w") as f:
+        json.dump(doc, f, indent=1, sort_keys=True)
+        f.write("\n")
+    print(json.dumps({k: [v["time_ratio_fp6_over_fp8"], v["time_ratio_fp6_over_fp4"], v["fp6_slower_than_fp8_beyond_the_spread"]]
+                      for k, v in rows.items()}))
+
+
+if __name__ == "__main__":
+    main()
