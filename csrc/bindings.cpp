@@ -13,6 +13,7 @@
 #include "device/comm_util.h"
 #include "kernels/kernel_api.h"
 #include "kernels/mx_layout.h"
+#include "kernels/mx_rot.h"
 
 namespace py = pybind11;
 
@@ -128,6 +129,13 @@ void mx_check_sr(bool sr, bool residual, int64_t stream, const char* who) {
   TORCH_CHECK_VALUE(!(sr && residual), who, ": stochastic rounding and a residual are alternatives");
   TORCH_CHECK_VALUE(stream >= 0 && stream <= 0xffffffffll, who, ": stream must be in [0, 2^32)");
 }
+// Hadamard rotation (docs/collectives.md "Hadamard rotation"): the sign word of `seed`, or none
+struct MxRot {
+  uint32_t signs = 0;
+  bool on = false;
+  MxRot(bool rot, uint64_t seed) : signs(rot ? pdcc::kern::mx_rot_signs(seed) : 0u), on(rot) {}
+  const uint32_t* ptr() const { return on ? &signs : nullptr; }
+};
 using pdcc::kern::MxFormat;
 MxFormat mx_format(const std::string& wire, const char* who) {
   if (wire == "mxfp8_e4m3") return MxFormat::FP8_E4M3;
@@ -139,8 +147,9 @@ MxFormat mx_format(const std::string& wire, const char* who) {
 
 at::Tensor mx_quantize(const at::Tensor& x, int world, const c10::optional<at::Tensor>& out, const std::string& fmt,
                        const c10::optional<at::Tensor>& residual, bool sr, uint64_t seed, int64_t sr_stream,
-                       uint64_t index_offset) {
+                       uint64_t index_offset, bool rot, uint64_t rot_seed) {
   const MxFormat f = mx_format(fmt, "mx_quantize");
+  const MxRot rt(rot, rot_seed);
   mx_check_sr(sr, residual.has_value(), sr_stream, "mx_quantize");
   TORCH_CHECK(x.is_cuda(), "mx_quantize: GPU tensors only");
   TORCH_CHECK(world >= 1, "mx_quantize: world must be >= 1");
@@ -157,9 +166,10 @@ at::Tensor mx_quantize(const at::Tensor& x, int world, const c10::optional<at::T
   at::Tensor src = mx_in(x), w = mx_out(wire);
   hipStream_t s = c10::hip::getCurrentHIPStreamMasqueradingAsCUDA(x.device().index()).stream();
   hipError_t e = sr    ? pdcc::kern::mx_quantize_sr(src.data_ptr(), numel, d, w.data_ptr(), cb, (size_t)world, seed,
-                                                    (uint32_t)sr_stream, index_offset, s, f)
-                 : res ? pdcc::kern::mx_quantize_ef(src.data_ptr(), numel, d, res, w.data_ptr(), cb, (size_t)world, s, f)
-                       : pdcc::kern::mx_quantize(src.data_ptr(), numel, d, w.data_ptr(), cb, (size_t)world, s, f);
+                                                    (uint32_t)sr_stream, index_offset, s, f, rt.ptr())
+                 : res ? pdcc::kern::mx_quantize_ef(src.data_ptr(), numel, d, res, w.data_ptr(), cb, (size_t)world, s, f,
+                                                    rt.ptr())
+                       : pdcc::kern::mx_quantize(src.data_ptr(), numel, d, w.data_ptr(), cb, (size_t)world, s, f, rt.ptr());
   TORCH_CHECK(e == hipSuccess, "mx_quantize launch failed: ", hipGetErrorString(e));
   if (!w.is_same(wire)) wire.copy_(w);
   return wire;
@@ -194,8 +204,10 @@ at::Tensor mx_reduce(const at::Tensor& wire, int nsrc, const std::string& op, co
   return res;
 }
 
-void mx_dequantize(const at::Tensor& wire, int world, at::Tensor& out, const std::string& fmt) {
+void mx_dequantize(const at::Tensor& wire, int world, at::Tensor& out, const std::string& fmt, bool rot,
+                   uint64_t rot_seed) {
   const MxFormat f = mx_format(fmt, "mx_dequantize");
+  const MxRot rt(rot, rot_seed);
   mx_check_wire(wire, "mx_dequantize");
   TORCH_CHECK(world >= 1, "mx_dequantize: world must be >= 1");
   TORCH_CHECK(out.is_cuda() && out.device() == wire.device(), "mx_dequantize: out must be on the wire's GPU");
@@ -208,7 +220,7 @@ void mx_dequantize(const at::Tensor& wire, int world, at::Tensor& out, const std
   c10::hip::HIPGuardMasqueradingAsCUDA g(wire.device());
   at::Tensor w = mx_in(wire), o = mx_out(out);
   hipStream_t s = c10::hip::getCurrentHIPStreamMasqueradingAsCUDA(wire.device().index()).stream();
-  hipError_t e = pdcc::kern::mx_dequantize(w.data_ptr(), cb, (size_t)world, o.data_ptr(), numel, d, s, f);
+  hipError_t e = pdcc::kern::mx_dequantize(w.data_ptr(), cb, (size_t)world, o.data_ptr(), numel, d, s, f, rt.ptr());
   TORCH_CHECK(e == hipSuccess, "mx_dequantize launch failed: ", hipGetErrorString(e));
   if (!o.is_same(out)) out.copy_(o);
 }
@@ -216,8 +228,9 @@ void mx_dequantize(const at::Tensor& wire, int world, at::Tensor& out, const std
 // ---- the shard layout (kernels/mx_layout.h): chunk r is shard r of `numel / world` elements
 at::Tensor mx_quantize_shards(const at::Tensor& x, int world, const c10::optional<at::Tensor>& out,
                               const std::string& fmt, const c10::optional<at::Tensor>& residual, bool sr, uint64_t seed,
-                              int64_t sr_stream, uint64_t index_offset) {
+                              int64_t sr_stream, uint64_t index_offset, bool rot, uint64_t rot_seed) {
   const MxFormat f = mx_format(fmt, "mx_quantize_shards");
+  const MxRot rt(rot, rot_seed);
   mx_check_sr(sr, residual.has_value(), sr_stream, "mx_quantize_shards");
   TORCH_CHECK(x.is_cuda(), "mx_quantize_shards: GPU tensors only");
   TORCH_CHECK(world >= 1 && world <= 65535, "mx_quantize_shards: world must be 1..65535");
@@ -236,16 +249,20 @@ at::Tensor mx_quantize_shards(const at::Tensor& x, int world, const c10::optiona
   at::Tensor src = mx_in(x), w = mx_out(wire);
   hipStream_t s = c10::hip::getCurrentHIPStreamMasqueradingAsCUDA(x.device().index()).stream();
   hipError_t e = sr    ? pdcc::kern::mx_quantize_shards_sr(src.data_ptr(), m, d, w.data_ptr(), cb, (size_t)world, seed,
-                                                           (uint32_t)sr_stream, index_offset, s, f)
-                 : res ? pdcc::kern::mx_quantize_shards_ef(src.data_ptr(), m, d, res, w.data_ptr(), cb, (size_t)world, s, f)
-                       : pdcc::kern::mx_quantize_shards(src.data_ptr(), m, d, w.data_ptr(), cb, (size_t)world, s, f);
+                                                           (uint32_t)sr_stream, index_offset, s, f, rt.ptr())
+                 : res ? pdcc::kern::mx_quantize_shards_ef(src.data_ptr(), m, d, res, w.data_ptr(), cb, (size_t)world, s, f,
+                                                           rt.ptr())
+                       : pdcc::kern::mx_quantize_shards(src.data_ptr(), m, d, w.data_ptr(), cb, (size_t)world, s, f,
+                                                        rt.ptr());
   TORCH_CHECK(e == hipSuccess, "mx_quantize_shards launch failed: ", hipGetErrorString(e));
   if (!w.is_same(wire)) wire.copy_(w);
   return wire;
 }
 
-void mx_dequantize_shards(const at::Tensor& wire, int world, at::Tensor& out, const std::string& fmt) {
+void mx_dequantize_shards(const at::Tensor& wire, int world, at::Tensor& out, const std::string& fmt, bool rot,
+                          uint64_t rot_seed) {
   const MxFormat f = mx_format(fmt, "mx_dequantize_shards");
+  const MxRot rt(rot, rot_seed);
   mx_check_wire(wire, "mx_dequantize_shards");
   TORCH_CHECK(world >= 1 && world <= 65535, "mx_dequantize_shards: world must be 1..65535");
   TORCH_CHECK(out.is_cuda() && out.device() == wire.device(), "mx_dequantize_shards: out must be on the wire's GPU");
@@ -260,13 +277,15 @@ void mx_dequantize_shards(const at::Tensor& wire, int world, at::Tensor& out, co
   c10::hip::HIPGuardMasqueradingAsCUDA g(wire.device());
   at::Tensor w = mx_in(wire), o = mx_out(out);
   hipStream_t s = c10::hip::getCurrentHIPStreamMasqueradingAsCUDA(wire.device().index()).stream();
-  hipError_t e = pdcc::kern::mx_dequantize_shards(w.data_ptr(), cb, (size_t)world, o.data_ptr(), m, d, s, f);
+  hipError_t e = pdcc::kern::mx_dequantize_shards(w.data_ptr(), cb, (size_t)world, o.data_ptr(), m, d, s, f, rt.ptr());
   TORCH_CHECK(e == hipSuccess, "mx_dequantize_shards launch failed: ", hipGetErrorString(e));
   if (!o.is_same(out)) out.copy_(o);
 }
 
-void mx_fold(const at::Tensor& wire, int nsrc, const std::string& op, at::Tensor& out, const std::string& fmt) {
+void mx_fold(const at::Tensor& wire, int nsrc, const std::string& op, at::Tensor& out, const std::string& fmt, bool rot,
+             uint64_t rot_seed) {
   const MxFormat f = mx_format(fmt, "mx_fold");
+  const MxRot rt(rot, rot_seed);
   mx_check_wire(wire, "mx_fold");
   TORCH_CHECK(nsrc >= 1 && nsrc <= pdcc::kern::kMaxRanks, "mx_fold: 1..8 sources");
   TORCH_CHECK_VALUE(op == "sum" || op == "avg", "mx_fold: op must be 'sum' or 'avg', got '", op, "'");
@@ -281,7 +300,7 @@ void mx_fold(const at::Tensor& wire, int nsrc, const std::string& op, at::Tensor
   c10::hip::HIPGuardMasqueradingAsCUDA g(wire.device());
   at::Tensor w = mx_in(wire), o = mx_out(out);
   hipStream_t s = c10::hip::getCurrentHIPStreamMasqueradingAsCUDA(wire.device().index()).stream();
-  hipError_t e = pdcc::kern::mx_fold(w.data_ptr(), nsrc, cb, kop(op), nsrc, o.data_ptr(), numel, d, s, f);
+  hipError_t e = pdcc::kern::mx_fold(w.data_ptr(), nsrc, cb, kop(op), nsrc, o.data_ptr(), numel, d, s, f, rt.ptr());
   TORCH_CHECK(e == hipSuccess, "mx_fold launch failed: ", hipGetErrorString(e));
   if (!o.is_same(out)) out.copy_(o);
 }
@@ -442,10 +461,11 @@ PYBIND11_MODULE(_C, m) {
         "K2: one-launch multi-tensor copy (max_blocks/depth 0 = defaults)");
   m.def("mx_quantize", &mx_quantize, py::arg("x"), py::arg("world") = 1, py::arg("out") = py::none(),
         py::arg("fmt") = "mxfp8_e4m3", py::arg("residual") = py::none(), py::arg("sr") = false, py::arg("seed") = 0,
-        py::arg("stream") = 0, py::arg("index_offset") = 0,
+        py::arg("stream") = 0, py::arg("index_offset") = 0, py::arg("rot") = false, py::arg("rot_seed") = 0,
         "tensor (f32 / bf16 / f16) -> mxfp8_e4m3 / mxfp4_e2m1 / mxfp6_e2m3 wire of `world` chunks, on the current stream; "
         "`residual`: one float per element of error feedback, added before and updated in place; `sr`: stochastic "
-        "rounding by the words of (seed, stream, index_offset + element index)");
+        "rounding by the words of (seed, stream, index_offset + element index); `rot`: every block rotated with the "
+        "sign word of `rot_seed` first (Hadamard rotation)");
   m.def("mx_reduce", &mx_reduce, py::arg("wire"), py::arg("nsrc"), py::arg("op") = "sum", py::arg("out") = py::none(),
         py::arg("fmt") = "mxfp8_e4m3", py::arg("residual") = py::none(), py::arg("sr") = false, py::arg("seed") = 0,
         py::arg("stream") = 0,
@@ -453,19 +473,24 @@ PYBIND11_MODULE(_C, m) {
         "`residual`: 32 cb floats of error feedback, updated in place; `sr`: stochastic requantization by the "
         "words of (seed, stream, index in the chunk)");
   m.def("mx_dequantize", &mx_dequantize, py::arg("wire"), py::arg("world"), py::arg("out"),
-        py::arg("fmt") = "mxfp8_e4m3",
-        "mxfp8_e4m3 / mxfp4_e2m1 / mxfp6_e2m3 wire of `world` chunks -> out (f32 / bf16 / f16), exactly out.numel() elements");
+        py::arg("fmt") = "mxfp8_e4m3", py::arg("rot") = false, py::arg("rot_seed") = 0,
+        "mxfp8_e4m3 / mxfp4_e2m1 / mxfp6_e2m3 wire of `world` chunks -> out (f32 / bf16 / f16), exactly out.numel() elements; "
+        "`rot`: every block rotated back with the sign word of `rot_seed`");
   m.def("mx_quantize_shards", &mx_quantize_shards, py::arg("x"), py::arg("world"), py::arg("out") = py::none(),
         py::arg("fmt") = "mxfp8_e4m3", py::arg("residual") = py::none(), py::arg("sr") = false, py::arg("seed") = 0,
-        py::arg("stream") = 0, py::arg("index_offset") = 0,
-        "tensor of `world` shards -> shard wire: chunk r is the wire of shard r alone; `residual` and `sr` as in "
+        py::arg("stream") = 0, py::arg("index_offset") = 0, py::arg("rot") = false, py::arg("rot_seed") = 0,
+        "tensor of `world` shards -> shard wire: chunk r is the wire of shard r alone; `residual`, `sr` and `rot` as in "
         "mx_quantize");
   m.def("mx_dequantize_shards", &mx_dequantize_shards, py::arg("wire"), py::arg("world"), py::arg("out"),
-        py::arg("fmt") = "mxfp8_e4m3",
-        "shard wire of `world` chunks -> out: chunk r fills out[r m, (r + 1) m), m = out.numel() / world");
+        py::arg("fmt") = "mxfp8_e4m3", py::arg("rot") = false, py::arg("rot_seed") = 0,
+        "shard wire of `world` chunks -> out: chunk r fills out[r m, (r + 1) m), m = out.numel() / world; `rot` as in "
+        "mx_dequantize");
   m.def("mx_fold", &mx_fold, py::arg("wire"), py::arg("nsrc"), py::arg("op"), py::arg("out"),
-        py::arg("fmt") = "mxfp8_e4m3",
-        "nsrc chunk wires of out.numel() elements -> out (dequantize, fold in f32 in source order, round once)");
+        py::arg("fmt") = "mxfp8_e4m3", py::arg("rot") = false, py::arg("rot_seed") = 0,
+        "nsrc chunk wires of out.numel() elements -> out (dequantize, fold in f32 in source order, round once); `rot`: "
+        "the fold rotated back before it is rounded");
+  m.def("mx_rotation_signs", [](uint64_t seed) { return pdcc::kern::mx_rot_signs(seed); }, py::arg("seed"),
+        "the sign word of a Hadamard rotation seed (kernels/mx_rot.h)");
   m.def("mx_shard_blocks", [](int64_t m, const std::string& fmt) {
     return (int64_t)pdcc::kern::mx_shard_blocks(mx_format(fmt, "mx_shard_blocks"), (size_t)m);
   }, py::arg("m"), py::arg("fmt") = "mxfp8_e4m3");

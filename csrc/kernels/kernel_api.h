@@ -330,38 +330,48 @@ hipError_t ipc_launch(const IpcView& view, const IpcCall& call, hipStream_t stre
 // aligned; `cb` (blocks per chunk) is a multiple of 16; `fmt` picks the payload (32 float8_e4m3fn
 // bytes, 16 bytes of e2m1 nibbles or 24 bytes of 6-bit e2m3 codes per block) and with it the chunk size
 // (33 cb, 17 cb or 25 cb bytes).
+// `rot_signs` (quantize, dequantize and fold; docs/collectives.md "Hadamard rotation", mx_rot.h): the sign
+// word of a call that rotates every 32-element block before it is quantized and back after it is
+// dequantized or folded; null: no rotation. mx_reduce folds rotated wires as they are.
 // Tensor (`t` in F32 / BF16 / F16, `numel` <= 32 cb nchunks elements) -> nchunks chunk wires. Every
 // block of every chunk is written (padding: scale 127, payload 0); nothing past src + numel is read.
 hipError_t mx_quantize(const void* src, size_t numel, DType t, void* wire, size_t cb, size_t nchunks,
-                       hipStream_t stream, MxFormat fmt = MxFormat::FP8_E4M3);
+                       hipStream_t stream, MxFormat fmt = MxFormat::FP8_E4M3,
+                       const uint32_t* rot_signs = nullptr);
 // `nsrc` (1..kMaxRanks) chunk wires back to back -> one chunk wire: dequantize, fold in f32 in source
 // order (`op` SUM or AVG; AVG divides by avg_div), requantize.
 hipError_t mx_reduce(const void* wire_in, int nsrc, size_t cb, RedOp op, int avg_div, void* wire_out,
                      hipStream_t stream, MxFormat fmt = MxFormat::FP8_E4M3);
 // nchunks chunk wires -> exactly `numel` elements of `dst`, rounded once to `t`.
 hipError_t mx_dequantize(const void* wire, size_t cb, size_t nchunks, void* dst, size_t numel, DType t,
-                         hipStream_t stream, MxFormat fmt = MxFormat::FP8_E4M3);
+                         hipStream_t stream, MxFormat fmt = MxFormat::FP8_E4M3,
+                         const uint32_t* rot_signs = nullptr);
 // The shard layout (mx_layout.h): chunk r is shard r, the `m` elements from r * m on, cb >=
 // mx_blocks(m). Quantize reads nchunks * m elements and writes every block of every chunk; dequantize
 // writes exactly dst[0, nchunks * m). 16-byte vectors when m * element size is a multiple of 16 (every
 // shard then starts aligned), single elements otherwise.
 hipError_t mx_quantize_shards(const void* src, size_t m, DType t, void* wire, size_t cb, size_t nchunks,
-                              hipStream_t stream, MxFormat fmt = MxFormat::FP8_E4M3);
+                              hipStream_t stream, MxFormat fmt = MxFormat::FP8_E4M3,
+                              const uint32_t* rot_signs = nullptr);
 hipError_t mx_dequantize_shards(const void* wire, size_t cb, size_t nchunks, void* dst, size_t m, DType t,
-                                hipStream_t stream, MxFormat fmt = MxFormat::FP8_E4M3);
+                                hipStream_t stream, MxFormat fmt = MxFormat::FP8_E4M3,
+                                const uint32_t* rot_signs = nullptr);
 // `nsrc` (1..kMaxRanks) chunk wires back to back -> exactly `numel` (1..32 cb) elements of `dst`:
 // dequantize, fold in f32 in source order (AVG divides by avg_div), round once to `t`. What mx_reduce
 // then mx_dequantize compute, without the requantization in between.
 hipError_t mx_fold(const void* wire_in, int nsrc, size_t cb, RedOp op, int avg_div, void* dst, size_t numel, DType t,
-                   hipStream_t stream, MxFormat fmt = MxFormat::FP8_E4M3);
+                   hipStream_t stream, MxFormat fmt = MxFormat::FP8_E4M3,
+                   const uint32_t* rot_signs = nullptr);
 // Error feedback (docs/collectives.md "Error feedback"): the same kernels with an f32 residual,
 // 16-byte aligned and updated in place. Quantize: one float per element of the tensor (`numel`, or
 // nchunks * m for shards); what is quantized is v = f32(x) + residual, and the residual becomes
 // v - D(Q(v)) where that is finite, +0 elsewhere. `src` is not modified; `numel` == 0 touches no residual.
 hipError_t mx_quantize_ef(const void* src, size_t numel, DType t, float* residual, void* wire, size_t cb,
-                          size_t nchunks, hipStream_t stream, MxFormat fmt = MxFormat::FP8_E4M3);
+                          size_t nchunks, hipStream_t stream, MxFormat fmt = MxFormat::FP8_E4M3,
+                          const uint32_t* rot_signs = nullptr);
 hipError_t mx_quantize_shards_ef(const void* src, size_t m, DType t, float* residual, void* wire, size_t cb,
-                                 size_t nchunks, hipStream_t stream, MxFormat fmt = MxFormat::FP8_E4M3);
+                                 size_t nchunks, hipStream_t stream, MxFormat fmt = MxFormat::FP8_E4M3,
+                                 const uint32_t* rot_signs = nullptr);
 // Reduce: 32 cb floats, one per element of the chunk, added to the fold (after the AVG division) before
 // it is quantized again and replaced by what that quantization dropped.
 hipError_t mx_reduce_ef(const void* wire_in, int nsrc, size_t cb, RedOp op, int avg_div, float* residual,
@@ -372,10 +382,12 @@ hipError_t mx_reduce_ef(const void* wire_in, int nsrc, size_t cb, RedOp op, int 
 // `index_offset` plus the element's index in the tensor, in both layouts (the sum must fit 64 bits).
 hipError_t mx_quantize_sr(const void* src, size_t numel, DType t, void* wire, size_t cb, size_t nchunks,
                           uint64_t seed, uint32_t sr_stream, uint64_t index_offset, hipStream_t stream,
-                          MxFormat fmt = MxFormat::FP8_E4M3);
+                          MxFormat fmt = MxFormat::FP8_E4M3,
+                          const uint32_t* rot_signs = nullptr);
 hipError_t mx_quantize_shards_sr(const void* src, size_t m, DType t, void* wire, size_t cb, size_t nchunks,
                                  uint64_t seed, uint32_t sr_stream, uint64_t index_offset, hipStream_t stream,
-                                 MxFormat fmt = MxFormat::FP8_E4M3);
+                                 MxFormat fmt = MxFormat::FP8_E4M3,
+                                 const uint32_t* rot_signs = nullptr);
 // Reduce: the index is the element's index in the chunk, 0 .. 32 cb - 1.
 hipError_t mx_reduce_sr(const void* wire_in, int nsrc, size_t cb, RedOp op, int avg_div, void* wire_out, uint64_t seed,
                         uint32_t sr_stream, hipStream_t stream, MxFormat fmt = MxFormat::FP8_E4M3);

@@ -47,6 +47,7 @@
 
 #include "dev_common.h"
 #include "mx_layout.h"
+#include "mx_rot.h"
 #include "mx_sr.h"
 
 namespace pdcc {
@@ -76,6 +77,76 @@ __device__ __forceinline__ uint32_t group_max(uint32_t x) {
 }
 
 __device__ __forceinline__ uint32_t abs_bits(float f) { return __float_as_uint(f) & 0x7fffffffu; }
+
+// ---- Hadamard rotation (mx_rot.h, docs/collectives.md "Hadamard rotation"). A lane holds the EPL elements
+// from position `place * EPL` of its block, place = v % LPB. The butterfly stages below EPL pair elements
+// of the lane, the later ones pair the lane with lane ^ 1, ^ 2 and (f32) ^ 4 of its block: quad_perm for
+// the first two, row_shl:4 for the low and row_shr:4 for the high four lanes of the eight (row_half_mirror
+// would pair i with 7 - i). The low lane of a pair keeps a + b and the high one a - b; as the sum of the
+// partner's value and its own with the sign flipped that is one v_add_f32 whose operand comes through DPP.
+// Every lane of the block must be active. Contraction is off inside: the order of the f32 roundings is the
+// definition, also where a dequantized operand's product with its scale overflows.
+constexpr int kDppRowShl4 = 0x104, kDppRowShr4 = 0x114;
+template <int CTRL>
+__device__ __forceinline__ float dpp_f32(float x) {
+  return __uint_as_float((uint32_t)__builtin_amdgcn_update_dpp(0, (int)__float_as_uint(x), CTRL, 0xf, 0xf, true));
+}
+template <int EPL>
+__device__ __forceinline__ void rot_flip(float* f, uint32_t signs, uint32_t place) {
+  const uint32_t s = signs >> (place * EPL);
+#pragma unroll
+  for (int i = 0; i < EPL; ++i) f[i] = __uint_as_float(__float_as_uint(f[i]) ^ ((s >> i) << 31));
+}
+// stage h = EPL * X of the butterfly: the exchange with lane ^ X
+template <int EPL, int X>
+__device__ __forceinline__ void rot_exchange(float* f, uint32_t place) {
+#pragma clang fp contract(off)  // (one f32 add each: nothing fused with the product that made an operand)
+  const bool high = (place & X) != 0;
+  const uint32_t flip = high ? 0x80000000u : 0u;
+#pragma unroll
+  for (int i = 0; i < EPL; ++i) {
+    float p;
+    if constexpr (X == 1) p = dpp_f32<kDppXor1>(f[i]);
+    else if constexpr (X == 2) p = dpp_f32<kDppXor2>(f[i]);
+    else {
+      const float up = dpp_f32<kDppRowShl4>(f[i]), down = dpp_f32<kDppRowShr4>(f[i]);
+      p = high ? down : up;
+    }
+    f[i] = p + __uint_as_float(__float_as_uint(f[i]) ^ flip);  // low: b + a, high: a - b
+  }
+}
+template <int EPL>
+__device__ __forceinline__ void rot_butterfly(float* f, uint32_t place) {
+#pragma clang fp contract(off)
+#pragma unroll
+  for (int h = 1; h < EPL; h <<= 1) {
+#pragma unroll
+    for (int j = 0; j < EPL; ++j) {
+      if ((j & h) == 0) {
+        const float a = f[j], b = f[j + h];
+        f[j] = a + b;
+        f[j + h] = a - b;
+      }
+    }
+  }
+  rot_exchange<EPL, 1>(f, place);
+  rot_exchange<EPL, 2>(f, place);
+  if constexpr (EPL == 4) rot_exchange<EPL, 4>(f, place);
+}
+// R x: signs, then the butterfly
+template <int EPL>
+__device__ __forceinline__ void rot_forward(float* f, uint32_t signs, uint32_t place) {
+  rot_flip<EPL>(f, signs, place);
+  rot_butterfly<EPL>(f, place);
+}
+// R^-1 d: the butterfly, one multiply by 2^-5, then the signs
+template <int EPL>
+__device__ __forceinline__ void rot_inverse(float* f, uint32_t signs, uint32_t place) {
+  rot_butterfly<EPL>(f, place);
+#pragma unroll
+  for (int i = 0; i < EPL; ++i) f[i] *= 0.03125f;
+  rot_flip<EPL>(f, signs, place);
+}
 
 // Scale of a block from max |x| as f32 bits: the byte, 2^-e for the payload, and whether the
 // payload is written as zeros (an all-zero block, or one that holds an inf / a NaN).
@@ -425,10 +496,15 @@ __device__ __forceinline__ void st_wire(char* p, const uint32_t* q) {
 // SR (stochastic rounding, never together with EF): the payload is rounded up or down by the word of
 // the element's index, `sr_base` plus its index in the tensor -- the same in the dealt and the shard
 // layout. The lane computes its EPL words itself; the scale byte and everything else are unchanged.
-template <MxFormat F, DType DT, bool SHARD, bool VEC, bool EF, bool SR>
+//
+// ROT (docs/collectives.md "Hadamard rotation"): every block is rotated (rot_forward) right after it is
+// widened, padding zeros included, so the residual is added to and taken from the rotated block.
+// `rot_signs` is the call's sign word.
+template <MxFormat F, DType DT, bool SHARD, bool VEC, bool EF, bool SR, bool ROT>
 __global__ __launch_bounds__(256) void k_mx_quantize(const char* __restrict__ src, size_t numel,
                                                      char* __restrict__ wire, uint32_t cb, size_t m,
-                                                     float* __restrict__ res, uint32_t sr_key, uint64_t sr_base) {
+                                                     float* __restrict__ res, uint32_t sr_key, uint64_t sr_base,
+                                                     uint32_t rot_signs) {
   static_assert(!(EF && SR), "error feedback and stochastic rounding are alternatives");
   using T = Tr<DT>;
   using S = typename T::S;
@@ -479,9 +555,14 @@ __global__ __launch_bounds__(256) void k_mx_quantize(const char* __restrict__ sr
       if (v >= nvec) break;  // (whole waves leave together: nvec and every span start are multiples of 64)
       float f[EPL];
       uint32_t am = 0;
+      if constexpr (ROT) {  // (whole blocks are here: nvec is a multiple of LPB)
+#pragma unroll
+        for (int i = 0; i < EPL; ++i) f[i] = T::in(s[u][i]);
+        rot_forward<EPL>(f, rot_signs, v % LPB);
+      }
 #pragma unroll
       for (int i = 0; i < EPL; ++i) {
-        f[i] = T::in(s[u][i]);
+        if constexpr (!ROT) f[i] = T::in(s[u][i]);
         if constexpr (EF) f[i] += r[u][i];
         const uint32_t a = abs_bits(f[i]);
         am = a > am ? a : am;
@@ -521,9 +602,14 @@ __global__ __launch_bounds__(256) void k_mx_quantize(const char* __restrict__ sr
 // The same lane layout as quantize: a lane reads EPL payload bytes and its block's scale byte and
 // stores 16 B of the tensor; nothing at or past `numel` is written. SHARD / VEC as in quantize:
 // chunk r fills exactly dst[r m, (r + 1) m).
-template <MxFormat F, DType DT, bool SHARD, bool VEC>
+//
+// ROT: the block is rotated back (rot_inverse) before the cast. Its lanes exchange values, so the lanes of
+// a partial last block all load, convert and take part -- the vectors are counted in whole blocks -- and
+// only the stores are masked.
+template <MxFormat F, DType DT, bool SHARD, bool VEC, bool ROT>
 __global__ __launch_bounds__(256) void k_mx_dequantize(const char* __restrict__ wire, uint32_t cb,
-                                                       char* __restrict__ dst, size_t numel, size_t m) {
+                                                       char* __restrict__ dst, size_t numel, size_t m,
+                                                       uint32_t rot_signs) {
   using T = Tr<DT>;
   using S = typename T::S;
   constexpr int EPL = 16 / (int)sizeof(S);
@@ -536,7 +622,8 @@ __global__ __launch_bounds__(256) void k_mx_dequantize(const char* __restrict__ 
   if (el0 >= numel) return;  // a padding chunk
   const size_t left = SHARD ? m : numel - el0;
   // vectors of this chunk that hold at least one element of the tensor
-  const uint32_t nvec = (uint32_t)(left >= (size_t)cb * kern::kMxBlock ? (size_t)cb * LPB : (left + EPL - 1) / EPL);
+  uint32_t nvec = (uint32_t)(left >= (size_t)cb * kern::kMxBlock ? (size_t)cb * LPB : (left + EPL - 1) / EPL);
+  if constexpr (ROT) nvec = (nvec + LPB - 1) / LPB * LPB;  // (<= cb * LPB, itself a multiple of LPB)
   constexpr uint32_t stride = 256u;  // (contiguous spans per workgroup, as in quantize)
   const uint32_t pass = gridDim.x * 256u * kMxUnroll;
   for (uint32_t v0 = blockIdx.x * 256u * kMxUnroll + threadIdx.x; v0 < nvec; v0 += pass) {
@@ -567,6 +654,7 @@ __global__ __launch_bounds__(256) void k_mx_dequantize(const char* __restrict__ 
       const float scale = mx_scale_value(sb[u]);
       float f[EPL];
       M::template unpack<EPL>(q[u], scale, f);
+      if constexpr (ROT) rot_inverse<EPL>(f, rot_signs, v % LPB);
       S s[EPL];
 #pragma unroll
       for (int i = 0; i < EPL; ++i) s[i] = T::out(f[i]);
@@ -687,9 +775,12 @@ __global__ __launch_bounds__(256) void k_mx_reduce(const char* __restrict__ in, 
 template <int NSRC>
 constexpr int kMxFoldUnroll = NSRC <= 2 ? 4 : (NSRC <= 4 ? 2 : 1);
 
-template <MxFormat F, DType DT, int NSRC, bool AVG>
+//
+// ROT: the sources are folded as they are (the rotation is linear) and the fold is rotated back after the
+// AVG division and before the cast; whole blocks take part, as in dequantize.
+template <MxFormat F, DType DT, int NSRC, bool AVG, bool ROT>
 __global__ __launch_bounds__(256) void k_mx_fold(const char* __restrict__ in, uint32_t cb, int avg_div,
-                                                 char* __restrict__ dst, size_t numel) {
+                                                 char* __restrict__ dst, size_t numel, uint32_t rot_signs) {
   using T = Tr<DT>;
   using S = typename T::S;
   constexpr int EPL = 16 / (int)sizeof(S);
@@ -698,7 +789,8 @@ __global__ __launch_bounds__(256) void k_mx_fold(const char* __restrict__ in, ui
   using M = MxFmt<F>;
   constexpr int QB = EPL * M::kPayload / kern::kMxBlock, QW = M::template kWords<EPL>;
   const size_t cbytes = kern::mx_chunk_bytes(F, cb);
-  const uint32_t nvec = (uint32_t)((numel + EPL - 1) / EPL);  // <= cb * LPB: numel <= 32 cb
+  uint32_t nvec = (uint32_t)((numel + EPL - 1) / EPL);  // <= cb * LPB: numel <= 32 cb
+  if constexpr (ROT) nvec = (nvec + LPB - 1) / LPB * LPB;
   const uint32_t pass = gridDim.x * 256u * U;
   for (uint32_t v0 = blockIdx.x * 256u * U + threadIdx.x; v0 < nvec; v0 += pass) {
     uint32_t q[U][NSRC][QW];
@@ -744,6 +836,7 @@ __global__ __launch_bounds__(256) void k_mx_fold(const char* __restrict__ in, ui
 #pragma unroll
         for (int i = 0; i < EPL; ++i) acc[i] = acc[i] / (float)avg_div;
       }
+      if constexpr (ROT) rot_inverse<EPL>(acc, rot_signs, v % LPB);
       S s[EPL];
 #pragma unroll
       for (int i = 0; i < EPL; ++i) s[i] = T::out(acc[i]);
@@ -799,27 +892,40 @@ struct MxSr {
   uint64_t base;
 };
 // quantize / dequantize of one format and dtype: the dealt kernel, or the shard one with or without vectors
-template <MxFormat F, DType DT, bool EF, bool SR>
+template <MxFormat F, DType DT, bool EF, bool SR, bool ROT>
 void mx_quantize_ef_go(bool shard, bool vec, const dim3& grid, const char* s, size_t numel, char* w, uint32_t cb,
-                       size_t m, float* res, uint32_t key, uint64_t base, hipStream_t stream) {
-  if (!shard) hipLaunchKernelGGL((dev::k_mx_quantize<F, DT, false, true, EF, SR>), grid, dim3(256), 0, stream, s, numel, w, cb, m, res, key, base);
-  else if (vec) hipLaunchKernelGGL((dev::k_mx_quantize<F, DT, true, true, EF, SR>), grid, dim3(256), 0, stream, s, numel, w, cb, m, res, key, base);
-  else hipLaunchKernelGGL((dev::k_mx_quantize<F, DT, true, false, EF, SR>), grid, dim3(256), 0, stream, s, numel, w, cb, m, res, key, base);
+                       size_t m, float* res, uint32_t key, uint64_t base, uint32_t signs, hipStream_t stream) {
+  if (!shard) hipLaunchKernelGGL((dev::k_mx_quantize<F, DT, false, true, EF, SR, ROT>), grid, dim3(256), 0, stream, s, numel, w, cb, m, res, key, base, signs);
+  else if (vec) hipLaunchKernelGGL((dev::k_mx_quantize<F, DT, true, true, EF, SR, ROT>), grid, dim3(256), 0, stream, s, numel, w, cb, m, res, key, base, signs);
+  else hipLaunchKernelGGL((dev::k_mx_quantize<F, DT, true, false, EF, SR, ROT>), grid, dim3(256), 0, stream, s, numel, w, cb, m, res, key, base, signs);
 }
 // (`sr`: the stochastic kernels; else `res` null: the plain kernels; otherwise the error-feedback ones)
+template <MxFormat F, DType DT, bool ROT>
+void mx_quantize_rot_go(bool shard, bool vec, const dim3& grid, const char* s, size_t numel, char* w, uint32_t cb, size_t m,
+                        float* res, const MxSr* sr, uint32_t signs, hipStream_t stream) {
+  if (sr) mx_quantize_ef_go<F, DT, false, true, ROT>(shard, vec, grid, s, numel, w, cb, m, nullptr, sr->key, sr->base, signs, stream);
+  else if (res) mx_quantize_ef_go<F, DT, true, false, ROT>(shard, vec, grid, s, numel, w, cb, m, res, 0u, 0u, signs, stream);
+  else mx_quantize_ef_go<F, DT, false, false, ROT>(shard, vec, grid, s, numel, w, cb, m, res, 0u, 0u, signs, stream);
+}
+// (`rot`: the sign word of the rotated kernels; null: the kernels without the rotation)
 template <MxFormat F, DType DT>
 void mx_quantize_go(bool shard, bool vec, const dim3& grid, const char* s, size_t numel, char* w, uint32_t cb, size_t m,
-                    float* res, const MxSr* sr, hipStream_t stream) {
-  if (sr) mx_quantize_ef_go<F, DT, false, true>(shard, vec, grid, s, numel, w, cb, m, nullptr, sr->key, sr->base, stream);
-  else if (res) mx_quantize_ef_go<F, DT, true, false>(shard, vec, grid, s, numel, w, cb, m, res, 0u, 0u, stream);
-  else mx_quantize_ef_go<F, DT, false, false>(shard, vec, grid, s, numel, w, cb, m, res, 0u, 0u, stream);
+                    float* res, const MxSr* sr, const uint32_t* rot, hipStream_t stream) {
+  if (rot) mx_quantize_rot_go<F, DT, true>(shard, vec, grid, s, numel, w, cb, m, res, sr, *rot, stream);
+  else mx_quantize_rot_go<F, DT, false>(shard, vec, grid, s, numel, w, cb, m, res, sr, 0u, stream);
+}
+template <MxFormat F, DType DT, bool ROT>
+void mx_dequantize_rot_go(bool shard, bool vec, const dim3& grid, const char* w, uint32_t cb, char* d, size_t numel, size_t m,
+                          uint32_t signs, hipStream_t stream) {
+  if (!shard) hipLaunchKernelGGL((dev::k_mx_dequantize<F, DT, false, true, ROT>), grid, dim3(256), 0, stream, w, cb, d, numel, m, signs);
+  else if (vec) hipLaunchKernelGGL((dev::k_mx_dequantize<F, DT, true, true, ROT>), grid, dim3(256), 0, stream, w, cb, d, numel, m, signs);
+  else hipLaunchKernelGGL((dev::k_mx_dequantize<F, DT, true, false, ROT>), grid, dim3(256), 0, stream, w, cb, d, numel, m, signs);
 }
 template <MxFormat F, DType DT>
 void mx_dequantize_go(bool shard, bool vec, const dim3& grid, const char* w, uint32_t cb, char* d, size_t numel, size_t m,
-                      hipStream_t stream) {
-  if (!shard) hipLaunchKernelGGL((dev::k_mx_dequantize<F, DT, false, true>), grid, dim3(256), 0, stream, w, cb, d, numel, m);
-  else if (vec) hipLaunchKernelGGL((dev::k_mx_dequantize<F, DT, true, true>), grid, dim3(256), 0, stream, w, cb, d, numel, m);
-  else hipLaunchKernelGGL((dev::k_mx_dequantize<F, DT, true, false>), grid, dim3(256), 0, stream, w, cb, d, numel, m);
+                      const uint32_t* rot, hipStream_t stream) {
+  if (rot) mx_dequantize_rot_go<F, DT, true>(shard, vec, grid, w, cb, d, numel, m, *rot, stream);
+  else mx_dequantize_rot_go<F, DT, false>(shard, vec, grid, w, cb, d, numel, m, 0u, stream);
 }
 template <MxFormat F, class... A>
 void mx_quantize_dt(DType t, A... a) {
@@ -838,101 +944,102 @@ void mx_dequantize_dt(DType t, A... a) {
   }
 }
 hipError_t mx_quantize_any(MxFormat fmt, DType t, bool shard, bool vec, const void* src, size_t numel, void* wire,
-                           size_t cb, size_t nchunks, size_t m, hipStream_t stream, float* res = nullptr,
-                           const MxSr* sr = nullptr) {
+                           size_t cb, size_t nchunks, size_t m, hipStream_t stream, const uint32_t* rot,
+                           float* res = nullptr, const MxSr* sr = nullptr) {
   const dim3 grid = mx_stream_grid(cb, t, nchunks);
   const char* s = static_cast<const char*>(src);
   char* w = static_cast<char*>(wire);
-  if (fmt == MxFormat::FP4_E2M1) mx_quantize_dt<MxFormat::FP4_E2M1>(t, shard, vec, grid, s, numel, w, (uint32_t)cb, m, res, sr, stream);
-  else if (fmt == MxFormat::FP6_E2M3) mx_quantize_dt<MxFormat::FP6_E2M3>(t, shard, vec, grid, s, numel, w, (uint32_t)cb, m, res, sr, stream);
-  else mx_quantize_dt<MxFormat::FP8_E4M3>(t, shard, vec, grid, s, numel, w, (uint32_t)cb, m, res, sr, stream);
+  if (fmt == MxFormat::FP4_E2M1) mx_quantize_dt<MxFormat::FP4_E2M1>(t, shard, vec, grid, s, numel, w, (uint32_t)cb, m, res, sr, rot, stream);
+  else if (fmt == MxFormat::FP6_E2M3) mx_quantize_dt<MxFormat::FP6_E2M3>(t, shard, vec, grid, s, numel, w, (uint32_t)cb, m, res, sr, rot, stream);
+  else mx_quantize_dt<MxFormat::FP8_E4M3>(t, shard, vec, grid, s, numel, w, (uint32_t)cb, m, res, sr, rot, stream);
   return hipGetLastError();
 }
 hipError_t mx_dequantize_any(MxFormat fmt, DType t, bool shard, bool vec, const void* wire, size_t cb, size_t nchunks,
-                             void* dst, size_t numel, size_t m, hipStream_t stream) {
+                             void* dst, size_t numel, size_t m, hipStream_t stream, const uint32_t* rot) {
   const dim3 grid = mx_stream_grid(cb, t, nchunks);
   const char* w = static_cast<const char*>(wire);
   char* d = static_cast<char*>(dst);
-  if (fmt == MxFormat::FP4_E2M1) mx_dequantize_dt<MxFormat::FP4_E2M1>(t, shard, vec, grid, w, (uint32_t)cb, d, numel, m, stream);
-  else if (fmt == MxFormat::FP6_E2M3) mx_dequantize_dt<MxFormat::FP6_E2M3>(t, shard, vec, grid, w, (uint32_t)cb, d, numel, m, stream);
-  else mx_dequantize_dt<MxFormat::FP8_E4M3>(t, shard, vec, grid, w, (uint32_t)cb, d, numel, m, stream);
+  if (fmt == MxFormat::FP4_E2M1) mx_dequantize_dt<MxFormat::FP4_E2M1>(t, shard, vec, grid, w, (uint32_t)cb, d, numel, m, rot, stream);
+  else if (fmt == MxFormat::FP6_E2M3) mx_dequantize_dt<MxFormat::FP6_E2M3>(t, shard, vec, grid, w, (uint32_t)cb, d, numel, m, rot, stream);
+  else mx_dequantize_dt<MxFormat::FP8_E4M3>(t, shard, vec, grid, w, (uint32_t)cb, d, numel, m, rot, stream);
   return hipGetLastError();
 }
 }  // namespace
 
 hipError_t mx_quantize(const void* src, size_t numel, DType t, void* wire, size_t cb, size_t nchunks,
-                       hipStream_t stream, MxFormat fmt) {
+                       hipStream_t stream, MxFormat fmt, const uint32_t* rot_signs) {
   if (!mx_fmt_ok(fmt) || !mx_dtype_ok(t)) return hipErrorInvalidValue;
   if (!mx_cb_ok(cb) || nchunks == 0 || nchunks > 65535 || !mx_al16(wire) || (numel && !mx_al16(src)))
     return hipErrorInvalidValue;
   if (numel > cb * nchunks * kMxBlock) return hipErrorInvalidValue;
-  return mx_quantize_any(fmt, t, false, true, src, numel, wire, cb, nchunks, 0, stream);
+  return mx_quantize_any(fmt, t, false, true, src, numel, wire, cb, nchunks, 0, stream, rot_signs);
 }
 
 hipError_t mx_dequantize(const void* wire, size_t cb, size_t nchunks, void* dst, size_t numel, DType t,
-                         hipStream_t stream, MxFormat fmt) {
+                         hipStream_t stream, MxFormat fmt, const uint32_t* rot_signs) {
   if (!mx_fmt_ok(fmt) || !mx_dtype_ok(t)) return hipErrorInvalidValue;
   if (!mx_cb_ok(cb) || nchunks == 0 || nchunks > 65535 || !mx_al16(wire) || (numel && !mx_al16(dst)))
     return hipErrorInvalidValue;
   if (numel > cb * nchunks * kMxBlock) return hipErrorInvalidValue;
   if (numel == 0) return hipSuccess;
-  return mx_dequantize_any(fmt, t, false, true, wire, cb, nchunks, dst, numel, 0, stream);
+  return mx_dequantize_any(fmt, t, false, true, wire, cb, nchunks, dst, numel, 0, stream, rot_signs);
 }
 
 hipError_t mx_quantize_shards(const void* src, size_t m, DType t, void* wire, size_t cb, size_t nchunks,
-                              hipStream_t stream, MxFormat fmt) {
+                              hipStream_t stream, MxFormat fmt, const uint32_t* rot_signs) {
   if (!mx_fmt_ok(fmt) || !mx_dtype_ok(t)) return hipErrorInvalidValue;
   if (!mx_shards_ok(m, cb, nchunks) || !mx_al16(wire) || !mx_al16(src)) return hipErrorInvalidValue;
   const bool vec = m * mx_esize(t) % 16 == 0;  // every shard starts 16-byte aligned
-  return mx_quantize_any(fmt, t, true, vec, src, m * nchunks, wire, cb, nchunks, m, stream);
+  return mx_quantize_any(fmt, t, true, vec, src, m * nchunks, wire, cb, nchunks, m, stream, rot_signs);
 }
 
 hipError_t mx_quantize_ef(const void* src, size_t numel, DType t, float* residual, void* wire, size_t cb,
-                          size_t nchunks, hipStream_t stream, MxFormat fmt) {
+                          size_t nchunks, hipStream_t stream, MxFormat fmt, const uint32_t* rot_signs) {
   if (!mx_fmt_ok(fmt) || !mx_dtype_ok(t)) return hipErrorInvalidValue;
   if (!mx_cb_ok(cb) || nchunks == 0 || nchunks > 65535 || !mx_al16(wire) || (numel && !mx_al16(src)))
     return hipErrorInvalidValue;
   if (numel > cb * nchunks * kMxBlock || (numel && (!residual || !mx_al16(residual)))) return hipErrorInvalidValue;
   // (no elements: no residual to update, the wire is all padding blocks)
-  return mx_quantize_any(fmt, t, false, true, src, numel, wire, cb, nchunks, 0, stream, numel ? residual : nullptr);
+  return mx_quantize_any(fmt, t, false, true, src, numel, wire, cb, nchunks, 0, stream, rot_signs, numel ? residual : nullptr);
 }
 
 hipError_t mx_quantize_shards_ef(const void* src, size_t m, DType t, float* residual, void* wire, size_t cb,
-                                 size_t nchunks, hipStream_t stream, MxFormat fmt) {
+                                 size_t nchunks, hipStream_t stream, MxFormat fmt, const uint32_t* rot_signs) {
   if (!mx_fmt_ok(fmt) || !mx_dtype_ok(t)) return hipErrorInvalidValue;
   if (!mx_shards_ok(m, cb, nchunks) || !mx_al16(wire) || !mx_al16(src) || !residual || !mx_al16(residual))
     return hipErrorInvalidValue;
   const bool vec = m * mx_esize(t) % 16 == 0;  // every shard, and its slice of the residual, starts 16-byte aligned
-  return mx_quantize_any(fmt, t, true, vec, src, m * nchunks, wire, cb, nchunks, m, stream, residual);
+  return mx_quantize_any(fmt, t, true, vec, src, m * nchunks, wire, cb, nchunks, m, stream, rot_signs, residual);
 }
 
 hipError_t mx_quantize_sr(const void* src, size_t numel, DType t, void* wire, size_t cb, size_t nchunks,
-                          uint64_t seed, uint32_t sr_stream, uint64_t index_offset, hipStream_t stream, MxFormat fmt) {
+                          uint64_t seed, uint32_t sr_stream, uint64_t index_offset, hipStream_t stream, MxFormat fmt,
+                          const uint32_t* rot_signs) {
   if (!mx_fmt_ok(fmt) || !mx_dtype_ok(t)) return hipErrorInvalidValue;
   if (!mx_cb_ok(cb) || nchunks == 0 || nchunks > 65535 || !mx_al16(wire) || (numel && !mx_al16(src)))
     return hipErrorInvalidValue;
   if (numel > cb * nchunks * kMxBlock || index_offset + numel < index_offset) return hipErrorInvalidValue;
   const MxSr sr{mx_sr_key(seed, sr_stream), index_offset};
-  return mx_quantize_any(fmt, t, false, true, src, numel, wire, cb, nchunks, 0, stream, nullptr, &sr);
+  return mx_quantize_any(fmt, t, false, true, src, numel, wire, cb, nchunks, 0, stream, rot_signs, nullptr, &sr);
 }
 
 hipError_t mx_quantize_shards_sr(const void* src, size_t m, DType t, void* wire, size_t cb, size_t nchunks,
                                  uint64_t seed, uint32_t sr_stream, uint64_t index_offset, hipStream_t stream,
-                                 MxFormat fmt) {
+                                 MxFormat fmt, const uint32_t* rot_signs) {
   if (!mx_fmt_ok(fmt) || !mx_dtype_ok(t)) return hipErrorInvalidValue;
   if (!mx_shards_ok(m, cb, nchunks) || !mx_al16(wire) || !mx_al16(src)) return hipErrorInvalidValue;
   if (index_offset + m * nchunks < index_offset) return hipErrorInvalidValue;
   const bool vec = m * mx_esize(t) % 16 == 0;
   const MxSr sr{mx_sr_key(seed, sr_stream), index_offset};
-  return mx_quantize_any(fmt, t, true, vec, src, m * nchunks, wire, cb, nchunks, m, stream, nullptr, &sr);
+  return mx_quantize_any(fmt, t, true, vec, src, m * nchunks, wire, cb, nchunks, m, stream, rot_signs, nullptr, &sr);
 }
 
 hipError_t mx_dequantize_shards(const void* wire, size_t cb, size_t nchunks, void* dst, size_t m, DType t,
-                                hipStream_t stream, MxFormat fmt) {
+                                hipStream_t stream, MxFormat fmt, const uint32_t* rot_signs) {
   if (!mx_fmt_ok(fmt) || !mx_dtype_ok(t)) return hipErrorInvalidValue;
   if (!mx_shards_ok(m, cb, nchunks) || !mx_al16(wire) || !mx_al16(dst)) return hipErrorInvalidValue;
   const bool vec = m * mx_esize(t) % 16 == 0;
-  return mx_dequantize_any(fmt, t, true, vec, wire, cb, nchunks, dst, m * nchunks, m, stream);
+  return mx_dequantize_any(fmt, t, true, vec, wire, cb, nchunks, dst, m * nchunks, m, stream, rot_signs);
 }
 
 namespace {
@@ -995,17 +1102,18 @@ hipError_t mx_reduce_sr(const void* wire_in, int nsrc, size_t cb, RedOp op, int 
 }
 
 namespace {
-template <MxFormat F, DType DT, bool AVG>
-hipError_t mx_fold_go(const char* in, int nsrc, uint32_t cb, int avg_div, char* dst, size_t numel, hipStream_t stream) {
+template <MxFormat F, DType DT, bool AVG, bool ROT>
+hipError_t mx_fold_go(const char* in, int nsrc, uint32_t cb, int avg_div, char* dst, size_t numel, uint32_t signs,
+                      hipStream_t stream) {
   constexpr int epl = 16 / (int)sizeof(typename dev::Tr<DT>::S);
   const uint64_t nvec = (numel + epl - 1) / epl;
   const dim3 block(256);
   switch (nsrc) {
-#define PDCC_MX_N(N)                                                                                           \
-  case N: {                                                                                                    \
-    const dim3 grid(dev::mx_grid_x(nvec, dev::kMxFoldUnroll<N>, 1, dev::kMxGridReduce));                       \
-    hipLaunchKernelGGL((dev::k_mx_fold<F, DT, N, AVG>), grid, block, 0, stream, in, cb, avg_div, dst, numel); \
-    break;                                                                                                     \
+#define PDCC_MX_N(N)                                                                                                       \
+  case N: {                                                                                                                \
+    const dim3 grid(dev::mx_grid_x(nvec, dev::kMxFoldUnroll<N>, 1, dev::kMxGridReduce));                                   \
+    hipLaunchKernelGGL((dev::k_mx_fold<F, DT, N, AVG, ROT>), grid, block, 0, stream, in, cb, avg_div, dst, numel, signs); \
+    break;                                                                                                                 \
   }
     PDCC_MX_N(1) PDCC_MX_N(2) PDCC_MX_N(3) PDCC_MX_N(4) PDCC_MX_N(5) PDCC_MX_N(6) PDCC_MX_N(7) PDCC_MX_N(8)
 #undef PDCC_MX_N
@@ -1015,24 +1123,27 @@ hipError_t mx_fold_go(const char* in, int nsrc, uint32_t cb, int avg_div, char* 
 }
 template <MxFormat F, DType DT>
 hipError_t mx_fold_op(const char* in, int nsrc, uint32_t cb, RedOp op, int avg_div, char* dst, size_t numel,
-                      hipStream_t stream) {
-  return op == RedOp::AVG ? mx_fold_go<F, DT, true>(in, nsrc, cb, avg_div, dst, numel, stream)
-                          : mx_fold_go<F, DT, false>(in, nsrc, cb, avg_div, dst, numel, stream);
+                      const uint32_t* rot, hipStream_t stream) {
+  if (rot)
+    return op == RedOp::AVG ? mx_fold_go<F, DT, true, true>(in, nsrc, cb, avg_div, dst, numel, *rot, stream)
+                            : mx_fold_go<F, DT, false, true>(in, nsrc, cb, avg_div, dst, numel, *rot, stream);
+  return op == RedOp::AVG ? mx_fold_go<F, DT, true, false>(in, nsrc, cb, avg_div, dst, numel, 0u, stream)
+                          : mx_fold_go<F, DT, false, false>(in, nsrc, cb, avg_div, dst, numel, 0u, stream);
 }
 template <MxFormat F>
 hipError_t mx_fold_dt(DType t, const char* in, int nsrc, uint32_t cb, RedOp op, int avg_div, char* d, size_t numel,
-                      hipStream_t stream) {
+                      const uint32_t* rot, hipStream_t stream) {
   switch (t) {
-    case DType::F32: return mx_fold_op<F, DType::F32>(in, nsrc, cb, op, avg_div, d, numel, stream);
-    case DType::BF16: return mx_fold_op<F, DType::BF16>(in, nsrc, cb, op, avg_div, d, numel, stream);
-    case DType::F16: return mx_fold_op<F, DType::F16>(in, nsrc, cb, op, avg_div, d, numel, stream);
+    case DType::F32: return mx_fold_op<F, DType::F32>(in, nsrc, cb, op, avg_div, d, numel, rot, stream);
+    case DType::BF16: return mx_fold_op<F, DType::BF16>(in, nsrc, cb, op, avg_div, d, numel, rot, stream);
+    case DType::F16: return mx_fold_op<F, DType::F16>(in, nsrc, cb, op, avg_div, d, numel, rot, stream);
     default: return hipErrorInvalidValue;
   }
 }
 }  // namespace
 
 hipError_t mx_fold(const void* wire_in, int nsrc, size_t cb, RedOp op, int avg_div, void* dst, size_t numel, DType t,
-                   hipStream_t stream, MxFormat fmt) {
+                   hipStream_t stream, MxFormat fmt, const uint32_t* rot_signs) {
   if (!mx_fmt_ok(fmt) || !mx_cb_ok(cb) || nsrc < 1 || nsrc > kMaxRanks || !mx_al16(wire_in) || !mx_al16(dst))
     return hipErrorInvalidValue;
   if (numel == 0 || numel > cb * kMxBlock) return hipErrorInvalidValue;
@@ -1040,9 +1151,9 @@ hipError_t mx_fold(const void* wire_in, int nsrc, size_t cb, RedOp op, int avg_d
   if (op == RedOp::AVG && avg_div < 1) return hipErrorInvalidValue;
   const char* in = static_cast<const char*>(wire_in);
   char* d = static_cast<char*>(dst);
-  if (fmt == MxFormat::FP6_E2M3) return mx_fold_dt<MxFormat::FP6_E2M3>(t, in, nsrc, (uint32_t)cb, op, avg_div, d, numel, stream);
-  return fmt == MxFormat::FP4_E2M1 ? mx_fold_dt<MxFormat::FP4_E2M1>(t, in, nsrc, (uint32_t)cb, op, avg_div, d, numel, stream)
-                                   : mx_fold_dt<MxFormat::FP8_E4M3>(t, in, nsrc, (uint32_t)cb, op, avg_div, d, numel, stream);
+  if (fmt == MxFormat::FP6_E2M3) return mx_fold_dt<MxFormat::FP6_E2M3>(t, in, nsrc, (uint32_t)cb, op, avg_div, d, numel, rot_signs, stream);
+  return fmt == MxFormat::FP4_E2M1 ? mx_fold_dt<MxFormat::FP4_E2M1>(t, in, nsrc, (uint32_t)cb, op, avg_div, d, numel, rot_signs, stream)
+                                   : mx_fold_dt<MxFormat::FP8_E4M3>(t, in, nsrc, (uint32_t)cb, op, avg_div, d, numel, rot_signs, stream);
 }
 
 }  // namespace kern

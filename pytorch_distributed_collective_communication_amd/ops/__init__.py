@@ -24,6 +24,10 @@
   rounding"), and ``residual=``: error feedback
   (docs/collectives.md "Error feedback"), an f32 tensor added before the quantization and left holding
   what it dropped, fused into the same kernel.
+  :func:`mx_quantize`, :func:`mx_quantize_shards`, :func:`mx_dequantize`, :func:`mx_dequantize_shards` and
+  :func:`mx_fold` take ``rotation="hadamard"`` with ``rotation_seed=``: a randomized Hadamard rotation of
+  every 32-element block before the quantization and back after the dequantization (docs/collectives.md
+  "Hadamard rotation"), inside the same kernels; :func:`mx_reduce` folds rotated wires as they are.
 * :func:`mx_quantize_shards`, :func:`mx_dequantize_shards`, :func:`mx_fold` -- the same wire with one
   chunk per shard (docs/collectives.md "Compressed reduce-scatter and all-gather") and the fold of
   chunk wires straight into a tensor; ``reduce_scatter_compressed`` / ``all_gather_compressed``.
@@ -238,9 +242,33 @@ def _mx_check_rounding(rounding, seed, stream, index_offset, numel, residual, wh
     return sr
 
 
+MX_ROTATIONS = ("hadamard",)
+_MX_ROT_STREAM = 0x52484431  # the stream of the sign word ("RHD1"), no rank's stream
+
+
+def _mx_check_rotation(rotation, rotation_seed, who: str) -> dict:
+    """The rotation arguments (docs/collectives.md "Hadamard rotation") -> the keywords of the native call: none
+    without a rotation, so that call is what it was. The seed is checked whatever the rotation is."""
+    if rotation is not None and (not isinstance(rotation, str) or rotation not in MX_ROTATIONS):
+        raise ValueError(f"{who}: unknown rotation {rotation!r} (supported: None, {', '.join(MX_ROTATIONS)})")
+    if isinstance(rotation_seed, bool) or not isinstance(rotation_seed, int):
+        raise TypeError(f"{who}: rotation_seed must be an int, got {type(rotation_seed).__name__}")
+    if not 0 <= rotation_seed < 1 << 64:
+        raise ValueError(f"{who}: rotation_seed must be in [0, 2^64), got {rotation_seed}")
+    return {} if rotation is None else {"rot": True, "rot_seed": rotation_seed}
+
+
+def mx_rotation_signs(seed: int) -> int:
+    """The 32-bit sign word of a rotation seed: bit ``j`` set flips the sign of position ``j`` of every
+    32-element block (csrc/kernels/mx_rot.h): the word of index 0 under the key of ``(seed, 0x52484431)``."""
+    _mx_check_rotation(None, seed, "mx_rotation_signs")
+    return int(_mx_sr_mix(torch.tensor(mx_sr_key(seed, _MX_ROT_STREAM), dtype=torch.int64)))
+
+
 def mx_quantize(x: torch.Tensor, world: int = 1, out: torch.Tensor | None = None, *,
                 wire: str = "mxfp8_e4m3", residual: torch.Tensor | None = None, rounding: str = "nearest",
-                seed: int = 0, stream: int = 0, index_offset: int = 0) -> torch.Tensor:
+                seed: int = 0, stream: int = 0, index_offset: int = 0, rotation: str | None = None,
+                rotation_seed: int = 0) -> torch.Tensor:
     """``x`` (GPU; f32 / bf16 / f16) -> its wire in the format ``wire``: a uint8 tensor of ``world`` chunks
     of ``[32 cb payload bytes][cb scale bytes]`` (``mxfp4_e2m1``: 16 cb payload bytes, two elements to a
     byte; ``mxfp6_e2m3``: 24 cb payload bytes, six bits to an element), padding blocks included (scale 127, payload 0).
@@ -252,15 +280,22 @@ def mx_quantize(x: torch.Tensor, world: int = 1, out: torch.Tensor | None = None
     ``rounding="stochastic"`` (docs/collectives.md "Stochastic rounding"): every payload element is rounded up
     or down with the probability of its distance, by the counter-based word of ``(seed, stream,
     index_offset + its index in x)`` -- no state, the same arguments give the same bytes. Scale bytes and
-    layout are unchanged. Not together with ``residual``."""
+    layout are unchanged. Not together with ``residual``.
+
+    ``rotation="hadamard"`` (docs/collectives.md "Hadamard rotation"): every 32-element block, padding zeros
+    included, is rotated with the sign word of ``rotation_seed`` before anything else happens to it, so the
+    scale, the rounding and the residual all belong to the rotated block; :func:`mx_dequantize` and
+    :func:`mx_fold` with the same two arguments rotate back. Wire layout and size are unchanged."""
     _mx_check_dtype(x.dtype, "mx_quantize")
     _mx_payload(wire, "mx_quantize")
+    rot = _mx_check_rotation(rotation, rotation_seed, "mx_quantize")
     if _mx_check_rounding(rounding, seed, stream, index_offset, x.numel(), residual, "mx_quantize"):
-        return _C().mx_quantize(x.detach().reshape(-1), int(world), out, wire, None, True, seed, stream, index_offset)
+        return _C().mx_quantize(x.detach().reshape(-1), int(world), out, wire, None, True, seed, stream, index_offset,
+                                **rot)
     if residual is None:
-        return _C().mx_quantize(x.detach().reshape(-1), int(world), out, wire)
+        return _C().mx_quantize(x.detach().reshape(-1), int(world), out, wire, **rot)
     _mx_check_residual(residual, x.numel(), x.device, "mx_quantize")
-    return _C().mx_quantize(x.detach().reshape(-1), int(world), out, wire, residual.detach())
+    return _C().mx_quantize(x.detach().reshape(-1), int(world), out, wire, residual.detach(), **rot)
 
 
 def mx_reduce(w: torch.Tensor, /, nsrc: int, op: str = "sum", out: torch.Tensor | None = None, *,
@@ -286,10 +321,14 @@ def mx_reduce(w: torch.Tensor, /, nsrc: int, op: str = "sum", out: torch.Tensor 
 
 
 def mx_dequantize(w: torch.Tensor, /, numel: int, dtype: torch.dtype = torch.float32, world: int = 1,
-                  out: torch.Tensor | None = None, *, wire: str = "mxfp8_e4m3") -> torch.Tensor:
+                  out: torch.Tensor | None = None, *, wire: str = "mxfp8_e4m3", rotation: str | None = None,
+                  rotation_seed: int = 0) -> torch.Tensor:
     """The first ``numel`` elements of a wire ``w`` of ``world`` chunks, rounded once to ``dtype``; written
-    into ``out`` (``numel`` elements, any shape) when given -- exactly those elements and nothing else."""
+    into ``out`` (``numel`` elements, any shape) when given -- exactly those elements and nothing else.
+    ``rotation``, ``rotation_seed``: those of the :func:`mx_quantize` that made the wire; every dequantized
+    block is rotated back before it is rounded."""
     _mx_payload(wire, "mx_dequantize")
+    rot = _mx_check_rotation(rotation, rotation_seed, "mx_dequantize")
     if out is None:
         _mx_check_dtype(dtype, "mx_dequantize")
         out = torch.empty(int(numel), dtype=dtype, device=w.device)
@@ -297,7 +336,7 @@ def mx_dequantize(w: torch.Tensor, /, numel: int, dtype: torch.dtype = torch.flo
         _mx_check_dtype(out.dtype, "mx_dequantize")
         if out.numel() != int(numel):
             raise ValueError(f"mx_dequantize: out has {out.numel()} elements, numel is {numel}")
-    _C().mx_dequantize(w, int(world), out, wire)
+    _C().mx_dequantize(w, int(world), out, wire, **rot)
     return out
 
 
@@ -310,29 +349,35 @@ def _mx_check_shards(numel: int, world: int, who: str) -> int:
 
 def mx_quantize_shards(x: torch.Tensor, world: int, out: torch.Tensor | None = None, *,
                        wire: str = "mxfp8_e4m3", residual: torch.Tensor | None = None, rounding: str = "nearest",
-                       seed: int = 0, stream: int = 0, index_offset: int = 0) -> torch.Tensor:
+                       seed: int = 0, stream: int = 0, index_offset: int = 0, rotation: str | None = None,
+                       rotation_seed: int = 0) -> torch.Tensor:
     """``x`` (GPU; ``world`` shards of ``m`` elements) -> its shard wire: chunk ``r`` is the wire of shard
     ``r`` alone (``mx_shard_blocks(m)`` blocks; what lies past the shard's end counts as +0).
     ``residual``: as in :func:`mx_quantize`, one float per element of ``x``. ``rounding``, ``seed``,
     ``stream``, ``index_offset``: as in :func:`mx_quantize` -- an element draws the word of its index in
-    ``x``, so it is rounded the same way in both layouts."""
+    ``x``, so it is rounded the same way in both layouts. ``rotation``, ``rotation_seed``: as in
+    :func:`mx_quantize`, on the blocks counted from each shard's first element."""
     _mx_check_dtype(x.dtype, "mx_quantize_shards")
     _mx_payload(wire, "mx_quantize_shards")
     _mx_check_shards(x.numel(), world, "mx_quantize_shards")
+    rot = _mx_check_rotation(rotation, rotation_seed, "mx_quantize_shards")
     if _mx_check_rounding(rounding, seed, stream, index_offset, x.numel(), residual, "mx_quantize_shards"):
         return _C().mx_quantize_shards(x.detach().reshape(-1), int(world), out, wire, None, True, seed, stream,
-                                       index_offset)
+                                       index_offset, **rot)
     if residual is None:
-        return _C().mx_quantize_shards(x.detach().reshape(-1), int(world), out, wire)
+        return _C().mx_quantize_shards(x.detach().reshape(-1), int(world), out, wire, **rot)
     _mx_check_residual(residual, x.numel(), x.device, "mx_quantize_shards")
-    return _C().mx_quantize_shards(x.detach().reshape(-1), int(world), out, wire, residual.detach())
+    return _C().mx_quantize_shards(x.detach().reshape(-1), int(world), out, wire, residual.detach(), **rot)
 
 
 def mx_dequantize_shards(w: torch.Tensor, /, shard_numel: int, dtype: torch.dtype = torch.float32, world: int = 1,
-                         out: torch.Tensor | None = None, *, wire: str = "mxfp8_e4m3") -> torch.Tensor:
+                         out: torch.Tensor | None = None, *, wire: str = "mxfp8_e4m3", rotation: str | None = None,
+                         rotation_seed: int = 0) -> torch.Tensor:
     """A shard wire ``w`` of ``world`` chunks -> ``world * shard_numel`` elements: chunk ``r`` fills
-    ``out[r * m:(r + 1) * m]``, rounded once to the dtype; nothing outside ``out`` is written."""
+    ``out[r * m:(r + 1) * m]``, rounded once to the dtype; nothing outside ``out`` is written.
+    ``rotation``, ``rotation_seed``: as in :func:`mx_dequantize`."""
     _mx_payload(wire, "mx_dequantize_shards")
+    rot = _mx_check_rotation(rotation, rotation_seed, "mx_dequantize_shards")
     n = int(shard_numel) * int(world)
     if out is None:
         _mx_check_dtype(dtype, "mx_dequantize_shards")
@@ -343,19 +388,23 @@ def mx_dequantize_shards(w: torch.Tensor, /, shard_numel: int, dtype: torch.dtyp
             raise ValueError(f"mx_dequantize_shards: out has {out.numel()} elements, {world} shards of "
                              f"{shard_numel} are {n}")
     _mx_check_shards(n, world, "mx_dequantize_shards")
-    _C().mx_dequantize_shards(w, int(world), out, wire)
+    _C().mx_dequantize_shards(w, int(world), out, wire, **rot)
     return out
 
 
 def mx_fold(w: torch.Tensor, /, nsrc: int, numel: int, dtype: torch.dtype = torch.float32, op: str = "sum",
-            out: torch.Tensor | None = None, *, wire: str = "mxfp8_e4m3") -> torch.Tensor:
+            out: torch.Tensor | None = None, *, wire: str = "mxfp8_e4m3", rotation: str | None = None,
+            rotation_seed: int = 0) -> torch.Tensor:
     """``nsrc`` (1..8) chunk wires ``w`` of ``mx_shard_blocks(numel)`` blocks back to back -> ``numel``
     elements: every source dequantized, folded in f32 in source order (``avg``: then divided by ``nsrc``)
     and rounded once to the dtype -- :func:`mx_reduce` then :func:`mx_dequantize` without the
-    requantization between."""
+    requantization between. ``rotation``, ``rotation_seed``: those of the sources' quantization; the fold
+    runs on the rotated values (the rotation is linear) and is rotated back once, after the ``avg`` division
+    and before the rounding."""
     if op not in ("sum", "avg"):
         raise ValueError(f"mx_fold: op must be 'sum' or 'avg', got {op!r}")
     _mx_payload(wire, "mx_fold")
+    rot = _mx_check_rotation(rotation, rotation_seed, "mx_fold")
     if out is None:
         _mx_check_dtype(dtype, "mx_fold")
         out = torch.empty(int(numel), dtype=dtype, device=w.device)
@@ -363,7 +412,7 @@ def mx_fold(w: torch.Tensor, /, nsrc: int, numel: int, dtype: torch.dtype = torc
         _mx_check_dtype(out.dtype, "mx_fold")
         if out.numel() != int(numel):
             raise ValueError(f"mx_fold: out has {out.numel()} elements, numel is {numel}")
-    _C().mx_fold(w, int(nsrc), op, out, wire)
+    _C().mx_fold(w, int(nsrc), op, out, wire, **rot)
     return out
 
 
@@ -544,6 +593,34 @@ def _mx_sr_quantize_blocks(xb: torch.Tensor, u: torch.Tensor, pb: int):
     return q, s
 
 
+# ---- Hadamard rotation (docs/collectives.md "Hadamard rotation"): f32 tensor operations in the defined order
+def _mx_rot_flip(b: torch.Tensor, signs: int) -> torch.Tensor:
+    """(blocks, 32) f32 with the sign of position j flipped where bit j of ``signs`` is set."""
+    bits = (signs >> torch.arange(MX_BLOCK, dtype=torch.int64)) & 1
+    mask = (bits * -0x80000000).to(torch.int32)  # 0x80000000 as an int32
+    return (b.contiguous().view(torch.int32) ^ mask).view(torch.float32)
+
+
+def _mx_rot_butterfly(b: torch.Tensor) -> torch.Tensor:
+    """The product with the unnormalized Sylvester-Hadamard matrix, stage by stage: h = 1, 2, 4, 8, 16, and
+    (y_j, y_{j+h}) <- (y_j + y_{j+h}, y_j - y_{j+h}) for every j with (j & h) == 0; one f32 operation each."""
+    for h in (1, 2, 4, 8, 16):
+        y = b.reshape(-1, MX_BLOCK // (2 * h), 2, h)
+        lo, hi = y[:, :, 0, :], y[:, :, 1, :]
+        b = torch.stack([lo + hi, lo - hi], dim=2).reshape(-1, MX_BLOCK)
+    return b
+
+
+def _mx_rot_forward(xb: torch.Tensor, signs: int) -> torch.Tensor:
+    """R x of (blocks, 32) f32: the signs, then the butterfly."""
+    return _mx_rot_butterfly(_mx_rot_flip(xb, signs))
+
+
+def _mx_rot_inverse(db: torch.Tensor, signs: int) -> torch.Tensor:
+    """R^-1 d of (blocks, 32) f32: the butterfly, one multiply by 2^-5, then the signs."""
+    return _mx_rot_flip(_mx_rot_butterfly(db) * torch.tensor(0.03125, dtype=torch.float32), signs)
+
+
 def _mx_blocks_fns(wire: str, who: str):
     """(payload bytes per block, Q, D) of a format."""
     pb = _mx_payload(wire, who)
@@ -573,30 +650,35 @@ def _mx_feed_back(v: torch.Tensor, d: torch.Tensor, residual: torch.Tensor) -> N
 
 def mx_quantize_reference(x: torch.Tensor, world: int = 1, *, wire: str = "mxfp8_e4m3",
                           residual: torch.Tensor | None = None, rounding: str = "nearest", seed: int = 0,
-                          stream: int = 0, index_offset: int = 0) -> torch.Tensor:
+                          stream: int = 0, index_offset: int = 0, rotation: str | None = None,
+                          rotation_seed: int = 0) -> torch.Tensor:
     """Plain-PyTorch :func:`mx_quantize` on a CPU tensor, bit for bit the documented contract (with
     ``residual``: the contract of "Error feedback", the residual updated in place; with
-    ``rounding="stochastic"``: the contract of "Stochastic rounding")."""
+    ``rounding="stochastic"``: the contract of "Stochastic rounding"; with ``rotation``: the contract of
+    "Hadamard rotation", every block rotated before any of that)."""
     _mx_check_dtype(x.dtype, "mx_quantize_reference")
     pb, Q, D = _mx_blocks_fns(wire, "mx_quantize_reference")
     world = max(1, int(world))
     flat = x.detach().reshape(-1).to(torch.float32)
     n = flat.numel()
-    if _mx_check_rounding(rounding, seed, stream, index_offset, n, residual, "mx_quantize_reference"):
-        total = mx_chunk_blocks(n, world, wire=wire) * world
-        xb = torch.zeros(total * MX_BLOCK, dtype=torch.float32)
-        xb[:n] = flat
-        u = _mx_sr_words(mx_sr_key(seed, stream), index_offset, total * MX_BLOCK)
-        return _mx_join(*_mx_sr_quantize_blocks(xb.view(total, MX_BLOCK), u.view(total, MX_BLOCK), pb), world)
-    if residual is not None:
-        _mx_check_residual(residual, n, x.device, "mx_quantize_reference")
-        flat = flat + residual.detach().view(-1)
+    rot = _mx_check_rotation(rotation, rotation_seed, "mx_quantize_reference")
+    sr = _mx_check_rounding(rounding, seed, stream, index_offset, n, residual, "mx_quantize_reference")
     total = mx_chunk_blocks(n, world, wire=wire) * world
     xb = torch.zeros(total * MX_BLOCK, dtype=torch.float32)
     xb[:n] = flat
+    if rot:  # the padding zeros of a partial block take part
+        xb = _mx_rot_forward(xb.view(total, MX_BLOCK), mx_rotation_signs(rotation_seed)).reshape(-1)
+    if sr:
+        u = _mx_sr_words(mx_sr_key(seed, stream), index_offset, total * MX_BLOCK)
+        return _mx_join(*_mx_sr_quantize_blocks(xb.view(total, MX_BLOCK), u.view(total, MX_BLOCK), pb), world)
+    if residual is not None:  # (one float per element of x: what lies past the end counts as +0 and is dropped)
+        _mx_check_residual(residual, n, x.device, "mx_quantize_reference")
+        rb = torch.zeros_like(xb)
+        rb[:n] = residual.detach().view(-1)
+        xb = xb + rb
     q, s = Q(xb.view(total, MX_BLOCK))
     if residual is not None:
-        _mx_feed_back(flat, D(q, s).reshape(-1)[:n], residual)
+        _mx_feed_back(xb[:n], D(q, s).reshape(-1)[:n], residual)
     return _mx_join(q, s, world)
 
 
@@ -629,47 +711,58 @@ def mx_reduce_reference(w: torch.Tensor, /, nsrc: int, op: str = "sum", *, wire:
 
 
 def mx_dequantize_reference(w: torch.Tensor, /, numel: int, dtype: torch.dtype = torch.float32,
-                            world: int = 1, *, wire: str = "mxfp8_e4m3") -> torch.Tensor:
+                            world: int = 1, *, wire: str = "mxfp8_e4m3", rotation: str | None = None,
+                            rotation_seed: int = 0) -> torch.Tensor:
     """Plain-PyTorch :func:`mx_dequantize` on a CPU wire."""
     _mx_check_dtype(dtype, "mx_dequantize_reference")
+    rot = _mx_check_rotation(rotation, rotation_seed, "mx_dequantize_reference")
     pb, _, D = _mx_blocks_fns(wire, "mx_dequantize_reference")
     world = max(1, int(world))
     if w.numel() != mx_wire_bytes(numel, world, wire=wire):
         raise ValueError(f"the wire of {numel} elements in {world} chunks has "
                          f"{mx_wire_bytes(numel, world, wire=wire)} bytes, got {w.numel()}")
     q, s = _mx_split(w, world, pb)
-    return D(q, s).reshape(-1)[:int(numel)].to(dtype)
+    d = D(q, s)
+    if rot:
+        d = _mx_rot_inverse(d, mx_rotation_signs(rotation_seed))
+    return d.reshape(-1)[:int(numel)].to(dtype)
 
 
 def mx_quantize_shards_reference(x: torch.Tensor, world: int, *, wire: str = "mxfp8_e4m3",
                                  residual: torch.Tensor | None = None, rounding: str = "nearest", seed: int = 0,
-                                 stream: int = 0, index_offset: int = 0) -> torch.Tensor:
+                                 stream: int = 0, index_offset: int = 0, rotation: str | None = None,
+                                 rotation_seed: int = 0) -> torch.Tensor:
     """Plain-PyTorch :func:`mx_quantize_shards` on a CPU tensor (``residual``: updated in place; ``rounding``,
-    ``seed``, ``stream``, ``index_offset``: as in :func:`mx_quantize_shards`)."""
+    ``seed``, ``stream``, ``index_offset``, ``rotation``, ``rotation_seed``: as in :func:`mx_quantize_shards`)."""
     _mx_check_dtype(x.dtype, "mx_quantize_shards_reference")
     _mx_payload(wire, "mx_quantize_shards_reference")
     m = _mx_check_shards(x.numel(), world, "mx_quantize_shards_reference")
     flat = x.detach().reshape(-1)
+    _mx_check_rotation(rotation, rotation_seed, "mx_quantize_shards_reference")
+    rot = {"rotation": rotation, "rotation_seed": rotation_seed}
     if _mx_check_rounding(rounding, seed, stream, index_offset, flat.numel(), residual,
                           "mx_quantize_shards_reference"):
         return torch.cat([mx_quantize_reference(flat[r * m:(r + 1) * m], 1, wire=wire, rounding=rounding, seed=seed,
-                                                stream=stream, index_offset=index_offset + r * m)
+                                                stream=stream, index_offset=index_offset + r * m, **rot)
                           for r in range(int(world))])
     if residual is None:
-        return torch.cat([mx_quantize_reference(flat[r * m:(r + 1) * m], 1, wire=wire) for r in range(int(world))])
+        return torch.cat([mx_quantize_reference(flat[r * m:(r + 1) * m], 1, wire=wire, **rot)
+                          for r in range(int(world))])
     _mx_check_residual(residual, flat.numel(), x.device, "mx_quantize_shards_reference")
     out = []
     for r in range(int(world)):  # (a shard's slice of the residual need not be aligned: it goes through a copy)
         part = residual.detach().view(-1)[r * m:(r + 1) * m].clone()
-        out.append(mx_quantize_reference(flat[r * m:(r + 1) * m], 1, wire=wire, residual=part))
+        out.append(mx_quantize_reference(flat[r * m:(r + 1) * m], 1, wire=wire, residual=part, **rot))
         residual.detach().view(-1)[r * m:(r + 1) * m] = part
     return torch.cat(out)
 
 
 def mx_dequantize_shards_reference(w: torch.Tensor, /, shard_numel: int, dtype: torch.dtype = torch.float32,
-                                   world: int = 1, *, wire: str = "mxfp8_e4m3") -> torch.Tensor:
+                                   world: int = 1, *, wire: str = "mxfp8_e4m3", rotation: str | None = None,
+                                   rotation_seed: int = 0) -> torch.Tensor:
     """Plain-PyTorch :func:`mx_dequantize_shards` on a CPU wire."""
     _mx_check_dtype(dtype, "mx_dequantize_shards_reference")
+    rot = _mx_check_rotation(rotation, rotation_seed, "mx_dequantize_shards_reference")
     pb, _, D = _mx_blocks_fns(wire, "mx_dequantize_shards_reference")
     m, world = int(shard_numel), int(world)
     _mx_check_shards(m * world, world, "mx_dequantize_shards_reference")
@@ -677,12 +770,17 @@ def mx_dequantize_shards_reference(w: torch.Tensor, /, shard_numel: int, dtype: 
         raise ValueError(f"the wire of {world} shards of {m} elements has "
                          f"{mx_shard_wire_bytes(m, world, wire=wire)} bytes, got {w.numel()}")
     q, s = _mx_split(w, world, pb)
-    return D(q, s).view(world, -1)[:, :m].reshape(-1).to(dtype)
+    d = D(q, s)
+    if rot:
+        d = _mx_rot_inverse(d, mx_rotation_signs(rotation_seed))
+    return d.reshape(world, -1)[:, :m].reshape(-1).to(dtype)
 
 
 def mx_fold_reference(w: torch.Tensor, /, nsrc: int, numel: int, dtype: torch.dtype = torch.float32,
-                      op: str = "sum", *, wire: str = "mxfp8_e4m3") -> torch.Tensor:
+                      op: str = "sum", *, wire: str = "mxfp8_e4m3", rotation: str | None = None,
+                      rotation_seed: int = 0) -> torch.Tensor:
     """Plain-PyTorch :func:`mx_fold` on a CPU wire."""
+    rot = _mx_check_rotation(rotation, rotation_seed, "mx_fold_reference")
     if op not in ("sum", "avg"):
         raise ValueError(f"mx_fold_reference: op must be 'sum' or 'avg', got {op!r}")
     _mx_check_dtype(dtype, "mx_fold_reference")
@@ -698,11 +796,13 @@ def mx_fold_reference(w: torch.Tensor, /, nsrc: int, numel: int, dtype: torch.dt
         acc = acc + d[r]
     if op == "avg":
         acc = acc / torch.tensor(float(nsrc), dtype=torch.float32)
+    if rot:
+        acc = _mx_rot_inverse(acc.view(-1, MX_BLOCK), mx_rotation_signs(rotation_seed)).reshape(-1)
     return acc[:numel].to(dtype)
 
 
 __all__ = ["reduce_nway", "reduce_nway_reference", "multi_copy", "pack", "unpack",
-           "MX_WIRES", "MX_ROUNDINGS", "mx_sr_key",
+           "MX_WIRES", "MX_ROUNDINGS", "MX_ROTATIONS", "mx_sr_key", "mx_rotation_signs",
            "mx_quantize", "mx_reduce", "mx_dequantize", "mx_chunk_blocks", "mx_wire_bytes",
            "mx_owner_residual_numel",
            "mx_quantize_reference", "mx_reduce_reference", "mx_dequantize_reference",

@@ -40,6 +40,13 @@ twice the worst-case error of one call. Rank ``r`` draws its words from stream `
 and ``2 r + 1`` (the chunk it requantizes), so ranks are independent even with one seed; varying the seed
 from call to call is the caller's job (``GradBucketer`` and ``ShardedOptimizer`` do it). Gradients are the
 intended use. Both are properties of the local kernels: the wire and the protocol do not change.
+
+``rotation="hadamard"`` with a ``rotation_seed=`` (docs/collectives.md "Hadamard rotation") composes with
+either: every 32-element block is rotated by a randomized Hadamard matrix before it is quantized and back
+after it is dequantized, inside the same kernels. A block's scale comes from its largest element, so one
+outlier pushes the rest of its block below the grid of the narrow formats; the rotation spreads it over
+the block. The fold is linear, so the owner's ``mx_reduce`` works on rotated chunks unchanged. Every rank
+must pass the same rotation and seed, and a carried residual belongs to one seed.
 """
 from __future__ import annotations
 
@@ -90,18 +97,19 @@ def _sequence(tensor, opn, group, world, quantize, reduce, dequantize):
     dequantize(wire, n, world)
 
 
-def _run_gpu(tensor, opn, group, world, wire, residual=None, owner_residual=None, sr=({}, {})):
-    _sequence(tensor, opn, group, world, lambda x, W: ops.mx_quantize(x, W, wire=wire, residual=residual, **sr[0]),
+def _run_gpu(tensor, opn, group, world, wire, residual=None, owner_residual=None, sr=({}, {}), rot={}):
+    _sequence(tensor, opn, group, world,
+              lambda x, W: ops.mx_quantize(x, W, wire=wire, residual=residual, **sr[0], **rot),
               lambda w, W, o: ops.mx_reduce(w, W, o, wire=wire, residual=owner_residual, **sr[1]),
-              lambda w, n, W: ops.mx_dequantize(w, n, tensor.dtype, W, out=tensor, wire=wire))
+              lambda w, n, W: ops.mx_dequantize(w, n, tensor.dtype, W, out=tensor, wire=wire, **rot))
 
 
-def _run_cpu(tensor, opn, group, world, wire, residual=None, owner_residual=None, sr=({}, {})):
+def _run_cpu(tensor, opn, group, world, wire, residual=None, owner_residual=None, sr=({}, {}), rot={}):
     def store(w, n, W):
-        tensor.copy_(ops.mx_dequantize_reference(w, n, tensor.dtype, W, wire=wire).view_as(tensor))
+        tensor.copy_(ops.mx_dequantize_reference(w, n, tensor.dtype, W, wire=wire, **rot).view_as(tensor))
 
     _sequence(tensor, opn, group, world,
-              lambda x, W: ops.mx_quantize_reference(x, W, wire=wire, residual=residual, **sr[0]),
+              lambda x, W: ops.mx_quantize_reference(x, W, wire=wire, residual=residual, **sr[0], **rot),
               lambda w, W, o: ops.mx_reduce_reference(w, W, o, wire=wire, residual=owner_residual, **sr[1]), store)
 
 
@@ -127,6 +135,21 @@ def _rounding_args(who, rounding, seed, group, residuals=()):
             dict(rounding=rounding, seed=seed, stream=2 * rank + 1))
 
 
+ROTATIONS = ("hadamard",)
+
+
+def _rotation_args(who, rotation, rotation_seed):
+    """The rotation arguments of a collective, checked before any communication. Returns the keywords of the
+    kernels that touch the tensor: none for ``None`` (the plain calls)."""
+    if rotation is not None and (not isinstance(rotation, str) or rotation not in ROTATIONS):
+        raise ValueError(f"{who}: unknown rotation {rotation!r} (supported: None, {', '.join(ROTATIONS)})")
+    if isinstance(rotation_seed, bool) or not isinstance(rotation_seed, int):
+        raise TypeError(f"{who}: rotation_seed must be an int, got {type(rotation_seed).__name__}")
+    if not 0 <= rotation_seed < 1 << 64:
+        raise ValueError(f"{who}: rotation_seed must be in [0, 2^64), got {rotation_seed}")
+    return {} if rotation is None else dict(rotation=rotation, rotation_seed=rotation_seed)
+
+
 def _check_residual(who, name, res, numel, device):
     """An error-feedback residual, checked before any communication: float32, ``numel`` elements, on the
     tensor's device, contiguous and 16-byte aligned (it is updated in place, so it cannot be copied)."""
@@ -147,7 +170,8 @@ def _check_residual(who, name, res, numel, device):
 
 def all_reduce_compressed(tensor: torch.Tensor, op=dist.ReduceOp.SUM, group=None, wire: str = "mxfp8_e4m3",
                           async_op: bool = False, *, residual: torch.Tensor | None = None,
-                          owner_residual: torch.Tensor | None = None, rounding: str = "nearest", seed: int = 0):
+                          owner_residual: torch.Tensor | None = None, rounding: str = "nearest", seed: int = 0,
+                          rotation: str | None = None, rotation_seed: int = 0):
     """In-place SUM / AVG all-reduce of ``tensor`` (float32, bfloat16 or float16) over the wire
     format ``wire`` (``mxfp8_e4m3``, ``mxfp4_e2m1`` or ``mxfp6_e2m3``). Every rank ends with the same bits; at world 1 the tensor is left
     unchanged (not even quantized). GPU tensors run on the current stream; with ``async_op=True``
@@ -168,7 +192,13 @@ def all_reduce_compressed(tensor: torch.Tensor, op=dist.ReduceOp.SUM, group=None
     rank's contribution by the words of ``(seed, 2 rank)`` and the chunk it owns by those of ``(seed,
     2 rank + 1)``; the expected value of either quantization is its input. Ranks may use any seeds (their
     errors are independent either way) and still end with the same bits; the same seeds give the same
-    bits again, so pass a new seed with every call. Not together with a residual (``ValueError``)."""
+    bits again, so pass a new seed with every call. Not together with a residual (``ValueError``).
+
+    Hadamard rotation (docs/collectives.md "Hadamard rotation"): ``rotation="hadamard"`` rotates every block
+    of this rank's contribution with the sign word of ``rotation_seed`` before it is quantized and rotates
+    the gathered result back; the owner stage folds and requantizes rotated chunks as they are. Every rank
+    must pass the same rotation and seed. Composes with the residuals (which then live in the rotated
+    domain: keep the seed for as long as they are carried) and with stochastic rounding."""
     opn = _op_name(op)
     if opn is None:
         raise ValueError(f"all_reduce_compressed: only ReduceOp.SUM and ReduceOp.AVG are supported, got {op}")
@@ -181,16 +211,18 @@ def all_reduce_compressed(tensor: torch.Tensor, op=dist.ReduceOp.SUM, group=None
     _check_residual("all_reduce_compressed", "owner_residual", owner_residual,
                     ops.mx_owner_residual_numel(tensor.numel(), world, wire=wire), tensor.device)
     sr = _rounding_args("all_reduce_compressed", rounding, seed, group, (residual, owner_residual))
+    rot = _rotation_args("all_reduce_compressed", rotation, rotation_seed)
     if world == 1 or tensor.numel() == 0:
         return CompressedWork() if async_op else None
     if not tensor.is_cuda:
         with torch.no_grad():
-            _run_cpu(tensor, opn, group, world, wire, residual, owner_residual, sr)
+            _run_cpu(tensor, opn, group, world, wire, residual, owner_residual, sr, rot)
         return CompressedWork() if async_op else None
     if world > MAX_GPU_WORLD:
         raise ValueError(f"all_reduce_compressed: GPU groups of up to {MAX_GPU_WORLD} ranks, got {world}")
     held = tuple(t for t in (tensor, residual, owner_residual) if t is not None)
-    return _issue_gpu(lambda: _run_gpu(tensor, opn, group, world, wire, residual, owner_residual, sr), held, async_op)
+    return _issue_gpu(lambda: _run_gpu(tensor, opn, group, world, wire, residual, owner_residual, sr, rot), held,
+                      async_op)
 
 
 def _issue_gpu(run, tensors, async_op):
@@ -252,7 +284,8 @@ def _done(async_op):
 
 def reduce_scatter_compressed(output: torch.Tensor, input: torch.Tensor, op=dist.ReduceOp.SUM, group=None,
                               wire: str = "mxfp8_e4m3", async_op: bool = False, *,
-                              residual: torch.Tensor | None = None, rounding: str = "nearest", seed: int = 0):
+                              residual: torch.Tensor | None = None, rounding: str = "nearest", seed: int = 0,
+                              rotation: str | None = None, rotation_seed: int = 0):
     """SUM / AVG reduce-scatter of ``input`` (``W * m`` elements; f32, bf16 or f16) into ``output`` (``m``
     elements) over the wire format ``wire``: rank ``k`` ends with the f32 fold, in rank order, of every
     rank's quantized shard ``k`` (its own included), rounded once to the dtype. The fold is not
@@ -265,7 +298,11 @@ def reduce_scatter_compressed(output: torch.Tensor, input: torch.Tensor, op=dist
 
     ``rounding="stochastic"`` with ``seed`` (as in :func:`all_reduce_compressed`): this rank's shards are
     rounded by the words of ``(seed, 2 rank)``, an element by its index in ``input``; the one quantization
-    of each contribution is then unbiased and the W errors of a sum are independent. Not with ``residual``."""
+    of each contribution is then unbiased and the W errors of a sum are independent. Not with ``residual``.
+
+    ``rotation="hadamard"`` with ``rotation_seed`` (as in :func:`all_reduce_compressed`, the same on every
+    rank): the blocks of every shard are rotated before they are quantized, and the fold is rotated back once
+    before it is rounded."""
     who = "reduce_scatter_compressed"
     opn = _op_name(op)
     if opn is None:
@@ -273,6 +310,7 @@ def reduce_scatter_compressed(output: torch.Tensor, input: torch.Tensor, op=dist
     world = _check_pair(who, output, input, wire, group, input, output)
     _check_residual(who, "residual", residual, input.numel(), input.device)
     sr, _ = _rounding_args(who, rounding, seed, group, (residual,))
+    rot = _rotation_args(who, rotation, rotation_seed)
     m = output.numel()
     if m == 0:
         return _done(async_op)
@@ -282,23 +320,24 @@ def reduce_scatter_compressed(output: torch.Tensor, input: torch.Tensor, op=dist
         return _done(async_op)
     if not input.is_cuda:
         with torch.no_grad():
-            w = ops.mx_quantize_shards_reference(input, world, wire=wire, residual=residual, **sr)
+            w = ops.mx_quantize_shards_reference(input, world, wire=wire, residual=residual, **sr, **rot)
             recv = torch.empty_like(w)
             dist.all_to_all_single(recv, w, group=group)
-            output.copy_(ops.mx_fold_reference(recv, world, m, output.dtype, opn, wire=wire).view_as(output))
+            output.copy_(ops.mx_fold_reference(recv, world, m, output.dtype, opn, wire=wire, **rot).view_as(output))
         return _done(async_op)
 
     def run():
-        w = ops.mx_quantize_shards(input, world, wire=wire, residual=residual, **sr)
+        w = ops.mx_quantize_shards(input, world, wire=wire, residual=residual, **sr, **rot)
         recv = torch.empty_like(w)
         dist.all_to_all_single(recv, w, group=group)  # chunk r of every rank -> rank r, in rank order
-        ops.mx_fold(recv, world, m, output.dtype, opn, out=output, wire=wire)
+        ops.mx_fold(recv, world, m, output.dtype, opn, out=output, wire=wire, **rot)
 
     return _issue_gpu(run, (output, input) if residual is None else (output, input, residual), async_op)
 
 
 def all_gather_compressed(output: torch.Tensor, input: torch.Tensor, group=None, wire: str = "mxfp8_e4m3",
-                          async_op: bool = False, *, rounding: str = "nearest", seed: int = 0):
+                          async_op: bool = False, *, rounding: str = "nearest", seed: int = 0,
+                          rotation: str | None = None, rotation_seed: int = 0):
     """All-gather of ``input`` (``m`` elements; f32, bf16 or f16) into ``output`` (``W * m`` elements)
     over the wire format ``wire``: every rank ends with the same bits, the dequantized wire of every
     rank's shard -- its own slot included. At world 1 ``input`` is copied bit for bit. Streams and
@@ -307,10 +346,14 @@ def all_gather_compressed(output: torch.Tensor, input: torch.Tensor, group=None,
     ``rounding="stochastic"`` with ``seed``: accepted because the gather shares the quantizer -- this rank's
     shard is rounded by the words of ``(seed, 2 rank)``, and every rank still ends with the same bits. It is
     meant for gradients; values that are not summed or averaged afterwards (parameters) gain nothing
-    from it and pay twice the worst-case error."""
+    from it and pay twice the worst-case error.
+
+    ``rotation="hadamard"`` with ``rotation_seed`` (the same on every rank): this rank's blocks are rotated
+    before they are quantized and every gathered shard is rotated back."""
     who = "all_gather_compressed"
     world = _check_pair(who, output, input, wire, group, output, input)
     sr, _ = _rounding_args(who, rounding, seed, group)
+    rot = _rotation_args(who, rotation, rotation_seed)
     m = input.numel()
     if m == 0:
         return _done(async_op)
@@ -320,16 +363,16 @@ def all_gather_compressed(output: torch.Tensor, input: torch.Tensor, group=None,
         return _done(async_op)
     if not input.is_cuda:
         with torch.no_grad():
-            mine = ops.mx_quantize_reference(input, 1, wire=wire, **sr)
+            mine = ops.mx_quantize_reference(input, 1, wire=wire, **sr, **rot)
             every = torch.empty(mine.numel() * world, dtype=torch.uint8)
             dist.all_gather_into_tensor(every, mine, group=group)
-            output.copy_(ops.mx_dequantize_shards_reference(every, m, output.dtype, world, wire=wire).view_as(output))
+            output.copy_(ops.mx_dequantize_shards_reference(every, m, output.dtype, world, wire=wire, **rot).view_as(output))
         return _done(async_op)
 
     def run():
-        mine = ops.mx_quantize(input, 1, wire=wire, **sr)
+        mine = ops.mx_quantize(input, 1, wire=wire, **sr, **rot)
         every = torch.empty(mine.numel() * world, dtype=torch.uint8, device=mine.device)
         dist.all_gather_into_tensor(every, mine, group=group)
-        ops.mx_dequantize_shards(every, m, output.dtype, world, out=output, wire=wire)
+        ops.mx_dequantize_shards(every, m, output.dtype, world, out=output, wire=wire, **rot)
 
     return _issue_gpu(run, (output, input), async_op)

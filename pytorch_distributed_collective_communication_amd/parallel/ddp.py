@@ -39,6 +39,9 @@ contract, MI355X-first:
   error of a step is independent of the last one's, with no state at all (docs/collectives.md
   "Stochastic rounding"). Bucket ``b`` of synchronised step ``n`` uses the seed
   ``(seed + n * nbuckets + b) mod 2^64``.
+* ``rotation="hadamard"`` (with a wire, together with either or neither of the two): every block of a
+  bucket is rotated by a randomized Hadamard matrix before it is quantized and back afterwards, which
+  keeps a block's small gradients on the grid next to an outlier (docs/collectives.md "Hadamard rotation").
 
 ``broadcast_parameters`` and ``scatter_batch`` cover the other two uses.
 torch's own ``DistributedDataParallel`` also runs unchanged on this backend.
@@ -97,12 +100,23 @@ class GradBucketer:
     ``rounding="stochastic"`` (needs ``wire``, excludes ``error_feedback``): every ``all_reduce_compressed``
     rounds stochastically, bucket ``b`` of synchronised step ``n`` (``rounding_step``, counted by
     :meth:`finish`) with the seed ``(seed + n * len(buckets) + b) mod 2^64``. A backward inside
-    ``no_sync()`` is no step."""
+    ``no_sync()`` is no step.
+
+    ``rotation="hadamard"`` with ``rotation_seed`` (needs ``wire``; composes with either of the above): every
+    ``all_reduce_compressed`` rotates the blocks of the bucket before it quantizes them and back afterwards
+    (docs/collectives.md "Hadamard rotation"). The seed is fixed for the object's life -- it does not step,
+    the residuals live in the rotated domain of that one seed -- and must be the same on every rank."""
 
     def __init__(self, module: torch.nn.Module, group=None, bucket_bytes: int = 256 << 20,
                  average: bool = True, wire: str | None = None, error_feedback: bool = False,
-                 rounding: str = "nearest", seed: int = 0):
-        from .compressed import ROUNDINGS
+                 rounding: str = "nearest", seed: int = 0, rotation: str | None = None, rotation_seed: int = 0):
+        from .compressed import ROUNDINGS, _rotation_args
+
+        self._rot = _rotation_args("GradBucketer", rotation, rotation_seed)
+        if rotation is not None and wire is None:
+            raise ValueError("GradBucketer: a rotation needs a compressed wire (wire=None sends exact gradients: "
+                             "nothing is quantized)")
+        self.rotation, self.rotation_seed = rotation, rotation_seed
 
         if rounding not in ROUNDINGS:
             raise ValueError(f"GradBucketer: unknown rounding {rounding!r} (supported: {', '.join(ROUNDINGS)})")
@@ -202,9 +216,9 @@ class GradBucketer:
                 nb = len(self.buckets)
                 seed = (self.seed + self.rounding_step * nb + self.buckets.index(b)) % (1 << 64)
                 return all_reduce_compressed(b.flat, dist.ReduceOp.AVG, group=self.group, wire=self.wire,
-                                             async_op=True, rounding="stochastic", seed=seed)
+                                             async_op=True, rounding="stochastic", seed=seed, **self._rot)
             return all_reduce_compressed(b.flat, dist.ReduceOp.AVG, group=self.group, wire=self.wire, async_op=True,
-                                         residual=b.residual, owner_residual=b.owner_residual)
+                                         residual=b.residual, owner_residual=b.owner_residual, **self._rot)
         return dist.all_reduce(b.flat, op=self._op, group=self.group, async_op=True)
 
     def finish(self) -> None:

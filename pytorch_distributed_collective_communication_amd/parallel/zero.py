@@ -57,6 +57,12 @@ unbiased, no state but a step counter. Gradient bucket ``b`` (counted over all s
 step ``n`` uses the seed ``(grad_seed + n * nbuckets + b) mod 2^64``; ``state_dict()`` saves ``n`` as
 ``grad_rounding_step`` (a checkpoint without it loads as 0). ``param_wire`` stays nearest.
 
+``grad_rotation="hadamard"`` / ``param_rotation="hadamard"`` (each with its wire) with one ``rotation_seed``:
+the reduce-scatters / the all-gathers rotate every 32-element block by a randomized Hadamard matrix before
+they quantize it and back afterwards (docs/collectives.md "Hadamard rotation"), which is what makes the
+narrow wires usable for heavy-tailed gradients. The seed never steps and is not saved: the gradient
+residuals live in the rotated domain of that seed.
+
 ``state_dict()`` / ``load_state_dict()`` save and restore this rank's shard
 (sharded checkpoint: every rank writes its own file) and re-gather the
 parameters on load.
@@ -181,7 +187,11 @@ class ShardedOptimizer:
     quantization error of this rank's gradients from step to step in an f32 residual, 4 bytes per gradient
     element, saved by :meth:`state_dict`. ``grad_rounding="stochastic"`` with ``grad_seed`` (needs ``grad_wire``,
     excludes ``grad_error_feedback``) rounds the gradients on the wire stochastically, a fresh seed per bucket
-    and step; :meth:`state_dict` saves the step counter. One parameter group: the inner optimizer's hyper-parameters
+    and step; :meth:`state_dict` saves the step counter. ``grad_rotation="hadamard"`` / ``param_rotation="hadamard"``
+    (each needs its wire; ``rotation_seed`` serves both) rotate every block by a randomized Hadamard matrix before it
+    is quantized and back afterwards (docs/collectives.md "Hadamard rotation"); the seed is fixed for the object's
+    life, must be the same on every rank and is a constructor argument, not part of :meth:`state_dict` -- a
+    checkpoint with gradient residuals is loaded into an optimizer built with the seed that wrote it. One parameter group: the inner optimizer's hyper-parameters
     come from ``**opt_kwargs``.
     """
 
@@ -189,8 +199,17 @@ class ShardedOptimizer:
                  master_dtype: torch.dtype = torch.float32, broadcast_from: int | None = 0,
                  bucket_bytes: int = 256 << 20, overlap: bool = True, grad_wire: str | None = None,
                  param_wire: str | None = None, grad_error_feedback: bool = False, grad_rounding: str = "nearest",
-                 grad_seed: int = 0, **opt_kwargs):
-        from .compressed import ROUNDINGS, WIRES
+                 grad_seed: int = 0, grad_rotation: str | None = None, param_rotation: str | None = None,
+                 rotation_seed: int = 0, **opt_kwargs):
+        from .compressed import ROUNDINGS, WIRES, _rotation_args
+
+        self._grad_rot = _rotation_args("ShardedOptimizer", grad_rotation, rotation_seed)
+        self._param_rot = _rotation_args("ShardedOptimizer", param_rotation, rotation_seed)
+        for name, rot, w in (("grad", grad_rotation, grad_wire), ("param", param_rotation, param_wire)):
+            if rot is not None and w is None:
+                raise ValueError(f"ShardedOptimizer: {name}_rotation needs a {name}_wire ({name}_wire=None sends exact "
+                                 "values: nothing is quantized)")
+        self.grad_rotation, self.param_rotation, self.rotation_seed = grad_rotation, param_rotation, rotation_seed
 
         if grad_rounding not in ROUNDINGS:
             raise ValueError(f"ShardedOptimizer: unknown grad_rounding {grad_rounding!r} "
@@ -291,13 +310,13 @@ class ShardedOptimizer:
                 b.work = reduce_scatter_compressed(s.grad_shard[b.soff:b.soff + b.shard],
                                                    s.grad[b.off:b.off + b.padded], op=dist.ReduceOp.AVG,
                                                    group=self.group, wire=self.grad_wire, async_op=True,
-                                                   rounding="stochastic", seed=seed)
+                                                   rounding="stochastic", seed=seed, **self._grad_rot)
                 return
             b.work = reduce_scatter_compressed(s.grad_shard[b.soff:b.soff + b.shard], s.grad[b.off:b.off + b.padded],
                                                op=dist.ReduceOp.AVG, group=self.group, wire=self.grad_wire,
                                                async_op=True,
                                                residual=None if s.grad_residual is None
-                                               else s.grad_residual[b.off:b.off + b.padded])
+                                               else s.grad_residual[b.off:b.off + b.padded], **self._grad_rot)
             return
         self._fence(s)
         b.work = dist.reduce_scatter_tensor(s.grad_shard[b.soff:b.soff + b.shard], s.grad[b.off:b.off + b.padded],
@@ -353,7 +372,7 @@ class ShardedOptimizer:
 
                     works.append(all_gather_compressed(s.flat[b.off:b.off + b.padded],
                                                        s.param_shard[b.soff:b.soff + b.shard], group=self.group,
-                                                       wire=self.param_wire, async_op=True))
+                                                       wire=self.param_wire, async_op=True, **self._param_rot))
                     continue
                 self._fence(s)
                 works.append(dist.all_gather_into_tensor(s.flat[b.off:b.off + b.padded],
