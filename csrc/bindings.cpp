@@ -225,6 +225,76 @@ void mx_dequantize(const at::Tensor& wire, int world, at::Tensor& out, const std
   if (!o.is_same(out)) out.copy_(o);
 }
 
+// ---- the tensor-list layout (kernels/mx_layout.h): the tensors are read and written where they are, so
+// nothing goes through a copy: one dtype, one GPU, contiguous (any element alignment).
+std::vector<pdcc::kern::MxListTensor> mx_list(const std::vector<at::Tensor>& xs, const at::Device& dev,
+                                              at::ScalarType st, const char* who) {
+  TORCH_CHECK_VALUE(xs.size() <= 65535, who, ": at most 65535 tensors in a list, got ", xs.size());
+  std::vector<pdcc::kern::MxListTensor> ts;
+  ts.reserve(xs.size());
+  for (const at::Tensor& x : xs) {
+    TORCH_CHECK(x.is_cuda(), who, ": GPU tensors only");
+    TORCH_CHECK_TYPE(x.scalar_type() == st, who, ": the tensors of a list share one dtype, got ", st, " and ",
+                     x.scalar_type());
+    TORCH_CHECK_VALUE(x.device() == dev, who, ": the tensors of a list share one device, got ", dev, " and ", x.device());
+    TORCH_CHECK_VALUE(x.is_contiguous(), who, ": the tensors of a list must be contiguous");
+    ts.push_back({x.numel() ? x.data_ptr() : nullptr, (size_t)x.numel()});
+  }
+  return ts;
+}
+
+at::Tensor mx_quantize_list(const std::vector<at::Tensor>& xs, int world, const c10::optional<at::Tensor>& out,
+                            const std::string& fmt, const c10::optional<at::Tensor>& residual, bool sr, uint64_t seed,
+                            int64_t sr_stream, bool rot, uint64_t rot_seed) {
+  const char* who = "mx_quantize_list";
+  const MxFormat f = mx_format(fmt, who);
+  const MxRot rt(rot, rot_seed);
+  mx_check_sr(sr, residual.has_value(), sr_stream, who);
+  TORCH_CHECK_VALUE(!xs.empty(), who, ": an empty list has no device and no dtype");
+  TORCH_CHECK(world >= 1 && world <= 65535, who, ": world must be 1..65535");
+  const auto d = mx_dtype(xs[0], who);
+  const at::Device dev = xs[0].device();
+  const auto ts = mx_list(xs, dev, xs[0].scalar_type(), who);
+  const size_t numel = pdcc::kern::mx_list_numel(ts.data(), ts.size());
+  const size_t cb = pdcc::kern::mx_chunk_blocks(f, numel, world);
+  const int64_t bytes = (int64_t)pdcc::kern::mx_wire_bytes(f, cb, (size_t)world);
+  float* res = mx_residual(residual, (int64_t)numel, dev, who);
+  c10::hip::HIPGuardMasqueradingAsCUDA g(dev);
+  at::Tensor wire = out ? *out : at::empty({bytes}, xs[0].options().dtype(at::kByte));
+  mx_check_wire(wire, who);
+  TORCH_CHECK(wire.device() == dev && wire.numel() == bytes, who, ": out must hold ", bytes, " bytes on ", dev);
+  at::Tensor w = mx_out(wire);
+  hipStream_t s = c10::hip::getCurrentHIPStreamMasqueradingAsCUDA(dev.index()).stream();
+  const pdcc::kern::MxListSr srs{seed, (uint32_t)sr_stream, 0};
+  hipError_t e = pdcc::kern::mx_quantize_list(ts.data(), ts.size(), d, w.data_ptr(), cb, (size_t)world, s, f, rt.ptr(), res,
+                                              sr ? &srs : nullptr);
+  TORCH_CHECK(e == hipSuccess, who, " launch failed: ", hipGetErrorString(e));
+  if (!w.is_same(wire)) wire.copy_(w);
+  return wire;
+}
+
+void mx_dequantize_list(const at::Tensor& wire, const std::vector<at::Tensor>& outs, int world, const std::string& fmt,
+                        bool rot, uint64_t rot_seed) {
+  const char* who = "mx_dequantize_list";
+  const MxFormat f = mx_format(fmt, who);
+  const MxRot rt(rot, rot_seed);
+  mx_check_wire(wire, who);
+  TORCH_CHECK(world >= 1 && world <= 65535, who, ": world must be 1..65535");
+  if (outs.empty()) return;
+  const auto d = mx_dtype(outs[0], who);
+  const auto ts = mx_list(outs, wire.device(), outs[0].scalar_type(), who);
+  const size_t numel = pdcc::kern::mx_list_numel(ts.data(), ts.size());
+  const size_t cb = pdcc::kern::mx_chunk_blocks(f, numel, world);
+  TORCH_CHECK((size_t)wire.numel() == pdcc::kern::mx_wire_bytes(f, cb, (size_t)world), who, ": the wire of a list of ",
+              numel, " padded elements in ", world, " chunks has ", pdcc::kern::mx_wire_bytes(f, cb, (size_t)world),
+              " bytes, got ", wire.numel());
+  c10::hip::HIPGuardMasqueradingAsCUDA g(wire.device());
+  at::Tensor w = mx_in(wire);
+  hipStream_t s = c10::hip::getCurrentHIPStreamMasqueradingAsCUDA(wire.device().index()).stream();
+  hipError_t e = pdcc::kern::mx_dequantize_list(w.data_ptr(), cb, (size_t)world, ts.data(), ts.size(), d, s, f, rt.ptr());
+  TORCH_CHECK(e == hipSuccess, who, " launch failed: ", hipGetErrorString(e));
+}
+
 // ---- the shard layout (kernels/mx_layout.h): chunk r is shard r of `numel / world` elements
 at::Tensor mx_quantize_shards(const at::Tensor& x, int world, const c10::optional<at::Tensor>& out,
                               const std::string& fmt, const c10::optional<at::Tensor>& residual, bool sr, uint64_t seed,
@@ -476,6 +546,14 @@ PYBIND11_MODULE(_C, m) {
         py::arg("fmt") = "mxfp8_e4m3", py::arg("rot") = false, py::arg("rot_seed") = 0,
         "mxfp8_e4m3 / mxfp4_e2m1 / mxfp6_e2m3 wire of `world` chunks -> out (f32 / bf16 / f16), exactly out.numel() elements; "
         "`rot`: every block rotated back with the sign word of `rot_seed`");
+  m.def("mx_quantize_list", &mx_quantize_list, py::arg("xs"), py::arg("world") = 1, py::arg("out") = py::none(),
+        py::arg("fmt") = "mxfp8_e4m3", py::arg("residual") = py::none(), py::arg("sr") = false, py::arg("seed") = 0,
+        py::arg("stream") = 0, py::arg("rot") = false, py::arg("rot_seed") = 0,
+        "list of tensors of one dtype -> the dealt wire of their tensor-list layout (every tensor starts a block), read "
+        "in place; `residual`: one float per virtual position; `sr` and `rot` as in mx_quantize");
+  m.def("mx_dequantize_list", &mx_dequantize_list, py::arg("wire"), py::arg("outs"), py::arg("world") = 1,
+        py::arg("fmt") = "mxfp8_e4m3", py::arg("rot") = false, py::arg("rot_seed") = 0,
+        "wire of a tensor list -> the tensors, written in place: exactly their elements; `rot` as in mx_dequantize");
   m.def("mx_quantize_shards", &mx_quantize_shards, py::arg("x"), py::arg("world"), py::arg("out") = py::none(),
         py::arg("fmt") = "mxfp8_e4m3", py::arg("residual") = py::none(), py::arg("sr") = false, py::arg("seed") = 0,
         py::arg("stream") = 0, py::arg("index_offset") = 0, py::arg("rot") = false, py::arg("rot_seed") = 0,

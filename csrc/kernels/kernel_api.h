@@ -391,6 +391,26 @@ hipError_t mx_quantize_shards_sr(const void* src, size_t m, DType t, void* wire,
 // Reduce: the index is the element's index in the chunk, 0 .. 32 cb - 1.
 hipError_t mx_reduce_sr(const void* wire_in, int nsrc, size_t cb, RedOp op, int avg_div, void* wire_out, uint64_t seed,
                         uint32_t sr_stream, hipStream_t stream, MxFormat fmt = MxFormat::FP8_E4M3);
+// The tensor-list layout (mx_layout.h, docs/collectives.md "Tensor-list layout"): the dealt wire of `k`
+// (<= 65535) tensors of dtype `t`, read and written where they are; cb * nchunks >= mx_list_blocks(ts, k)
+// and < 2^32. A launch takes the descriptors of kMaxMxListDescs tensors in its kernarg; longer lists are
+// split at tensor boundaries. Quantize writes every block of every chunk. `residual` (error feedback,
+// mx_list_numel(ts, k) floats at the elements' virtual positions, 16-byte aligned): as in mx_quantize_ef,
+// positions past a tensor's end are written as +0. `sr` (stochastic rounding, not with `residual`): the
+// word index of an element is `index_offset` plus its virtual position.
+constexpr int kMaxMxListDescs = 64;
+struct MxListSr {
+  uint64_t seed;
+  uint32_t stream;
+  uint64_t index_offset;
+};
+hipError_t mx_quantize_list(const MxListTensor* ts, size_t k, DType t, void* wire, size_t cb, size_t nchunks,
+                            hipStream_t stream, MxFormat fmt = MxFormat::FP8_E4M3, const uint32_t* rot_signs = nullptr,
+                            float* residual = nullptr, const MxListSr* sr = nullptr);
+// nchunks chunk wires -> exactly the numel elements of every tensor, rounded once to `t`.
+hipError_t mx_dequantize_list(const void* wire, size_t cb, size_t nchunks, const MxListTensor* ts, size_t k, DType t,
+                              hipStream_t stream, MxFormat fmt = MxFormat::FP8_E4M3,
+                              const uint32_t* rot_signs = nullptr);
 
 }  // namespace kern
 }  // namespace pdcc

@@ -112,5 +112,23 @@ PDCC_MX_HD inline size_t mx_shard_scale_byte(size_t m, size_t i) {
   return mx_shard_scale_byte(MxFormat::FP8_E4M3, m, i);
 }
 
+// ---- tensor-list layout (docs/collectives.md "Tensor-list layout"): k tensors of one dtype are one virtual
+// tensor in which every tensor starts a fresh block. Tensor i owns the mx_blocks(n_i) blocks from
+// B_i = sum_{j<i} mx_blocks(n_j) on (an empty tensor owns none); positions of its last block past n_i count
+// as +0 and are never read or written. The NB = mx_list_blocks(...) blocks are dealt to chunks by the rule
+// above, cb = mx_chunk_blocks(f, 32 NB, world): the wire of a list is, byte for byte, the dealt wire of the
+// concatenation of the tensors, each zero-padded to a multiple of 32 elements.
+struct MxListTensor {
+  void* base;    // contiguous elements; any element alignment (16-byte aligned tensors move as vectors)
+  size_t numel;  // n_i
+};
+PDCC_MX_HD inline size_t mx_list_blocks(const MxListTensor* ts, size_t k) {
+  size_t nb = 0;
+  for (size_t i = 0; i < k; ++i) nb += mx_blocks(ts[i].numel);
+  return nb;
+}
+// elements of the virtual tensor, and of the residual of a list: 32 NB
+PDCC_MX_HD inline size_t mx_list_numel(const MxListTensor* ts, size_t k) { return kMxBlock * mx_list_blocks(ts, k); }
+
 }  // namespace kern
 }  // namespace pdcc

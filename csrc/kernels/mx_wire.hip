@@ -15,6 +15,9 @@
 //   mx_quantize_sr / mx_quantize_shards_sr / mx_reduce_sr: the SR instantiations of quantize and
 //                  reduce, which round the payload stochastically (docs/collectives.md "Stochastic
 //                  rounding", mx_sr.h); they move the bytes of the plain kernels
+//   mx_quantize_list / mx_dequantize_list: the dealt wire of a list of tensors read and written where they
+//                  are, every tensor starting a fresh block (docs/collectives.md "Tensor-list layout"); the
+//                  one pair of kernels that uses LDS, for the table of the tensors' descriptors
 //
 // All of them are streaming kernels: a lane moves 16 B on the wide side of its conversion (the tensor
 // for quantize / dequantize / fold, the payload for reduce), the lanes of a block sit next to each other
@@ -855,6 +858,235 @@ __global__ __launch_bounds__(256) void k_mx_fold(const char* __restrict__ in, ui
   }
 }
 
+// ---------------------------------------------------------------------------- tensor lists
+// Quantize and dequantize in the tensor-list layout (mx_layout.h): the dealt wire of a virtual tensor whose
+// blocks belong to up to kMaxMxListDescs tensors of this launch, read and written where they lie. The wire
+// side is that of the dealt kernels. The tensor side goes through a descriptor table: the kernarg copy is
+// spread to LDS once per workgroup, a span (kMxUnroll * 256 vectors of one chunk) finds the tensor of its
+// first block by binary search, and every lane then walks its own cursor forward -- a span lies inside one
+// tensor almost always, and then that walk is one LDS read per vector that fails its test.
+//
+// A launch owns the blocks [g0, g1) of the virtual tensor (the host splits long lists at tensor boundaries,
+// which are block boundaries): [g0, end) belong to its tensors, [end, g1) are padding blocks of the wire
+// (quantize only). Spans are cut per chunk, span s is the vectors from (s % spc) * kMxUnroll * 256 on of
+// chunk s / spc, so a span at an edge of the range is shared with the neighbouring launch and each masks
+// the other's blocks. Whole blocks are live or not, so the lanes that share a DPP exchange run together.
+struct MxListDesc {
+  const char* base;
+  uint64_t numel;
+  uint32_t first;  // B_i
+};
+struct MxListArgs {
+  MxListDesc d[kern::kMaxMxListDescs];
+  uint32_t n, g0, g1, end;
+};
+struct MxListTable {
+  uint32_t first[kern::kMaxMxListDescs + 1];  // first[n] = end
+  const char* base[kern::kMaxMxListDescs];
+  uint64_t numel[kern::kMaxMxListDescs];
+};
+__device__ __forceinline__ void list_table_load(const MxListArgs& a, MxListTable& t) {
+  if (threadIdx.x < a.n) {
+    t.first[threadIdx.x] = a.d[threadIdx.x].first;
+    t.base[threadIdx.x] = a.d[threadIdx.x].base;
+    t.numel[threadIdx.x] = a.d[threadIdx.x].numel;
+  }
+  if (threadIdx.x == 0) t.first[a.n] = a.end;
+  __syncthreads();
+}
+// the last descriptor that starts at or before block g (g >= first[0]); 0 for an empty table
+__device__ __forceinline__ uint32_t list_find(const MxListTable& t, uint32_t n, uint32_t g) {
+  uint32_t lo = 0, hi = n;
+  while (lo < hi) {
+    const uint32_t mid = (lo + hi) >> 1;
+    if (t.first[mid] <= g) lo = mid + 1;
+    else hi = mid;
+  }
+  return lo ? lo - 1 : 0;
+}
+// A lane's place in the list: the tensor of block g (a block below `end`; g never decreases between calls),
+// and how many of the EPL elements from the lane's `place` on the tensor has (0 .. EPL).
+struct MxListCursor {
+  uint32_t idx;
+  template <int EPL>
+  __device__ __forceinline__ uint32_t seek(const MxListTable& t, uint32_t n, uint32_t g, uint32_t place, uint64_t* el) {
+    while (idx + 1 < n && g >= t.first[idx + 1]) ++idx;
+    *el = (uint64_t)(g - t.first[idx]) * kern::kMxBlock + place * EPL;  // first element, in the tensor
+    const uint64_t numel = t.numel[idx];
+    return *el >= numel ? 0u : (numel - *el >= (uint64_t)EPL ? (uint32_t)EPL : (uint32_t)(numel - *el));
+  }
+};
+
+// EF: `res` holds one float per virtual position, 32 per block, so a lane's EPL floats are always aligned
+// vectors; the positions of a last block past its tensor's end are read like the others and written as
+// +0. Padding blocks have no residual. SR: the word index is `sr_base` plus the virtual position.
+template <MxFormat F, DType DT, bool EF, bool SR, bool ROT>
+__global__ __launch_bounds__(256) void k_mx_quantize_list(const MxListArgs a, char* __restrict__ wire, uint32_t cb,
+                                                          uint32_t spc, uint32_t s0, uint32_t s1,
+                                                          float* __restrict__ res, uint32_t sr_key, uint64_t sr_base,
+                                                          uint32_t rot_signs) {
+  static_assert(!(EF && SR), "error feedback and stochastic rounding are alternatives");
+  using T = Tr<DT>;
+  using S = typename T::S;
+  constexpr int EPL = 16 / (int)sizeof(S);
+  constexpr int LPB = kern::kMxBlock / EPL;
+  using M = MxFmt<F>;
+  constexpr int QB = EPL * M::kPayload / kern::kMxBlock, QW = M::template kWords<EPL>;
+  __shared__ MxListTable t;
+  list_table_load(a, t);
+  const uint32_t nvec = cb * LPB;
+  for (uint32_t s = s0 + blockIdx.x; s < s1; s += gridDim.x) {
+    const uint32_t chunk = s / spc, vs = (s - chunk * spc) * (256u * kMxUnroll);
+    char* __restrict__ w = wire + (size_t)chunk * kern::mx_chunk_bytes(F, cb);
+    const uint32_t gb = chunk * cb;  // the chunk's first block
+    const uint32_t gs = gb + vs / LPB;
+    MxListCursor cur{list_find(t, a.n, gs > a.g0 ? gs : a.g0)};
+    S sv[kMxUnroll][EPL];
+    float r[EF ? kMxUnroll : 1][EPL];
+    uint32_t have[EF ? kMxUnroll : 1];
+#pragma unroll
+    for (int u = 0; u < kMxUnroll; ++u) {
+      const uint32_t v = vs + threadIdx.x + u * 256u, g = gb + v / LPB;
+      __builtin_memset(sv[u], 0, sizeof(sv[u]));
+      if constexpr (EF) {
+        __builtin_memset(r[u], 0, sizeof(r[u]));
+        have[u] = 0u;
+      }
+      if (v < nvec && g >= a.g0 && g < a.end) {
+        uint64_t el;
+        const uint32_t nv = cur.template seek<EPL>(t, a.n, g, v % LPB, &el);
+        const char* p = t.base[cur.idx] + el * sizeof(S);
+        if (nv == (uint32_t)EPL && (reinterpret_cast<uintptr_t>(p) & 15u) == 0) {
+          const uint4 x = *reinterpret_cast<const uint4*>(p);
+          __builtin_memcpy(sv[u], &x, 16);
+        } else {
+          // a misaligned tensor, or its last vector: elements past the end count as +0 and are never read
+#pragma unroll
+          for (int i = 0; i < EPL; ++i)
+            if ((uint32_t)i < nv) sv[u][i] = reinterpret_cast<const S*>(p)[i];
+        }
+        if constexpr (EF) {
+          have[u] = nv;
+          const float* rp = res + (size_t)g * kern::kMxBlock + (v % LPB) * EPL;
+#pragma unroll
+          for (int j = 0; j < EPL / 4; ++j) {
+            const uint4 y = *reinterpret_cast<const uint4*>(rp + 4 * j);
+            __builtin_memcpy(&r[u][4 * j], &y, 16);
+          }
+        }
+      }
+    }
+#pragma unroll
+    for (int u = 0; u < kMxUnroll; ++u) {
+      const uint32_t v = vs + threadIdx.x + u * 256u, g = gb + v / LPB;
+      if (v >= nvec) break;  // (whole waves leave together: nvec and every span start are multiples of 64)
+      if (g < a.g0 || g >= a.g1) continue;  // (a neighbouring launch's blocks)
+      float f[EPL];
+      uint32_t am = 0;
+      if constexpr (ROT) {
+#pragma unroll
+        for (int i = 0; i < EPL; ++i) f[i] = T::in(sv[u][i]);
+        rot_forward<EPL>(f, rot_signs, v % LPB);
+      }
+#pragma unroll
+      for (int i = 0; i < EPL; ++i) {
+        if constexpr (!ROT) f[i] = T::in(sv[u][i]);
+        if constexpr (EF) f[i] += r[u][i];
+        const uint32_t ab = abs_bits(f[i]);
+        am = ab > am ? ab : am;
+      }
+      const MxScale sc = M::scale(group_max<LPB>(am));
+      uint32_t q[QW];
+      const uint64_t pos = (uint64_t)g * kern::kMxBlock + (v % LPB) * EPL;  // the lane's virtual position
+      if constexpr (SR) M::template pack_sr<EPL>(f, sc, q, SrWords(sr_key, sr_base + pos, EPL));
+      else M::template pack<EPL>(f, sc, q);
+      if constexpr (M::kLanes) M::template st_lanes<EPL>(w, v, q);
+      else st_wire<QB>(w + (size_t)v * QB, q);
+      if (v % LPB == 0) w[kern::mx_scale_off(F, cb, v / LPB)] = (char)sc.byte;
+      if constexpr (EF) {
+        if (g < a.end) {
+          float d[EPL];
+          M::template unpack<EPL>(q, mx_scale_value(sc.byte), d);
+#pragma unroll
+          for (int i = 0; i < EPL; ++i) d[i] = (uint32_t)i < have[u] ? ef_residual(f[i], d[i]) : 0.0f;
+#pragma unroll
+          for (int j = 0; j < EPL / 4; ++j) {
+            uint4 y;
+            __builtin_memcpy(&y, &d[4 * j], 16);
+            *reinterpret_cast<uint4*>(res + pos + 4 * j) = y;
+          }
+        }
+      }
+    }
+  }
+}
+
+// Every lane of a tensor's blocks loads, converts and (ROT) takes part in the rotation; only the stores are
+// masked, by the tensor's end, and go out as one vector where the tensor is 16-byte aligned.
+template <MxFormat F, DType DT, bool ROT>
+__global__ __launch_bounds__(256) void k_mx_dequantize_list(const MxListArgs a, const char* __restrict__ wire,
+                                                            uint32_t cb, uint32_t spc, uint32_t s0, uint32_t s1,
+                                                            uint32_t rot_signs) {
+  using T = Tr<DT>;
+  using S = typename T::S;
+  constexpr int EPL = 16 / (int)sizeof(S);
+  constexpr int LPB = kern::kMxBlock / EPL;
+  using M = MxFmt<F>;
+  constexpr int QB = EPL * M::kPayload / kern::kMxBlock, QW = M::template kWords<EPL>;
+  __shared__ MxListTable t;
+  list_table_load(a, t);
+  const uint32_t nvec = cb * LPB;
+  for (uint32_t s = s0 + blockIdx.x; s < s1; s += gridDim.x) {
+    const uint32_t chunk = s / spc, vs = (s - chunk * spc) * (256u * kMxUnroll);
+    const char* __restrict__ w = wire + (size_t)chunk * kern::mx_chunk_bytes(F, cb);
+    const uint32_t gb = chunk * cb;
+    const uint32_t gs = gb + vs / LPB;
+    MxListCursor cur{list_find(t, a.n, gs > a.g0 ? gs : a.g0)};
+    uint32_t q[kMxUnroll][QW];
+    uint32_t sb[kMxUnroll];
+#pragma unroll
+    for (int u = 0; u < kMxUnroll; ++u) {
+      const uint32_t v = vs + threadIdx.x + u * 256u, g = gb + v / LPB;
+      sb[u] = 127u;
+#pragma unroll
+      for (int d = 0; d < QW; ++d) q[u][d] = 0u;
+      if (v < nvec && g >= a.g0 && g < a.end) {
+        if constexpr (M::kLanes) M::template ld_lanes<EPL>(w, v, q[u]);
+        else ld_wire<QB>(w + (size_t)v * QB, q[u]);
+        sb[u] = (uint8_t)w[kern::mx_scale_off(F, cb, v / LPB)];
+      }
+    }
+    if constexpr (M::kLanes) {  // (v % 4 is the lane's place in its hardware quad: vs is a multiple of 64)
+#pragma unroll
+      for (int u = 0; u < kMxUnroll; ++u) M::template gather<EPL>(vs + threadIdx.x + u * 256u, q[u]);
+    }
+#pragma unroll
+    for (int u = 0; u < kMxUnroll; ++u) {
+      const uint32_t v = vs + threadIdx.x + u * 256u, g = gb + v / LPB;
+      if (v >= nvec) break;
+      if (g < a.g0 || g >= a.end) continue;
+      float f[EPL];
+      M::template unpack<EPL>(q[u], mx_scale_value(sb[u]), f);
+      if constexpr (ROT) rot_inverse<EPL>(f, rot_signs, v % LPB);
+      S o[EPL];
+#pragma unroll
+      for (int i = 0; i < EPL; ++i) o[i] = T::out(f[i]);
+      uint64_t el;
+      const uint32_t nv = cur.template seek<EPL>(t, a.n, g, v % LPB, &el);
+      char* p = const_cast<char*>(t.base[cur.idx]) + el * sizeof(S);
+      if (nv == (uint32_t)EPL && (reinterpret_cast<uintptr_t>(p) & 15u) == 0) {
+        uint4 x;
+        __builtin_memcpy(&x, o, 16);
+        *reinterpret_cast<uint4*>(p) = x;
+      } else {
+#pragma unroll
+        for (int i = 0; i < EPL; ++i)
+          if ((uint32_t)i < nv) reinterpret_cast<S*>(p)[i] = o[i];
+      }
+    }
+  }
+}
+
 // grid row of `nvec` vectors with `per` of them per lane and pass, at most `most` workgroups in all
 // rows (the kernels loop past that). Quantize / dequantize: one pass per workgroup up to 2^20 of them;
 // reduce: a grid-stride loop over 8 workgroups per CU.
@@ -1040,6 +1272,102 @@ hipError_t mx_dequantize_shards(const void* wire, size_t cb, size_t nchunks, voi
   if (!mx_shards_ok(m, cb, nchunks) || !mx_al16(wire) || !mx_al16(dst)) return hipErrorInvalidValue;
   const bool vec = m * mx_esize(t) % 16 == 0;
   return mx_dequantize_any(fmt, t, true, vec, wire, cb, nchunks, dst, m * nchunks, m, stream, rot_signs);
+}
+
+// ---- tensor lists: one launch per kMaxMxListDescs tensors that own a block
+namespace {
+template <MxFormat F, DType DT, bool ROT>
+void mx_quantize_list_go(const dim3& grid, const dev::MxListArgs& a, char* w, uint32_t cb, uint32_t spc, uint32_t s0,
+                         uint32_t s1, float* res, const MxSr* sr, hipStream_t stream, uint32_t signs) {
+  if (sr) hipLaunchKernelGGL((dev::k_mx_quantize_list<F, DT, false, true, ROT>), grid, dim3(256), 0, stream, a, w, cb, spc, s0, s1, nullptr, sr->key, sr->base, signs);
+  else if (res) hipLaunchKernelGGL((dev::k_mx_quantize_list<F, DT, true, false, ROT>), grid, dim3(256), 0, stream, a, w, cb, spc, s0, s1, res, 0u, 0u, signs);
+  else hipLaunchKernelGGL((dev::k_mx_quantize_list<F, DT, false, false, ROT>), grid, dim3(256), 0, stream, a, w, cb, spc, s0, s1, res, 0u, 0u, signs);
+}
+template <MxFormat F, DType DT, bool ROT>
+void mx_dequantize_list_go(const dim3& grid, const dev::MxListArgs& a, char* w, uint32_t cb, uint32_t spc, uint32_t s0,
+                           uint32_t s1, float*, const MxSr*, hipStream_t stream, uint32_t signs) {
+  hipLaunchKernelGGL((dev::k_mx_dequantize_list<F, DT, ROT>), grid, dim3(256), 0, stream, a, w, cb, spc, s0, s1, signs);
+}
+template <bool QUANT, MxFormat F, DType DT, class... A>
+void mx_list_rot(const uint32_t* rot, A... a) {
+  if constexpr (QUANT) {
+    if (rot) mx_quantize_list_go<F, DT, true>(a..., *rot);
+    else mx_quantize_list_go<F, DT, false>(a..., 0u);
+  } else {
+    if (rot) mx_dequantize_list_go<F, DT, true>(a..., *rot);
+    else mx_dequantize_list_go<F, DT, false>(a..., 0u);
+  }
+}
+template <bool QUANT, MxFormat F, class... A>
+void mx_list_dt(DType t, A... a) {
+  switch (t) {
+    case DType::F32: mx_list_rot<QUANT, F, DType::F32>(a...); break;
+    case DType::BF16: mx_list_rot<QUANT, F, DType::BF16>(a...); break;
+    default: mx_list_rot<QUANT, F, DType::F16>(a...); break;
+  }
+}
+// Quantize (QUANT) or dequantize the list in launches of up to kMaxMxListDescs tensors. A launch owns the
+// blocks from its first tensor's to the next launch's; the last one of a quantize also owns the padding
+// blocks up to cb * nchunks, and a list without a block is one launch of padding alone.
+template <bool QUANT>
+hipError_t mx_list_run(const MxListTensor* ts, size_t k, DType t, char* wire, size_t cb, size_t nchunks, MxFormat fmt,
+                       const uint32_t* rot, float* res, const MxSr* sr, hipStream_t stream) {
+  if (!mx_fmt_ok(fmt) || !mx_dtype_ok(t) || !mx_cb_ok(cb) || nchunks == 0 || nchunks > 65535 || !mx_al16(wire))
+    return hipErrorInvalidValue;
+  if (k > 65535 || (k && !ts)) return hipErrorInvalidValue;
+  const uint64_t total = (uint64_t)cb * nchunks;  // blocks on the wire; the kernels count them in 32 bits
+  if (total >= (uint64_t(1) << 32) || mx_list_blocks(ts, k) > total) return hipErrorInvalidValue;
+  for (size_t i = 0; i < k; ++i)
+    if (ts[i].numel && (!ts[i].base || reinterpret_cast<uintptr_t>(ts[i].base) % mx_esize(t))) return hipErrorInvalidValue;
+  const uint32_t lpb = t == DType::F32 ? 8 : 4, span = 256u * dev::kMxUnroll;
+  const uint32_t spc = (uint32_t)(((uint64_t)cb * lpb + span - 1) / span);  // spans per chunk
+  const auto span_of = [&](uint64_t g) { return (uint32_t)(g / cb * spc + g % cb * lpb / span); };
+  size_t i = 0;
+  uint64_t first = 0;  // B_i
+  bool more = true;
+  while (more) {
+    dev::MxListArgs a{};
+    a.g0 = (uint32_t)first;
+    for (; i < k && a.n < (uint32_t)kMaxMxListDescs; ++i) {
+      if (ts[i].numel == 0) continue;  // (owns no block)
+      a.d[a.n++] = dev::MxListDesc{static_cast<const char*>(ts[i].base), (uint64_t)ts[i].numel, (uint32_t)first};
+      first += mx_blocks(ts[i].numel);
+    }
+    while (i < k && ts[i].numel == 0) ++i;
+    more = i < k;
+    a.end = (uint32_t)first;
+    a.g1 = QUANT && !more ? (uint32_t)total : a.end;
+    if (a.g1 == a.g0) break;  // (a dequantize without a block)
+    const uint32_t s0 = span_of(a.g0), s1 = span_of(a.g1 - 1) + 1;
+    const dim3 grid((uint32_t)std::min<uint64_t>(s1 - s0, dev::kMxGridStream));
+    const uint32_t c = (uint32_t)cb;
+    if (fmt == MxFormat::FP4_E2M1) mx_list_dt<QUANT, MxFormat::FP4_E2M1>(t, rot, grid, a, wire, c, spc, s0, s1, res, sr, stream);
+    else if (fmt == MxFormat::FP6_E2M3) mx_list_dt<QUANT, MxFormat::FP6_E2M3>(t, rot, grid, a, wire, c, spc, s0, s1, res, sr, stream);
+    else mx_list_dt<QUANT, MxFormat::FP8_E4M3>(t, rot, grid, a, wire, c, spc, s0, s1, res, sr, stream);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+  }
+  return hipSuccess;
+}
+}  // namespace
+
+hipError_t mx_quantize_list(const MxListTensor* ts, size_t k, DType t, void* wire, size_t cb, size_t nchunks,
+                            hipStream_t stream, MxFormat fmt, const uint32_t* rot_signs, float* residual,
+                            const MxListSr* sr) {
+  if (residual && sr) return hipErrorInvalidValue;
+  const size_t n = mx_list_numel(ts, k);
+  if (residual && !mx_al16(residual)) return hipErrorInvalidValue;
+  if (sr && sr->index_offset + n < sr->index_offset) return hipErrorInvalidValue;
+  const MxSr s{sr ? mx_sr_key(sr->seed, sr->stream) : 0u, sr ? sr->index_offset : 0u};
+  // (no block: no residual to update, the wire is all padding blocks)
+  return mx_list_run<true>(ts, k, t, static_cast<char*>(wire), cb, nchunks, fmt, rot_signs, n ? residual : nullptr,
+                           sr ? &s : nullptr, stream);
+}
+
+hipError_t mx_dequantize_list(const void* wire, size_t cb, size_t nchunks, const MxListTensor* ts, size_t k, DType t,
+                              hipStream_t stream, MxFormat fmt, const uint32_t* rot_signs) {
+  return mx_list_run<false>(ts, k, t, const_cast<char*>(static_cast<const char*>(wire)), cb, nchunks, fmt, rot_signs,
+                            nullptr, nullptr, stream);
 }
 
 namespace {

@@ -31,6 +31,9 @@
 * :func:`mx_quantize_shards`, :func:`mx_dequantize_shards`, :func:`mx_fold` -- the same wire with one
   chunk per shard (docs/collectives.md "Compressed reduce-scatter and all-gather") and the fold of
   chunk wires straight into a tensor; ``reduce_scatter_compressed`` / ``all_gather_compressed``.
+* :func:`mx_quantize_list`, :func:`mx_dequantize_list`, :func:`mx_list_numel` -- the same wire for a list of
+  tensors, read and written where they are, every tensor starting a fresh block (docs/collectives.md
+  "Tensor-list layout"); ``all_reduce_compressed`` of a list and ``GradBucketer(in_place=True)``.
 
 Every function runs on the current HIP stream and raises if the native
 extension is missing (no silent eager fallback). ``*_reference`` functions are
@@ -338,6 +341,66 @@ def mx_dequantize(w: torch.Tensor, /, numel: int, dtype: torch.dtype = torch.flo
             raise ValueError(f"mx_dequantize: out has {out.numel()} elements, numel is {numel}")
     _C().mx_dequantize(w, int(world), out, wire, **rot)
     return out
+
+
+def mx_list_numel(numels: Sequence[int]) -> int:
+    """Elements of the virtual tensor of a tensor list (docs/collectives.md "Tensor-list layout"): every tensor
+    starts a fresh block, so ``32 * sum(ceil(n_i / 32))``. The size of a list's residual."""
+    return MX_BLOCK * sum((int(n) + MX_BLOCK - 1) // MX_BLOCK for n in numels)
+
+
+def _mx_check_list(xs, who: str) -> list:
+    """The tensors of a list call: a list or tuple of tensors of one MX dtype on one device, contiguous (they are
+    read and written where they are, so none can go through a copy)."""
+    if not isinstance(xs, (list, tuple)) or not all(isinstance(x, torch.Tensor) for x in xs):
+        raise TypeError(f"{who}: a list or tuple of tensors expected")
+    if not xs:
+        raise ValueError(f"{who}: an empty list has no device and no dtype")
+    if len(xs) > 65535:
+        raise ValueError(f"{who}: at most 65535 tensors in a list, got {len(xs)}")
+    _mx_check_dtype(xs[0].dtype, who)
+    for x in xs:
+        if x.dtype != xs[0].dtype:
+            raise TypeError(f"{who}: the tensors of a list share one dtype, got {xs[0].dtype} and {x.dtype}")
+        if x.device != xs[0].device:
+            raise ValueError(f"{who}: the tensors of a list share one device, got {xs[0].device} and {x.device}")
+        if not x.is_contiguous():
+            raise ValueError(f"{who}: the tensors of a list must be contiguous")
+    return [x.detach() for x in xs]
+
+
+def mx_quantize_list(xs: Sequence[torch.Tensor], world: int = 1, out: torch.Tensor | None = None, *,
+                     wire: str = "mxfp8_e4m3", residual: torch.Tensor | None = None, rounding: str = "nearest",
+                     seed: int = 0, stream: int = 0, rotation: str | None = None,
+                     rotation_seed: int = 0) -> torch.Tensor:
+    """The tensors ``xs`` (GPU, one dtype, contiguous) -> the wire of their tensor-list layout (docs/collectives.md
+    "Tensor-list layout"), read where they are: byte for byte ``mx_quantize`` of their concatenation with every
+    tensor zero-padded to a multiple of 32 elements, so no block holds elements of two tensors. A tensor that is
+    not 16-byte aligned is read element by element; the others move as vectors.
+
+    ``residual``: float32, ``mx_list_numel`` elements, indexed by the position in that padded concatenation; the
+    positions past a tensor's end are left as +0. ``rounding``, ``seed``, ``stream``: as in :func:`mx_quantize`,
+    the word index of an element being its position in the padded concatenation. ``rotation``: as there."""
+    xs = _mx_check_list(xs, "mx_quantize_list")
+    _mx_payload(wire, "mx_quantize_list")
+    n = mx_list_numel([x.numel() for x in xs])
+    rot = _mx_check_rotation(rotation, rotation_seed, "mx_quantize_list")
+    if _mx_check_rounding(rounding, seed, stream, 0, n, residual, "mx_quantize_list"):
+        return _C().mx_quantize_list(xs, int(world), out, wire, None, True, seed, stream, **rot)
+    if residual is None:
+        return _C().mx_quantize_list(xs, int(world), out, wire, **rot)
+    _mx_check_residual(residual, n, xs[0].device, "mx_quantize_list")
+    return _C().mx_quantize_list(xs, int(world), out, wire, residual.detach(), **rot)
+
+
+def mx_dequantize_list(w: torch.Tensor, /, outs: Sequence[torch.Tensor], world: int = 1, *,
+                       wire: str = "mxfp8_e4m3", rotation: str | None = None, rotation_seed: int = 0) -> None:
+    """The wire ``w`` of a tensor list in ``world`` chunks -> the tensors ``outs`` (GPU, one dtype, contiguous),
+    written where they are: exactly their elements and nothing else. ``rotation``, ``rotation_seed``: those of
+    the :func:`mx_quantize_list` that made the wire."""
+    outs = _mx_check_list(outs, "mx_dequantize_list")
+    _mx_payload(wire, "mx_dequantize_list")
+    _C().mx_dequantize_list(w, outs, int(world), wire, **_mx_check_rotation(rotation, rotation_seed, "mx_dequantize_list"))
 
 
 def _mx_check_shards(numel: int, world: int, who: str) -> int:
@@ -726,6 +789,41 @@ def mx_dequantize_reference(w: torch.Tensor, /, numel: int, dtype: torch.dtype =
     if rot:
         d = _mx_rot_inverse(d, mx_rotation_signs(rotation_seed))
     return d.reshape(-1)[:int(numel)].to(dtype)
+
+
+def _mx_list_pad(n: int) -> int:
+    return -int(n) % MX_BLOCK
+
+
+def mx_quantize_list_reference(xs: Sequence[torch.Tensor], world: int = 1, *, wire: str = "mxfp8_e4m3",
+                               residual: torch.Tensor | None = None, rounding: str = "nearest", seed: int = 0,
+                               stream: int = 0, rotation: str | None = None, rotation_seed: int = 0) -> torch.Tensor:
+    """Plain-PyTorch :func:`mx_quantize_list` on CPU tensors: :func:`mx_quantize_reference` of the concatenation
+    of the tensors, each zero-padded to a multiple of 32 elements. ``residual`` is updated in place; its
+    positions past a tensor's end are left as +0."""
+    xs = _mx_check_list(xs, "mx_quantize_list_reference")
+    flat = torch.cat([torch.nn.functional.pad(x.reshape(-1), (0, _mx_list_pad(x.numel()))) for x in xs])
+    w = mx_quantize_reference(flat, world, wire=wire, residual=residual, rounding=rounding, seed=seed, stream=stream,
+                              rotation=rotation, rotation_seed=rotation_seed)
+    if residual is not None:
+        at, r = 0, residual.detach().view(-1)
+        for x in xs:
+            at += x.numel() + _mx_list_pad(x.numel())
+            r[at - _mx_list_pad(x.numel()):at] = 0.0
+    return w
+
+
+def mx_dequantize_list_reference(w: torch.Tensor, /, outs: Sequence[torch.Tensor], world: int = 1, *,
+                                 wire: str = "mxfp8_e4m3", rotation: str | None = None, rotation_seed: int = 0) -> None:
+    """Plain-PyTorch :func:`mx_dequantize_list` on a CPU wire: :func:`mx_dequantize_reference` of the padded
+    concatenation, split into ``outs``."""
+    outs = _mx_check_list(outs, "mx_dequantize_list_reference")
+    d = mx_dequantize_reference(w, mx_list_numel([o.numel() for o in outs]), outs[0].dtype, world, wire=wire,
+                                rotation=rotation, rotation_seed=rotation_seed)
+    at = 0
+    for o in outs:
+        o.copy_(d[at:at + o.numel()].view_as(o))
+        at += o.numel() + _mx_list_pad(o.numel())
 
 
 def mx_quantize_shards_reference(x: torch.Tensor, world: int, *, wire: str = "mxfp8_e4m3",

@@ -198,12 +198,21 @@ def all_reduce_compressed(tensor: torch.Tensor, op=dist.ReduceOp.SUM, group=None
     of this rank's contribution with the sign word of ``rotation_seed`` before it is quantized and rotates
     the gathered result back; the owner stage folds and requantizes rotated chunks as they are. Every rank
     must pass the same rotation and seed. Composes with the residuals (which then live in the rotated
-    domain: keep the seed for as long as they are carried) and with stochastic rounding."""
+    domain: keep the seed for as long as they are carried) and with stochastic rounding.
+
+    A list or tuple of tensors (one dtype, one device, contiguous) in place of ``tensor`` is reduced in the
+    tensor-list layout (docs/collectives.md "Tensor-list layout"): every tensor is quantized from and dequantized
+    into its own memory, with no flat copy, and starts a fresh block. ``residual`` then has
+    ``ops.mx_list_numel(numels)`` elements and ``owner_residual`` ``ops.mx_owner_residual_numel`` of that many.
+    Every rank passes lists of the same sizes; an empty list touches nothing."""
     opn = _op_name(op)
     if opn is None:
         raise ValueError(f"all_reduce_compressed: only ReduceOp.SUM and ReduceOp.AVG are supported, got {op}")
     if wire not in WIRES:
         raise ValueError(f"all_reduce_compressed: unknown wire format {wire!r} (supported: {', '.join(WIRES)})")
+    if isinstance(tensor, (list, tuple)):
+        return _all_reduce_list(list(tensor), opn, group, wire, async_op, residual, owner_residual, rounding, seed,
+                                rotation, rotation_seed)
     if tensor.dtype not in ops.MX_DTYPES:
         raise TypeError(f"all_reduce_compressed: float32, bfloat16 or float16 tensors only, got {tensor.dtype}")
     world = dist.get_world_size(group)
@@ -223,6 +232,51 @@ def all_reduce_compressed(tensor: torch.Tensor, op=dist.ReduceOp.SUM, group=None
     held = tuple(t for t in (tensor, residual, owner_residual) if t is not None)
     return _issue_gpu(lambda: _run_gpu(tensor, opn, group, world, wire, residual, owner_residual, sr, rot), held,
                       async_op)
+
+
+def _all_reduce_list(xs, opn, group, wire, async_op, residual, owner_residual, rounding, seed, rotation,
+                     rotation_seed):
+    """:func:`all_reduce_compressed` of a list of tensors (one dtype, one device, contiguous) in the tensor-list
+    layout (docs/collectives.md "Tensor-list layout"): the same sequence, with a quantize that reads the tensors
+    where they are and a dequantize that writes them where they are. Every tensor starts a fresh block, so no
+    scale is shared between two tensors, and the result is what the call on the concatenation of the tensors,
+    each zero-padded to a multiple of 32 elements, leaves in it. ``residual`` has ``ops.mx_list_numel(numels)``
+    elements, ``owner_residual`` ``ops.mx_owner_residual_numel`` of that many."""
+    who = "all_reduce_compressed"
+    world = dist.get_world_size(group)
+    if xs:
+        ops._mx_check_list(xs, who)
+    n = ops.mx_list_numel([x.numel() for x in xs])
+    device = xs[0].device if xs else None
+    if residual is not None or owner_residual is not None:
+        if not xs:
+            raise ValueError(f"{who}: an empty list has no residual")
+        _check_residual(who, "residual", residual, n, device)
+        _check_residual(who, "owner_residual", owner_residual, ops.mx_owner_residual_numel(n, world, wire=wire), device)
+    sr = _rounding_args(who, rounding, seed, group, (residual, owner_residual))
+    rot = _rotation_args(who, rotation, rotation_seed)
+    if world == 1 or n == 0:
+        return _done(async_op)
+    gpu = xs[0].is_cuda
+    if gpu and world > MAX_GPU_WORLD:
+        raise ValueError(f"{who}: GPU groups of up to {MAX_GPU_WORLD} ranks, got {world}")
+    quantize, reduce, dequantize = ((ops.mx_quantize_list, ops.mx_reduce, ops.mx_dequantize_list) if gpu else
+                                    (ops.mx_quantize_list_reference, ops.mx_reduce_reference,
+                                     ops.mx_dequantize_list_reference))
+
+    def run():
+        w = quantize(xs, world, wire=wire, residual=residual, **sr[0], **rot)
+        recv = torch.empty_like(w)
+        dist.all_to_all_single(recv, w, group=group)  # chunk r of every rank -> rank r, in rank order
+        mine = reduce(recv, world, opn, wire=wire, residual=owner_residual, **sr[1])
+        dist.all_gather_into_tensor(w, mine, group=group)
+        dequantize(w, xs, world, wire=wire, **rot)
+
+    if not gpu:
+        with torch.no_grad():
+            run()
+        return _done(async_op)
+    return _issue_gpu(run, tuple(xs) + tuple(t for t in (residual, owner_residual) if t is not None), async_op)
 
 
 def _issue_gpu(run, tensors, async_op):

@@ -42,6 +42,9 @@ contract, MI355X-first:
 * ``rotation="hadamard"`` (with a wire, together with either or neither of the two): every block of a
   bucket is rotated by a randomized Hadamard matrix before it is quantized and back afterwards, which
   keeps a block's small gradients on the grid next to an outlier (docs/collectives.md "Hadamard rotation").
+* ``in_place=True`` (with a wire, together with any of the above): no flat buckets. A complete bucket is reduced
+  as the list of its ``.grad`` tensors, quantized from and dequantized into their own memory
+  (docs/collectives.md "Tensor-list layout"): no pack, no unpack, no second copy of the gradients.
 
 ``broadcast_parameters`` and ``scatter_batch`` cover the other two uses.
 torch's own ``DistributedDataParallel`` also runs unchanged on this backend.
@@ -74,10 +77,12 @@ def scatter_batch(batch: torch.Tensor | None, shard_shape, dtype, device, src: i
 
 
 class _Bucket:
-    def __init__(self, params: List[torch.nn.Parameter], dtype, device):
+    def __init__(self, params: List[torch.nn.Parameter], dtype, device, in_place: bool = False):
         self.params = params
+        self.device = device
         self.numel = sum(p.numel() for p in params)
-        self.flat = torch.empty(self.numel, dtype=dtype, device=device)
+        # in place: the gradients are reduced where they are (the tensor-list layout), there is no flat copy
+        self.flat = None if in_place else torch.empty(self.numel, dtype=dtype, device=device)
         self.offsets = []
         off = 0
         for p in params:
@@ -105,12 +110,24 @@ class GradBucketer:
     ``rotation="hadamard"`` with ``rotation_seed`` (needs ``wire``; composes with either of the above): every
     ``all_reduce_compressed`` rotates the blocks of the bucket before it quantizes them and back afterwards
     (docs/collectives.md "Hadamard rotation"). The seed is fixed for the object's life -- it does not step,
-    the residuals live in the rotated domain of that one seed -- and must be the same on every rank."""
+    the residuals live in the rotated domain of that one seed -- and must be the same on every rank.
+
+    ``in_place=True`` (needs ``wire``; composes with all of the above): no flat bucket is allocated and no
+    gradient is copied. The hook only counts down; a complete bucket goes to ``all_reduce_compressed`` as the
+    list of its ``.grad`` tensors (docs/collectives.md "Tensor-list layout"), which quantizes them from and
+    dequantizes them into their own memory, and :meth:`finish` only waits. Every gradient starts a fresh block,
+    so no scale byte serves two parameters; the residuals are sized for that layout
+    (``ops.mx_list_numel``). The gradients must be contiguous. The default ``False`` is the packed path."""
 
     def __init__(self, module: torch.nn.Module, group=None, bucket_bytes: int = 256 << 20,
                  average: bool = True, wire: str | None = None, error_feedback: bool = False,
-                 rounding: str = "nearest", seed: int = 0, rotation: str | None = None, rotation_seed: int = 0):
+                 rounding: str = "nearest", seed: int = 0, rotation: str | None = None, rotation_seed: int = 0,
+                 in_place: bool = False):
         from .compressed import ROUNDINGS, _rotation_args
+
+        if in_place and wire is None:
+            raise ValueError("GradBucketer: in_place=True needs a compressed wire (wire=None reduces flat buckets)")
+        self.in_place = bool(in_place)
 
         self._rot = _rotation_args("GradBucketer", rotation, rotation_seed)
         if rotation is not None and wire is None:
@@ -158,12 +175,14 @@ class GradBucketer:
         if cur:
             self._add_bucket(cur)
         if self.error_feedback:
-            from ..ops import mx_owner_residual_numel
+            from ..ops import mx_list_numel, mx_owner_residual_numel
 
             for b in self.buckets:
-                b.residual = torch.zeros(b.numel, dtype=torch.float32, device=b.flat.device)
-                b.owner_residual = torch.zeros(mx_owner_residual_numel(b.numel, self.world, wire=wire),
-                                               dtype=torch.float32, device=b.flat.device)
+                # (in place: one float per position of the list layout, where every gradient starts a block)
+                n = mx_list_numel([p.numel() for p in b.params]) if self.in_place else b.numel
+                b.residual = torch.zeros(n, dtype=torch.float32, device=b.device)
+                b.owner_residual = torch.zeros(mx_owner_residual_numel(n, self.world, wire=wire),
+                                               dtype=torch.float32, device=b.device)
         self._hooks = [p.register_post_accumulate_grad_hook(self._on_grad) for p in params]
         self._sync = True
         # (a compressed wire divides before it requantizes: always fused)
@@ -182,7 +201,7 @@ class GradBucketer:
             self._sync = prev
 
     def _add_bucket(self, ps):
-        b = _Bucket(ps, ps[0].dtype, ps[0].device)
+        b = _Bucket(ps, ps[0].dtype, ps[0].device, self.in_place)
         idx = len(self.buckets)
         for i, p in enumerate(ps):
             self._where[id(p)] = (idx, i)
@@ -202,8 +221,9 @@ class GradBucketer:
             raise RuntimeError(
                 "GradBucketer: a gradient arrived for a bucket that is already being reduced -- two backward "
                 "passes without finish() in between; wrap the accumulation steps in `with bucketer.no_sync():`")
-        off = b.offsets[i]
-        b.flat[off:off + p.numel()].copy_(p.grad.reshape(-1))
+        if not self.in_place:
+            off = b.offsets[i]
+            b.flat[off:off + p.numel()].copy_(p.grad.reshape(-1))
         b.pending -= 1
         if b.pending == 0:
             b.work = self._reduce(b)
@@ -212,12 +232,13 @@ class GradBucketer:
         if self.wire is not None:
             from .compressed import all_reduce_compressed
 
+            what = [p.grad for p in b.params] if self.in_place else b.flat
             if self.rounding == "stochastic":
                 nb = len(self.buckets)
                 seed = (self.seed + self.rounding_step * nb + self.buckets.index(b)) % (1 << 64)
-                return all_reduce_compressed(b.flat, dist.ReduceOp.AVG, group=self.group, wire=self.wire,
+                return all_reduce_compressed(what, dist.ReduceOp.AVG, group=self.group, wire=self.wire,
                                              async_op=True, rounding="stochastic", seed=seed, **self._rot)
-            return all_reduce_compressed(b.flat, dist.ReduceOp.AVG, group=self.group, wire=self.wire, async_op=True,
+            return all_reduce_compressed(what, dist.ReduceOp.AVG, group=self.group, wire=self.wire, async_op=True,
                                          residual=b.residual, owner_residual=b.owner_residual, **self._rot)
         return dist.all_reduce(b.flat, op=self._op, group=self.group, async_op=True)
 
@@ -229,10 +250,13 @@ class GradBucketer:
                     if p.grad is None:
                         p.grad = torch.zeros_like(p)
                 for p, off in zip(b.params, b.offsets):
-                    b.flat[off:off + p.numel()].copy_(p.grad.reshape(-1))
+                    if not self.in_place:
+                        b.flat[off:off + p.numel()].copy_(p.grad.reshape(-1))
                 b.work = self._reduce(b)
         for b in self.buckets:
             b.work.wait()
+            if self.in_place:  # (the collective wrote the gradients themselves)
+                continue
             if self.average and self.world > 1 and not self._fused_avg:
                 b.flat.div_(self.world)
             _unpack(b)
@@ -262,7 +286,7 @@ def _is_native(group, buckets) -> bool:
     try:
         from .backend import native_backend
 
-        native_backend(group, buckets[0].flat.device.type)
+        native_backend(group, buckets[0].device.type)
         return True
     except Exception:
         return False
