@@ -175,7 +175,7 @@ c10::intrusive_ptr<c10d::Work> ProcessGroupMI355X::allgather_into_tensor_coalesc
   bool padded = false;
   const size_t S = pack_layout(bytes, off, padded);  // one rank's block of the gathered buffer
   const bool gpu = inputs[0].is_cuda();
-  if (size_ == 1 && (!gpu || cfg_.world1_local)) {
+  if ((size_ == 1 && (!gpu || cfg_.world1_local)) || (gpu && S == 0)) {  // (all members empty: nothing to gather)
     before_op(Coll::ALLGATHER, inputs, -1);
     for (size_t i = 0; i < inputs.size(); ++i) outputs[i].view(-1).copy_(inputs[i].reshape(-1));
     record(Coll::ALLGATHER, "local", S, t0);
@@ -244,7 +244,7 @@ c10::intrusive_ptr<c10d::Work> ProcessGroupMI355X::reduce_scatter_tensor_coalesc
   const size_t S = pack_layout(bytes, off, padded);  // one rank's chunk of the flat input
   const bool gpu = outputs[0].is_cuda();
   const auto dt = outputs[0].scalar_type();
-  if (size_ == 1 && (!gpu || cfg_.world1_local)) {
+  if ((size_ == 1 && (!gpu || cfg_.world1_local)) || (gpu && S == 0)) {  // (all members empty: nothing to reduce)
     before_op(Coll::REDUCE_SCATTER, outputs, -1);
     for (size_t i = 0; i < inputs.size(); ++i) outputs[i].view(-1).copy_(inputs[i].reshape(-1));
     record(Coll::REDUCE_SCATTER, "local", S, t0);
