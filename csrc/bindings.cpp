@@ -375,6 +375,59 @@ void mx_fold(const at::Tensor& wire, int nsrc, const std::string& op, at::Tensor
   if (!o.is_same(out)) out.copy_(o);
 }
 
+// ---- gradient clipping (kernels/grad_clip.hip, docs/collectives.md "Gradient clipping"). The tensors are read and
+// written where they are, at any alignment: nothing goes through a copy.
+pdcc::kern::DType clip_dtype(const at::Tensor& t, const char* who) {
+  TORCH_CHECK_VALUE(t.scalar_type() == at::kFloat || t.scalar_type() == at::kBFloat16 || t.scalar_type() == at::kHalf,
+                    who, ": float32, bfloat16 or float16 tensors only, got ", t.scalar_type());
+  return kdtype(t.scalar_type());
+}
+void clip_check_total(const at::Tensor& t, const at::Device& dev, const char* who, const char* what) {
+  TORCH_CHECK_VALUE(t.scalar_type() == at::kDouble && t.numel() == 1 && t.device() == dev, who, ": ", what,
+                    " must be one float64 element on ", dev);
+}
+
+at::Tensor sumsq(const std::vector<at::Tensor>& xs, const c10::optional<at::Tensor>& out, int max_blocks) {
+  const char* who = "sumsq";
+  TORCH_CHECK_VALUE(!xs.empty(), who, ": an empty list has no device");
+  const at::Device dev = xs[0].device();
+  TORCH_CHECK(dev.is_cuda(), who, ": GPU tensors only");
+  std::vector<pdcc::kern::SumsqTensor> ts;
+  int64_t tiles = 0;
+  for (const auto& x : xs) {
+    TORCH_CHECK_VALUE(x.device() == dev, who, ": the tensors share one device, got ", dev, " and ", x.device());
+    TORCH_CHECK_VALUE(x.is_contiguous(), who, ": the tensors must be contiguous");
+    ts.push_back({x.numel() ? x.data_ptr() : nullptr, (size_t)x.numel(), clip_dtype(x, who)});
+    tiles += (int64_t)pdcc::kern::sumsq_tiles((size_t)x.numel());
+  }
+  c10::hip::HIPGuardMasqueradingAsCUDA g(dev);
+  const auto f64 = xs[0].options().dtype(at::kDouble);
+  at::Tensor o = out ? *out : at::empty({1}, f64);
+  clip_check_total(o, dev, who, "out");
+  at::Tensor partials = at::empty({std::max<int64_t>(tiles, 1)}, f64);
+  hipStream_t s = c10::hip::getCurrentHIPStreamMasqueradingAsCUDA(dev.index()).stream();
+  hipError_t e = pdcc::kern::sumsq(ts.data(), ts.size(), partials.data_ptr<double>(), o.data_ptr<double>(), s, max_blocks);
+  TORCH_CHECK(e == hipSuccess, who, " launch failed: ", hipGetErrorString(e));
+  return o;
+}
+
+void clip_scale(const at::Tensor& src, const at::Tensor& total, double max_norm, at::Tensor& out) {
+  const char* who = "clip_scale";
+  TORCH_CHECK(src.is_cuda(), who, ": GPU tensors only");
+  const auto sd = clip_dtype(src, who), od = clip_dtype(out, who);
+  clip_check_total(total, src.device(), who, "total");
+  TORCH_CHECK_VALUE(out.device() == src.device() && out.numel() == src.numel(), who, ": out must hold ", src.numel(),
+                    " elements on ", src.device());
+  TORCH_CHECK_VALUE(od == pdcc::kern::DType::F32 || od == sd, who, ": out must be float32 or of src's dtype, got ",
+                    out.scalar_type(), " for ", src.scalar_type());
+  TORCH_CHECK_VALUE(src.is_contiguous() && out.is_contiguous(), who, ": src and out must be contiguous");
+  c10::hip::HIPGuardMasqueradingAsCUDA g(src.device());
+  hipStream_t s = c10::hip::getCurrentHIPStreamMasqueradingAsCUDA(src.device().index()).stream();
+  hipError_t e = pdcc::kern::clip_scale(src.data_ptr(), sd, total.data_ptr<double>(), (float)max_norm, out.data_ptr(), od,
+                                        (size_t)src.numel(), s);
+  TORCH_CHECK(e == hipSuccess, who, " launch failed: ", hipGetErrorString(e));
+}
+
 // Peer links between every pair of visible GPUs, as the runtime reports them: HSA link
 // type (xGMI on an MI355X node, PCIe otherwise), hop count, P2P access / atomics and
 // the runtime's relative performance rank. Local queries only (no collective).
@@ -575,6 +628,13 @@ PYBIND11_MODULE(_C, m) {
   m.def("mx_chunk_blocks", [](int64_t numel, int world, const std::string& fmt) {
     return (int64_t)pdcc::kern::mx_chunk_blocks(mx_format(fmt, "mx_chunk_blocks"), (size_t)numel, world);
   }, py::arg("numel"), py::arg("world"), py::arg("fmt") = "mxfp8_e4m3");
+  m.def("sumsq", &sumsq, py::arg("xs"), py::arg("out") = py::none(), py::arg("max_blocks") = 0,
+        "the sum of the squares of a list of f32 / bf16 / f16 GPU tensors as one float64 element: the same bits for any "
+        "grid (`max_blocks` caps stage 1) and any alignment");
+  m.def("clip_scale", &clip_scale, py::arg("src"), py::arg("total"), py::arg("max_norm"), py::arg("out"),
+        "out = src * min(1, max_norm / (sqrt(total) + 1e-6)) in f32, rounded once; the float64 total is read on the GPU");
+  m.attr("SUMSQ_TILE") = pdcc::kern::kSumsqTile;
+  m.attr("SUMSQ_CHAIN") = pdcc::kern::kSumsqChain;
   m.def("ipc_signal_bytes", &pdcc::kern::ipc_signal_bytes);
   m.def("device_links", &device_links,
         "peer links between every pair of visible GPUs: link type (xgmi/pcie), hops, p2p, atomics, perf_rank");

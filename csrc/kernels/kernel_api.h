@@ -412,5 +412,25 @@ hipError_t mx_dequantize_list(const void* wire, size_t cb, size_t nchunks, const
                               hipStream_t stream, MxFormat fmt = MxFormat::FP8_E4M3,
                               const uint32_t* rot_signs = nullptr);
 
+// ---------------------------------------------------------------- gradient clipping (grad_clip.hip)
+// Contract: docs/collectives.md "Gradient clipping". Single-GPU kernels on the caller's stream.
+constexpr int kSumsqTile = 8192;  // elements of a stage-1 tile, counted from the tensor's element 0
+constexpr int kSumsqChain = 38;   // L: the longest chain of f32 roundings from an element to its tile's f64 partial
+inline size_t sumsq_tiles(size_t numel) { return (numel + kSumsqTile - 1) / kSumsqTile; }
+struct SumsqTensor {
+  const void* ptr;  // any alignment of the element size (16-byte aligned: vector loads; same bits either way)
+  size_t numel;     // 0: skipped
+  DType t;          // F32, BF16 or F16
+};
+// out[0] = the sum of the squares of every element of the `k` tensors (k may be 0: +0), the same bits for any
+// `max_blocks` (cap of the stage-1 grid; 0: default). `partials`: scratch of sum(sumsq_tiles(numel)) doubles
+// (at least one), written by one launch per non-empty tensor and folded by one workgroup.
+hipError_t sumsq(const SumsqTensor* ts, size_t k, double* partials, double* out, hipStream_t stream,
+                 int max_blocks = 0);
+// out[i] = round_once((float)src[i] * coef) for i < numel; coef = min(1, max_norm / ((float)sqrt(*total) + 1e-6f)) in
+// f32, NaN kept, read and computed on the device. `ot` is F32 or `st`; out may be src when they are the same dtype.
+hipError_t clip_scale(const void* src, DType st, const double* total, float max_norm, void* out, DType ot,
+                      size_t numel, hipStream_t stream);
+
 }  // namespace kern
 }  // namespace pdcc

@@ -34,6 +34,9 @@
 * :func:`mx_quantize_list`, :func:`mx_dequantize_list`, :func:`mx_list_numel` -- the same wire for a list of
   tensors, read and written where they are, every tensor starting a fresh block (docs/collectives.md
   "Tensor-list layout"); ``all_reduce_compressed`` of a list and ``GradBucketer(in_place=True)``.
+* :func:`sumsq`, :func:`clip_scale` -- gradient clipping by global norm (docs/collectives.md "Gradient
+  clipping"): a deterministic f64 sum of squares of a tensor list, and the cast that multiplies by the clip
+  coefficient it computes on the device from that sum; ``ShardedOptimizer(max_grad_norm=...)``.
 
 Every function runs on the current HIP stream and raises if the native
 extension is missing (no silent eager fallback). ``*_reference`` functions are
@@ -899,7 +902,101 @@ def mx_fold_reference(w: torch.Tensor, /, nsrc: int, numel: int, dtype: torch.dt
     return acc[:numel].to(dtype)
 
 
+# ------------------------------------------ gradient clipping (docs/collectives.md "Gradient clipping")
+CLIP_DTYPES = MX_DTYPES
+SUMSQ_TILE = 8192  # elements of a stage-1 tile (csrc/kernels/kernel_api.h kSumsqTile)
+SUMSQ_CHAIN = 38   # L: f32 roundings between an element and its tile's f64 partial, at most (kSumsqChain)
+
+
+def _clip_check_list(tensors, who: str) -> list:
+    if not isinstance(tensors, (list, tuple)) or not all(isinstance(t, torch.Tensor) for t in tensors):
+        raise TypeError(f"{who}: a list or tuple of tensors expected")
+    if not tensors:
+        raise ValueError(f"{who}: an empty list has no device")
+    for t in tensors:
+        if t.dtype not in CLIP_DTYPES:
+            raise ValueError(f"{who}: float32, bfloat16 or float16 tensors only, got {t.dtype}")
+        if t.device != tensors[0].device:
+            raise ValueError(f"{who}: the tensors share one device, got {tensors[0].device} and {t.device}")
+    return [t.detach() for t in tensors]
+
+
+def _clip_check_total(t, device, who: str, what: str) -> None:
+    if not isinstance(t, torch.Tensor) or t.dtype != torch.float64 or t.numel() != 1 or t.device != device:
+        raise ValueError(f"{who}: {what} must be one float64 element on {device}")
+
+
+def sumsq_reference(tensors: Sequence[torch.Tensor]) -> torch.Tensor:
+    """Plain-PyTorch :func:`sumsq`: the f64 sum of the squares of the values as stored, shape ``[1]``."""
+    xs = _clip_check_list(tensors, "sumsq_reference")
+    total = torch.zeros(1, dtype=torch.float64, device=xs[0].device)
+    for x in xs:
+        total += x.double().square().sum()
+    return total
+
+
+def sumsq(tensors: Sequence[torch.Tensor], out: torch.Tensor | None = None, *, max_blocks: int = 0) -> torch.Tensor:
+    """The sum of the squares of every element of ``tensors`` (f32 / bf16 / f16, mixed freely, empty ones allowed)
+    as one float64 element of shape ``[1]`` on their device, left there: nothing synchronises with the host.
+
+    On the GPU (contiguous tensors, any alignment) two plain launches per call and one more per further tensor:
+    fixed 8192-element tiles counted from each tensor's element 0, a fixed tree inside a tile, one f64 partial per
+    tile, and one workgroup that folds the partials in a fixed order -- so the result is the same bits for any grid
+    (``max_blocks`` caps the tile kernel's) and any base alignment, and within ``(SUMSQ_CHAIN + 1) 2^-24`` of the
+    exact sum, relatively (docs/collectives.md "Gradient clipping"). inf and NaN propagate. CPU tensors:
+    :func:`sumsq_reference`."""
+    xs = _clip_check_list(tensors, "sumsq")
+    if out is not None:
+        _clip_check_total(out, xs[0].device, "sumsq", "out")
+    if xs[0].device.type == "cpu":
+        total = sumsq_reference(xs)
+        return total if out is None else out.copy_(total.view_as(out))
+    if not all(x.is_contiguous() for x in xs):
+        raise ValueError("sumsq: the tensors must be contiguous")
+    return _C().sumsq(xs, out, int(max_blocks))
+
+
+def _clip_check_scale(src, total, max_norm, out, who: str) -> torch.Tensor:
+    if not isinstance(src, torch.Tensor) or src.dtype not in CLIP_DTYPES:
+        raise ValueError(f"{who}: src must be a float32, bfloat16 or float16 tensor")
+    _clip_check_total(total, src.device, who, "total")
+    float(max_norm)
+    if out is None:
+        return torch.empty(src.shape, dtype=torch.float32, device=src.device)
+    if out.dtype not in (torch.float32, src.dtype) or out.numel() != src.numel() or out.device != src.device:
+        raise ValueError(f"{who}: out must hold {src.numel()} float32 or {src.dtype} elements on {src.device}")
+    return out
+
+
+def clip_scale_reference(src: torch.Tensor, total: torch.Tensor, max_norm: float,
+                         out: torch.Tensor | None = None) -> torch.Tensor:
+    """Plain-PyTorch :func:`clip_scale`: the coefficient of ``torch.nn.utils.clip_grad_norm_`` in f32 from the f64
+    ``total``, one f32 product per element, one rounding to ``out``'s dtype."""
+    out = _clip_check_scale(src, total, max_norm, out, "clip_scale_reference")
+    norm = total.detach().reshape(()).sqrt().to(torch.float32)
+    c = torch.tensor(float(max_norm), dtype=torch.float32, device=src.device) / (norm + 1e-6)
+    coef = torch.clamp(c, max=1.0)  # (a NaN stays a NaN)
+    return out.copy_((src.detach().to(torch.float32) * coef).view_as(out))
+
+
+def clip_scale(src: torch.Tensor, total: torch.Tensor, max_norm: float, out: torch.Tensor | None = None) -> torch.Tensor:
+    """``out[i] = round_once(float(src[i]) * coef)`` with ``coef = min(1, max_norm / (float(sqrt(total)) + 1e-6))``
+    evaluated in f32 from the float64 one-element tensor ``total`` (:func:`sumsq`) where it lives: on the GPU the
+    kernel reads it, the host never does. ``out`` is float32 (the default: a new tensor) or of ``src``'s dtype, and
+    may then be ``src`` itself. With ``coef == 1`` the result is bit for bit the plain cast. A NaN total gives NaN
+    everywhere, an infinite one coefficient 0 (finite elements 0, infinite ones NaN) --
+    ``clip_grad_norm_(error_if_nonfinite=False)``. CPU tensors: :func:`clip_scale_reference`."""
+    out = _clip_check_scale(src, total, max_norm, out, "clip_scale")
+    if src.device.type == "cpu":
+        return clip_scale_reference(src, total, max_norm, out)
+    if not (src.is_contiguous() and out.is_contiguous()):
+        raise ValueError("clip_scale: src and out must be contiguous")
+    _C().clip_scale(src.detach(), total.detach(), float(max_norm), out)
+    return out
+
+
 __all__ = ["reduce_nway", "reduce_nway_reference", "multi_copy", "pack", "unpack",
+           "sumsq", "clip_scale", "sumsq_reference", "clip_scale_reference",
            "MX_WIRES", "MX_ROUNDINGS", "MX_ROTATIONS", "mx_sr_key", "mx_rotation_signs",
            "mx_quantize", "mx_reduce", "mx_dequantize", "mx_chunk_blocks", "mx_wire_bytes",
            "mx_owner_residual_numel",

@@ -63,6 +63,15 @@ they quantize it and back afterwards (docs/collectives.md "Hadamard rotation"), 
 narrow wires usable for heavy-tailed gradients. The seed never steps and is not saved: the gradient
 residuals live in the rotated domain of that seed.
 
+``max_grad_norm=c`` clips the reduced gradients by their global 2-norm (docs/collectives.md "Gradient
+clipping"), between the last bucket's wait and the inner optimizer's step -- the one place where it can be
+done: after the reduce-scatter a rank holds only its shard, so ``torch.nn.utils.clip_grad_norm_`` on the model
+would see the local, unreduced gradients. ``ops.sumsq`` of the shards (one read, deterministic), an
+``all_reduce`` of the f64 scalar (every rank folds in rank order: the same bits, so the same coefficient,
+everywhere), and ``ops.clip_scale`` in place of the cast to the master dtype: the coefficient rides on the
+cast bf16 / f16 parameters need anyway, and f32 parameters are scaled in place. The norm never reaches the host;
+``opt.grad_norm`` holds it (before clipping) as a 0-d device tensor.
+
 ``state_dict()`` / ``load_state_dict()`` save and restore this rank's shard
 (sharded checkpoint: every rank writes its own file) and re-gather the
 parameters on load.
@@ -191,7 +200,16 @@ class ShardedOptimizer:
     (each needs its wire; ``rotation_seed`` serves both) rotate every block by a randomized Hadamard matrix before it
     is quantized and back afterwards (docs/collectives.md "Hadamard rotation"); the seed is fixed for the object's
     life, must be the same on every rank and is a constructor argument, not part of :meth:`state_dict` -- a
-    checkpoint with gradient residuals is loaded into an optimizer built with the seed that wrote it. One parameter group: the inner optimizer's hyper-parameters
+    checkpoint with gradient residuals is loaded into an optimizer built with the seed that wrote it.
+    ``max_grad_norm`` (default ``None``: :meth:`step` is what it is without the argument, call for call; else a
+    positive finite float; f32 / bf16 / f16 parameters, ``master_dtype`` float32 or the parameters' own) clips the
+    reduced gradients to that global 2-norm before the inner optimizer sees them, with the coefficient of
+    ``torch.nn.utils.clip_grad_norm_``, ``min(1, max_grad_norm / (norm + 1e-6))`` in f32; ``grad_norm`` is then the
+    norm before clipping, a 0-d float32 tensor on the device (``None`` before the first step), the same bits on every
+    rank. Non-finite norms behave as ``clip_grad_norm_(error_if_nonfinite=False)``: an infinite norm gives
+    coefficient 0 (finite elements become 0, infinite ones NaN), a NaN norm makes every element NaN. On a backend that
+    cannot divide inside the reduction the shard is divided by the world size first, in its own dtype. Nothing of
+    it is part of :meth:`state_dict`. One parameter group: the inner optimizer's hyper-parameters
     come from ``**opt_kwargs``.
     """
 
@@ -200,8 +218,16 @@ class ShardedOptimizer:
                  bucket_bytes: int = 256 << 20, overlap: bool = True, grad_wire: str | None = None,
                  param_wire: str | None = None, grad_error_feedback: bool = False, grad_rounding: str = "nearest",
                  grad_seed: int = 0, grad_rotation: str | None = None, param_rotation: str | None = None,
-                 rotation_seed: int = 0, **opt_kwargs):
+                 rotation_seed: int = 0, max_grad_norm: float | None = None, **opt_kwargs):
         from .compressed import ROUNDINGS, WIRES, _rotation_args
+
+        if max_grad_norm is not None:
+            if isinstance(max_grad_norm, bool) or not isinstance(max_grad_norm, (int, float)) \
+                    or not 0 < max_grad_norm < float("inf"):
+                raise ValueError(f"ShardedOptimizer: max_grad_norm must be a positive finite number or None, "
+                                 f"got {max_grad_norm!r}")
+            max_grad_norm = float(max_grad_norm)
+        self.max_grad_norm, self.grad_norm = max_grad_norm, None
 
         self._grad_rot = _rotation_args("ShardedOptimizer", grad_rotation, rotation_seed)
         self._param_rot = _rotation_args("ShardedOptimizer", param_rotation, rotation_seed)
@@ -253,6 +279,18 @@ class ShardedOptimizer:
         for s in self.spaces:  # the error-feedback residual of the space's flat gradient, or None
             s.grad_residual = (torch.zeros(s.padded, dtype=torch.float32, device=s.device)
                                if self.grad_error_feedback and self._on_wire(s, grad_wire) else None)
+        if max_grad_norm is not None:
+            from .. import ops
+
+            for s in self.spaces:
+                if s.dtype not in ops.CLIP_DTYPES:
+                    raise ValueError(f"ShardedOptimizer: max_grad_norm clips float32, bfloat16 and float16 parameters, "
+                                     f"got {s.dtype}")
+                if s.master.dtype not in (torch.float32, s.dtype):
+                    raise ValueError(f"ShardedOptimizer: with max_grad_norm the master_dtype is float32 or the "
+                                     f"parameters' own ({s.dtype}), got {s.master.dtype}")
+                # the master gradient: the shard itself, scaled in place, or an f32 buffer the scaled cast fills
+                s.master_grad = s.grad_shard if s.master.dtype == s.dtype else torch.empty_like(s.master)
         self.inner = optimizer_cls([s.master for s in self.spaces], **opt_kwargs)
         self._avg = self._fused_avg()
         self._op = dist.ReduceOp.AVG if self._avg else dist.ReduceOp.SUM
@@ -353,13 +391,33 @@ class ShardedOptimizer:
                 b.work.wait()
                 b.work = None
                 b.pending = len(b.idx)
+            if self.max_grad_norm is not None:  # (_clip below sets every master gradient)
+                if not self._avg and self.world > 1 and not self._on_wire(s, self.grad_wire):
+                    s.grad_shard.div_(self.world)
+                continue
             g = s.grad_shard if s.master.dtype == s.dtype else s.grad_shard.to(s.master.dtype)
             if not self._avg and self.world > 1 and not self._on_wire(s, self.grad_wire):  # (a wire divides inside)
                 g = g / self.world
             s.master.grad = g
+        if self.max_grad_norm is not None:
+            self._clip()
         self.grad_rounding_step += 1
         self.inner.step()
         self._gather()
+
+    def _clip(self) -> None:
+        """Clip by global norm (docs/collectives.md "Gradient clipping"): the f64 sum of squares of this rank's
+        shards (their padding is zeros), summed over the ranks, then per space the cast to the master dtype with
+        the coefficient on it. Everything stays on the device."""
+        from .. import ops
+
+        total = ops.sumsq([s.grad_shard for s in self.spaces])
+        self._fence(self.spaces[0])
+        dist.all_reduce(total, op=dist.ReduceOp.SUM, group=self.group)
+        for s in self.spaces:
+            ops.clip_scale(s.grad_shard, total, self.max_grad_norm, out=s.master_grad)
+            s.master.grad = s.master_grad
+        self.grad_norm = total[0].sqrt().to(torch.float32)
 
     @torch.no_grad()
     def _gather(self) -> None:
