@@ -123,19 +123,6 @@ float* mx_residual(const c10::optional<at::Tensor>& r, int64_t numel, const at::
   TORCH_CHECK_VALUE(al16(r->data_ptr()), who, ": the residual must be 16-byte aligned");
   return r->data_ptr<float>();
 }
-// Stochastic rounding (docs/collectives.md "Stochastic rounding"): `sr` selects the kernels that round by the
-// words of (seed, stream, element index); with a residual it is refused (the two are alternatives).
-void mx_check_sr(bool sr, bool residual, int64_t stream, const char* who) {
-  TORCH_CHECK_VALUE(!(sr && residual), who, ": stochastic rounding and a residual are alternatives");
-  TORCH_CHECK_VALUE(stream >= 0 && stream <= 0xffffffffll, who, ": stream must be in [0, 2^32)");
-}
-// Hadamard rotation (docs/collectives.md "Hadamard rotation"): the sign word of `seed`, or none
-struct MxRot {
-  uint32_t signs = 0;
-  bool on = false;
-  MxRot(bool rot, uint64_t seed) : signs(rot ? pdcc::kern::mx_rot_signs(seed) : 0u), on(rot) {}
-  const uint32_t* ptr() const { return on ? &signs : nullptr; }
-};
 using pdcc::kern::MxFormat;
 MxFormat mx_format(const std::string& wire, const char* who) {
   if (wire == "mxfp8_e4m3") return MxFormat::FP8_E4M3;
@@ -144,33 +131,60 @@ MxFormat mx_format(const std::string& wire, const char* who) {
   TORCH_CHECK_VALUE(false, who, ": unknown wire format '", wire, "' (supported: mxfp8_e4m3, mxfp4_e2m1, mxfp6_e2m3)");
   return MxFormat::FP8_E4M3;
 }
+// One binding's call: its name for the messages, the native options (kern::MxOpts) from the Python-side
+// arguments, and the steps every binding takes around its one native call. `opts` points into the object.
+//  * `wire`: the format's name.
+//  * `rot`: Hadamard rotation (docs/collectives.md "Hadamard rotation") with the sign word of `rot_seed`.
+//  * `sr`: stochastic rounding (docs/collectives.md "Stochastic rounding") by the words of (seed, stream,
+//    index_offset + element index); with a residual it is refused (the two are alternatives).
+struct MxCall {
+  const char* who;
+  pdcc::kern::MxOpts opts;
+  pdcc::kern::MxSr sr_words;
+  uint32_t signs;
+  MxCall(const char* who, const std::string& wire, bool rot, uint64_t rot_seed, bool sr = false, bool residual = false,
+         uint64_t seed = 0, int64_t stream = 0, uint64_t index_offset = 0)
+      : who(who), sr_words{seed, (uint32_t)stream, index_offset}, signs(rot ? pdcc::kern::mx_rot_signs(rot_seed) : 0u) {
+    opts.fmt = mx_format(wire, who);
+    TORCH_CHECK_VALUE(!(sr && residual), who, ": stochastic rounding and a residual are alternatives");
+    TORCH_CHECK_VALUE(stream >= 0 && stream <= 0xffffffffll, who, ": stream must be in [0, 2^32)");
+    if (rot) opts.rot_signs = &signs;
+    if (sr) opts.sr = &sr_words;
+  }
+  MxCall(const MxCall&) = delete;
+  MxFormat fmt() const { return opts.fmt; }
+  // the residual of `numel` elements for data on `dev`, checked
+  void residual(const c10::optional<at::Tensor>& r, int64_t numel, const at::Device& dev) {
+    opts.residual = mx_residual(r, numel, dev, who);
+  }
+  // a wire tensor: the caller's `out` or a fresh one, `bytes` bytes on `dev`, checked
+  at::Tensor out(const c10::optional<at::Tensor>& out, int64_t bytes, const at::TensorOptions& like) const {
+    at::Tensor wire = out ? *out : at::empty({bytes}, like.dtype(at::kByte));
+    mx_check_wire(wire, who);
+    TORCH_CHECK(wire.device() == like.device() && wire.numel() == bytes, who, ": out must hold ", bytes, " bytes on ",
+                like.device());
+    return wire;
+  }
+  hipStream_t stream(const at::Device& dev) const {
+    return c10::hip::getCurrentHIPStreamMasqueradingAsCUDA(dev.index()).stream();
+  }
+  void launched(hipError_t e) const { TORCH_CHECK(e == hipSuccess, who, " launch failed: ", hipGetErrorString(e)); }
+};
 
 at::Tensor mx_quantize(const at::Tensor& x, int world, const c10::optional<at::Tensor>& out, const std::string& fmt,
                        const c10::optional<at::Tensor>& residual, bool sr, uint64_t seed, int64_t sr_stream,
                        uint64_t index_offset, bool rot, uint64_t rot_seed) {
-  const MxFormat f = mx_format(fmt, "mx_quantize");
-  const MxRot rt(rot, rot_seed);
-  mx_check_sr(sr, residual.has_value(), sr_stream, "mx_quantize");
+  MxCall c("mx_quantize", fmt, rot, rot_seed, sr, residual.has_value(), seed, sr_stream, index_offset);
   TORCH_CHECK(x.is_cuda(), "mx_quantize: GPU tensors only");
   TORCH_CHECK(world >= 1, "mx_quantize: world must be >= 1");
-  const auto d = mx_dtype(x, "mx_quantize");
+  const auto d = mx_dtype(x, c.who);
   const size_t numel = (size_t)x.numel();
-  const size_t cb = pdcc::kern::mx_chunk_blocks(f, numel, world);
-  const int64_t bytes = (int64_t)pdcc::kern::mx_wire_bytes(f, cb, (size_t)world);
-  float* res = mx_residual(residual, x.numel(), x.device(), "mx_quantize");
+  const size_t cb = pdcc::kern::mx_chunk_blocks(c.fmt(), numel, world);
+  c.residual(residual, x.numel(), x.device());
   c10::hip::HIPGuardMasqueradingAsCUDA g(x.device());
-  at::Tensor wire = out ? *out : at::empty({bytes}, x.options().dtype(at::kByte));
-  mx_check_wire(wire, "mx_quantize");
-  TORCH_CHECK(wire.device() == x.device() && wire.numel() == bytes, "mx_quantize: out must hold ", bytes, " bytes on ",
-              x.device());
+  at::Tensor wire = c.out(out, (int64_t)pdcc::kern::mx_wire_bytes(c.fmt(), cb, (size_t)world), x.options());
   at::Tensor src = mx_in(x), w = mx_out(wire);
-  hipStream_t s = c10::hip::getCurrentHIPStreamMasqueradingAsCUDA(x.device().index()).stream();
-  hipError_t e = sr    ? pdcc::kern::mx_quantize_sr(src.data_ptr(), numel, d, w.data_ptr(), cb, (size_t)world, seed,
-                                                    (uint32_t)sr_stream, index_offset, s, f, rt.ptr())
-                 : res ? pdcc::kern::mx_quantize_ef(src.data_ptr(), numel, d, res, w.data_ptr(), cb, (size_t)world, s, f,
-                                                    rt.ptr())
-                       : pdcc::kern::mx_quantize(src.data_ptr(), numel, d, w.data_ptr(), cb, (size_t)world, s, f, rt.ptr());
-  TORCH_CHECK(e == hipSuccess, "mx_quantize launch failed: ", hipGetErrorString(e));
+  c.launched(pdcc::kern::mx_quantize(src.data_ptr(), numel, d, w.data_ptr(), cb, (size_t)world, c.stream(x.device()), c.opts));
   if (!w.is_same(wire)) wire.copy_(w);
   return wire;
 }
@@ -178,8 +192,8 @@ at::Tensor mx_quantize(const at::Tensor& x, int world, const c10::optional<at::T
 at::Tensor mx_reduce(const at::Tensor& wire, int nsrc, const std::string& op, const c10::optional<at::Tensor>& out,
                      const std::string& fmt, const c10::optional<at::Tensor>& residual, bool sr, uint64_t seed,
                      int64_t sr_stream) {
-  const MxFormat f = mx_format(fmt, "mx_reduce");
-  mx_check_sr(sr, residual.has_value(), sr_stream, "mx_reduce");
+  MxCall c("mx_reduce", fmt, false, 0, sr, residual.has_value(), seed, sr_stream);
+  const MxFormat f = c.fmt();
   mx_check_wire(wire, "mx_reduce");
   TORCH_CHECK(nsrc >= 1 && nsrc <= pdcc::kern::kMaxRanks, "mx_reduce: 1..8 sources");
   TORCH_CHECK_VALUE(op == "sum" || op == "avg", "mx_reduce: op must be 'sum' or 'avg', got '", op, "'");
@@ -188,26 +202,19 @@ at::Tensor mx_reduce(const at::Tensor& wire, int nsrc, const std::string& op, co
   TORCH_CHECK(chunk > 0 && chunk * nsrc == wire.numel() && chunk % (bw * 16) == 0, "mx_reduce: ", wire.numel(),
               " bytes are not ", nsrc, " chunk wires (", bw, " bytes per block, blocks in groups of 16)");
   const size_t cb = (size_t)(chunk / bw);
-  float* r = mx_residual(residual, (int64_t)cb * pdcc::kern::kMxBlock, wire.device(), "mx_reduce");
+  c.residual(residual, (int64_t)cb * pdcc::kern::kMxBlock, wire.device());
   c10::hip::HIPGuardMasqueradingAsCUDA g(wire.device());
-  at::Tensor res = out ? *out : at::empty({chunk}, wire.options());
-  mx_check_wire(res, "mx_reduce");
-  TORCH_CHECK(res.device() == wire.device() && res.numel() == chunk, "mx_reduce: out must hold ", chunk, " bytes");
+  at::Tensor res = c.out(out, chunk, wire.options());
   at::Tensor in = mx_in(wire), o = mx_out(res);
-  hipStream_t s = c10::hip::getCurrentHIPStreamMasqueradingAsCUDA(wire.device().index()).stream();
-  hipError_t e = sr  ? pdcc::kern::mx_reduce_sr(in.data_ptr(), nsrc, cb, kop(op), nsrc, o.data_ptr(), seed,
-                                                (uint32_t)sr_stream, s, f)
-                 : r ? pdcc::kern::mx_reduce_ef(in.data_ptr(), nsrc, cb, kop(op), nsrc, r, o.data_ptr(), s, f)
-                     : pdcc::kern::mx_reduce(in.data_ptr(), nsrc, cb, kop(op), nsrc, o.data_ptr(), s, f);
-  TORCH_CHECK(e == hipSuccess, "mx_reduce launch failed: ", hipGetErrorString(e));
+  c.launched(pdcc::kern::mx_reduce(in.data_ptr(), nsrc, cb, kop(op), nsrc, o.data_ptr(), c.stream(wire.device()), c.opts));
   if (!o.is_same(res)) res.copy_(o);
   return res;
 }
 
 void mx_dequantize(const at::Tensor& wire, int world, at::Tensor& out, const std::string& fmt, bool rot,
                    uint64_t rot_seed) {
-  const MxFormat f = mx_format(fmt, "mx_dequantize");
-  const MxRot rt(rot, rot_seed);
+  MxCall c("mx_dequantize", fmt, rot, rot_seed);
+  const MxFormat f = c.fmt();
   mx_check_wire(wire, "mx_dequantize");
   TORCH_CHECK(world >= 1, "mx_dequantize: world must be >= 1");
   TORCH_CHECK(out.is_cuda() && out.device() == wire.device(), "mx_dequantize: out must be on the wire's GPU");
@@ -219,9 +226,7 @@ void mx_dequantize(const at::Tensor& wire, int world, at::Tensor& out, const std
               " bytes, got ", wire.numel());
   c10::hip::HIPGuardMasqueradingAsCUDA g(wire.device());
   at::Tensor w = mx_in(wire), o = mx_out(out);
-  hipStream_t s = c10::hip::getCurrentHIPStreamMasqueradingAsCUDA(wire.device().index()).stream();
-  hipError_t e = pdcc::kern::mx_dequantize(w.data_ptr(), cb, (size_t)world, o.data_ptr(), numel, d, s, f, rt.ptr());
-  TORCH_CHECK(e == hipSuccess, "mx_dequantize launch failed: ", hipGetErrorString(e));
+  c.launched(pdcc::kern::mx_dequantize(w.data_ptr(), cb, (size_t)world, o.data_ptr(), numel, d, c.stream(wire.device()), c.opts));
   if (!o.is_same(out)) out.copy_(o);
 }
 
@@ -247,9 +252,8 @@ at::Tensor mx_quantize_list(const std::vector<at::Tensor>& xs, int world, const 
                             const std::string& fmt, const c10::optional<at::Tensor>& residual, bool sr, uint64_t seed,
                             int64_t sr_stream, bool rot, uint64_t rot_seed) {
   const char* who = "mx_quantize_list";
-  const MxFormat f = mx_format(fmt, who);
-  const MxRot rt(rot, rot_seed);
-  mx_check_sr(sr, residual.has_value(), sr_stream, who);
+  MxCall c(who, fmt, rot, rot_seed, sr, residual.has_value(), seed, sr_stream);
+  const MxFormat f = c.fmt();
   TORCH_CHECK_VALUE(!xs.empty(), who, ": an empty list has no device and no dtype");
   TORCH_CHECK(world >= 1 && world <= 65535, who, ": world must be 1..65535");
   const auto d = mx_dtype(xs[0], who);
@@ -257,18 +261,11 @@ at::Tensor mx_quantize_list(const std::vector<at::Tensor>& xs, int world, const 
   const auto ts = mx_list(xs, dev, xs[0].scalar_type(), who);
   const size_t numel = pdcc::kern::mx_list_numel(ts.data(), ts.size());
   const size_t cb = pdcc::kern::mx_chunk_blocks(f, numel, world);
-  const int64_t bytes = (int64_t)pdcc::kern::mx_wire_bytes(f, cb, (size_t)world);
-  float* res = mx_residual(residual, (int64_t)numel, dev, who);
+  c.residual(residual, (int64_t)numel, dev);
   c10::hip::HIPGuardMasqueradingAsCUDA g(dev);
-  at::Tensor wire = out ? *out : at::empty({bytes}, xs[0].options().dtype(at::kByte));
-  mx_check_wire(wire, who);
-  TORCH_CHECK(wire.device() == dev && wire.numel() == bytes, who, ": out must hold ", bytes, " bytes on ", dev);
+  at::Tensor wire = c.out(out, (int64_t)pdcc::kern::mx_wire_bytes(f, cb, (size_t)world), xs[0].options());
   at::Tensor w = mx_out(wire);
-  hipStream_t s = c10::hip::getCurrentHIPStreamMasqueradingAsCUDA(dev.index()).stream();
-  const pdcc::kern::MxListSr srs{seed, (uint32_t)sr_stream, 0};
-  hipError_t e = pdcc::kern::mx_quantize_list(ts.data(), ts.size(), d, w.data_ptr(), cb, (size_t)world, s, f, rt.ptr(), res,
-                                              sr ? &srs : nullptr);
-  TORCH_CHECK(e == hipSuccess, who, " launch failed: ", hipGetErrorString(e));
+  c.launched(pdcc::kern::mx_quantize_list(ts.data(), ts.size(), d, w.data_ptr(), cb, (size_t)world, c.stream(dev), c.opts));
   if (!w.is_same(wire)) wire.copy_(w);
   return wire;
 }
@@ -276,8 +273,8 @@ at::Tensor mx_quantize_list(const std::vector<at::Tensor>& xs, int world, const 
 void mx_dequantize_list(const at::Tensor& wire, const std::vector<at::Tensor>& outs, int world, const std::string& fmt,
                         bool rot, uint64_t rot_seed) {
   const char* who = "mx_dequantize_list";
-  const MxFormat f = mx_format(fmt, who);
-  const MxRot rt(rot, rot_seed);
+  MxCall c(who, fmt, rot, rot_seed);
+  const MxFormat f = c.fmt();
   mx_check_wire(wire, who);
   TORCH_CHECK(world >= 1 && world <= 65535, who, ": world must be 1..65535");
   if (outs.empty()) return;
@@ -290,18 +287,16 @@ void mx_dequantize_list(const at::Tensor& wire, const std::vector<at::Tensor>& o
               " bytes, got ", wire.numel());
   c10::hip::HIPGuardMasqueradingAsCUDA g(wire.device());
   at::Tensor w = mx_in(wire);
-  hipStream_t s = c10::hip::getCurrentHIPStreamMasqueradingAsCUDA(wire.device().index()).stream();
-  hipError_t e = pdcc::kern::mx_dequantize_list(w.data_ptr(), cb, (size_t)world, ts.data(), ts.size(), d, s, f, rt.ptr());
-  TORCH_CHECK(e == hipSuccess, who, " launch failed: ", hipGetErrorString(e));
+  c.launched(pdcc::kern::mx_dequantize_list(w.data_ptr(), cb, (size_t)world, ts.data(), ts.size(), d, c.stream(wire.device()),
+                                            c.opts));
 }
 
 // ---- the shard layout (kernels/mx_layout.h): chunk r is shard r of `numel / world` elements
 at::Tensor mx_quantize_shards(const at::Tensor& x, int world, const c10::optional<at::Tensor>& out,
                               const std::string& fmt, const c10::optional<at::Tensor>& residual, bool sr, uint64_t seed,
                               int64_t sr_stream, uint64_t index_offset, bool rot, uint64_t rot_seed) {
-  const MxFormat f = mx_format(fmt, "mx_quantize_shards");
-  const MxRot rt(rot, rot_seed);
-  mx_check_sr(sr, residual.has_value(), sr_stream, "mx_quantize_shards");
+  MxCall c("mx_quantize_shards", fmt, rot, rot_seed, sr, residual.has_value(), seed, sr_stream, index_offset);
+  const MxFormat f = c.fmt();
   TORCH_CHECK(x.is_cuda(), "mx_quantize_shards: GPU tensors only");
   TORCH_CHECK(world >= 1 && world <= 65535, "mx_quantize_shards: world must be 1..65535");
   const auto d = mx_dtype(x, "mx_quantize_shards");
@@ -309,30 +304,19 @@ at::Tensor mx_quantize_shards(const at::Tensor& x, int world, const c10::optiona
                     " elements are not ", world, " shards of one or more elements");
   const size_t m = (size_t)x.numel() / (size_t)world;
   const size_t cb = pdcc::kern::mx_shard_blocks(f, m);
-  const int64_t bytes = (int64_t)pdcc::kern::mx_shard_wire_bytes(f, m, (size_t)world);
-  float* res = mx_residual(residual, x.numel(), x.device(), "mx_quantize_shards");
+  c.residual(residual, x.numel(), x.device());
   c10::hip::HIPGuardMasqueradingAsCUDA g(x.device());
-  at::Tensor wire = out ? *out : at::empty({bytes}, x.options().dtype(at::kByte));
-  mx_check_wire(wire, "mx_quantize_shards");
-  TORCH_CHECK(wire.device() == x.device() && wire.numel() == bytes, "mx_quantize_shards: out must hold ", bytes,
-              " bytes on ", x.device());
+  at::Tensor wire = c.out(out, (int64_t)pdcc::kern::mx_shard_wire_bytes(f, m, (size_t)world), x.options());
   at::Tensor src = mx_in(x), w = mx_out(wire);
-  hipStream_t s = c10::hip::getCurrentHIPStreamMasqueradingAsCUDA(x.device().index()).stream();
-  hipError_t e = sr    ? pdcc::kern::mx_quantize_shards_sr(src.data_ptr(), m, d, w.data_ptr(), cb, (size_t)world, seed,
-                                                           (uint32_t)sr_stream, index_offset, s, f, rt.ptr())
-                 : res ? pdcc::kern::mx_quantize_shards_ef(src.data_ptr(), m, d, res, w.data_ptr(), cb, (size_t)world, s, f,
-                                                           rt.ptr())
-                       : pdcc::kern::mx_quantize_shards(src.data_ptr(), m, d, w.data_ptr(), cb, (size_t)world, s, f,
-                                                        rt.ptr());
-  TORCH_CHECK(e == hipSuccess, "mx_quantize_shards launch failed: ", hipGetErrorString(e));
+  c.launched(pdcc::kern::mx_quantize_shards(src.data_ptr(), m, d, w.data_ptr(), cb, (size_t)world, c.stream(x.device()), c.opts));
   if (!w.is_same(wire)) wire.copy_(w);
   return wire;
 }
 
 void mx_dequantize_shards(const at::Tensor& wire, int world, at::Tensor& out, const std::string& fmt, bool rot,
                           uint64_t rot_seed) {
-  const MxFormat f = mx_format(fmt, "mx_dequantize_shards");
-  const MxRot rt(rot, rot_seed);
+  MxCall c("mx_dequantize_shards", fmt, rot, rot_seed);
+  const MxFormat f = c.fmt();
   mx_check_wire(wire, "mx_dequantize_shards");
   TORCH_CHECK(world >= 1 && world <= 65535, "mx_dequantize_shards: world must be 1..65535");
   TORCH_CHECK(out.is_cuda() && out.device() == wire.device(), "mx_dequantize_shards: out must be on the wire's GPU");
@@ -346,16 +330,14 @@ void mx_dequantize_shards(const at::Tensor& wire, int world, at::Tensor& out, co
               " elements has ", bytes, " bytes, got ", wire.numel());
   c10::hip::HIPGuardMasqueradingAsCUDA g(wire.device());
   at::Tensor w = mx_in(wire), o = mx_out(out);
-  hipStream_t s = c10::hip::getCurrentHIPStreamMasqueradingAsCUDA(wire.device().index()).stream();
-  hipError_t e = pdcc::kern::mx_dequantize_shards(w.data_ptr(), cb, (size_t)world, o.data_ptr(), m, d, s, f, rt.ptr());
-  TORCH_CHECK(e == hipSuccess, "mx_dequantize_shards launch failed: ", hipGetErrorString(e));
+  c.launched(pdcc::kern::mx_dequantize_shards(w.data_ptr(), cb, (size_t)world, o.data_ptr(), m, d, c.stream(wire.device()), c.opts));
   if (!o.is_same(out)) out.copy_(o);
 }
 
 void mx_fold(const at::Tensor& wire, int nsrc, const std::string& op, at::Tensor& out, const std::string& fmt, bool rot,
              uint64_t rot_seed) {
-  const MxFormat f = mx_format(fmt, "mx_fold");
-  const MxRot rt(rot, rot_seed);
+  MxCall c("mx_fold", fmt, rot, rot_seed);
+  const MxFormat f = c.fmt();
   mx_check_wire(wire, "mx_fold");
   TORCH_CHECK(nsrc >= 1 && nsrc <= pdcc::kern::kMaxRanks, "mx_fold: 1..8 sources");
   TORCH_CHECK_VALUE(op == "sum" || op == "avg", "mx_fold: op must be 'sum' or 'avg', got '", op, "'");
@@ -369,9 +351,7 @@ void mx_fold(const at::Tensor& wire, int nsrc, const std::string& op, at::Tensor
               " bytes, got ", wire.numel());
   c10::hip::HIPGuardMasqueradingAsCUDA g(wire.device());
   at::Tensor w = mx_in(wire), o = mx_out(out);
-  hipStream_t s = c10::hip::getCurrentHIPStreamMasqueradingAsCUDA(wire.device().index()).stream();
-  hipError_t e = pdcc::kern::mx_fold(w.data_ptr(), nsrc, cb, kop(op), nsrc, o.data_ptr(), numel, d, s, f, rt.ptr());
-  TORCH_CHECK(e == hipSuccess, "mx_fold launch failed: ", hipGetErrorString(e));
+  c.launched(pdcc::kern::mx_fold(w.data_ptr(), nsrc, cb, kop(op), nsrc, o.data_ptr(), numel, d, c.stream(wire.device()), c.opts));
   if (!o.is_same(out)) out.copy_(o);
 }
 

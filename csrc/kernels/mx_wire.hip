@@ -8,16 +8,19 @@
 //   mx_fold        nsrc chunk wires -> f32 / bf16 / f16 tensor (dequantize, fold in f32, round once)
 //   mx_quantize_shards / mx_dequantize_shards: quantize / dequantize with one chunk per shard of m
 //                  elements (the SHARD instantiations of the same two kernels)
-//   mx_quantize_ef / mx_quantize_shards_ef / mx_reduce_ef: the EF instantiations of quantize and
-//                  reduce, which add an f32 residual before they quantize and leave what the
-//                  quantizer dropped in it (docs/collectives.md "Error feedback"); per f32 element
-//                  quantize then reads 8 and writes 4 + 33/32 bytes instead of reading 4
-//   mx_quantize_sr / mx_quantize_shards_sr / mx_reduce_sr: the SR instantiations of quantize and
-//                  reduce, which round the payload stochastically (docs/collectives.md "Stochastic
-//                  rounding", mx_sr.h); they move the bytes of the plain kernels
 //   mx_quantize_list / mx_dequantize_list: the dealt wire of a list of tensors read and written where they
 //                  are, every tensor starting a fresh block (docs/collectives.md "Tensor-list layout"); the
 //                  one pair of kernels that uses LDS, for the table of the tensors' descriptors
+//
+// The options of a call (MxOpts, kernel_api.h) pick the instantiation:
+//   residual       the EF instantiations of the quantizers (quantize, its shard and list forms, reduce), which
+//                  add an f32 residual before they quantize and leave what the quantizer dropped in it
+//                  (docs/collectives.md "Error feedback"); per f32 element quantize then reads 8 and
+//                  writes 4 + 33/32 bytes instead of reading 4
+//   sr             the SR instantiations of the quantizers, which round the payload stochastically
+//                  (docs/collectives.md "Stochastic rounding", mx_sr.h); they move the bytes of the plain kernels
+//   rot_signs      the ROT instantiations of everything that touches the tensor (all but reduce), which
+//                  rotate every block (docs/collectives.md "Hadamard rotation", mx_rot.h)
 //
 // All of them are streaming kernels: a lane moves 16 B on the wide side of its conversion (the tensor
 // for quantize / dequantize / fold, the payload for reduce), the lanes of a block sit next to each other
@@ -47,6 +50,7 @@
 // |s| <= 7.5 and the code is its low five bits and its sign (MxFmt<FP6_E2M3> below). e is clamped to
 // [-123, 126].
 #include <algorithm>
+#include <type_traits>
 
 #include "dev_common.h"
 #include "mx_layout.h"
@@ -158,11 +162,13 @@ struct MxScale {
   float inv;
   bool blank;
 };
-__device__ __forceinline__ MxScale mx_scale(uint32_t amax) {
-  // amax = m 2^k, 1 <= m < 2 (k = -127 for a subnormal: the clamp decides); the smallest e with
-  // amax 2^-e <= 448 = 1.75 2^8 is k - 8 for m <= 1.75 and k - 7 above
-  int e = (int)(amax >> 23) - 127 - 8 + ((amax & 0x7fffffu) > 0x600000u ? 1 : 0);
-  e = e < -117 ? -117 : (e > 120 ? 120 : e);
+// amax = m 2^k, 1 <= m < 2 (k = -127 for a subnormal: the clamp decides). With the format's largest
+// magnitude (1 + SWITCH 2^-23) 2^BIAS, the smallest e with amax 2^-e <= that is k - BIAS for a mantissa
+// field <= SWITCH and one more above; e is clamped to [EMIN, EMAX] (the four constants: MxFmt below).
+template <int BIAS, uint32_t SWITCH, int EMIN, int EMAX>
+__device__ __forceinline__ MxScale mx_scale_of(uint32_t amax) {
+  int e = (int)(amax >> 23) - 127 - BIAS + ((amax & 0x7fffffu) > SWITCH ? 1 : 0);
+  e = e < EMIN ? EMIN : (e > EMAX ? EMAX : e);
   const bool special = amax >= 0x7f800000u;
   if (amax == 0) e = 0;
   MxScale r;
@@ -201,33 +207,6 @@ __device__ __forceinline__ void fp4_widen8(uint32_t w, float scale, float* f) {
   const f32x2 d = __builtin_amdgcn_cvt_scalef32_pk_f32_fp4(w, 1.0f, 3);
   f[0] = a[0] * scale; f[1] = a[1] * scale; f[2] = b[0] * scale; f[3] = b[1] * scale;
   f[4] = c[0] * scale; f[5] = c[1] * scale; f[6] = d[0] * scale; f[7] = d[1] * scale;
-}
-__device__ __forceinline__ MxScale mx4_scale(uint32_t amax) {
-  // the smallest e with amax 2^-e <= 6 = 1.5 2^2 is k - 2 for m <= 1.5 and k - 1 above; the lower
-  // clamp keeps 0.5 2^e a normal f32, the upper one is never reached (k <= 127)
-  int e = (int)(amax >> 23) - 127 - 2 + ((amax & 0x7fffffu) > 0x400000u ? 1 : 0);
-  e = e < -125 ? -125 : (e > 126 ? 126 : e);
-  const bool special = amax >= 0x7f800000u;
-  if (amax == 0) e = 0;
-  MxScale r;
-  r.byte = special ? 255u : (uint32_t)(e + 127);
-  r.inv = __uint_as_float((uint32_t)(127 - e) << 23);
-  r.blank = special || amax == 0;
-  return r;
-}
-
-__device__ __forceinline__ MxScale mx6_scale(uint32_t amax) {
-  // the smallest e with amax 2^-e <= 7.5 = 1.875 2^2 is k - 2 for m <= 1.875 and k - 1 above; the lower
-  // clamp keeps 0.125 2^e a normal f32, the upper one is never reached (k <= 127)
-  int e = (int)(amax >> 23) - 127 - 2 + ((amax & 0x7fffffu) > 0x700000u ? 1 : 0);
-  e = e < -123 ? -123 : (e > 126 ? 126 : e);
-  const bool special = amax >= 0x7f800000u;
-  if (amax == 0) e = 0;
-  MxScale r;
-  r.byte = special ? 255u : (uint32_t)(e + 127);
-  r.inv = __uint_as_float((uint32_t)(127 - e) << 23);
-  r.blank = special || amax == 0;
-  return r;
 }
 // e2m3 through the FP8 converts. Four scaled values s / 64 -> four e4m3 bytes -> 24 bits of codes (element
 // j in bits 6j .. 6j + 5), and back: 24 bits -> four e4m3 bytes -> four values of s / 64.
@@ -269,7 +248,8 @@ template <> struct MxFmt<MxFormat::FP8_E4M3> {
   static constexpr int kPayload = 32;
   static constexpr bool kLanes = false;
   template <int N> static constexpr int kWords = N / 4;
-  __device__ static __forceinline__ MxScale scale(uint32_t amax) { return mx_scale(amax); }
+  // the largest magnitude is 448 = 1.75 2^8: e = k - 8 for m <= 1.75 and k - 7 above
+  __device__ static __forceinline__ MxScale scale(uint32_t amax) { return mx_scale_of<8, 0x600000u, -117, 120>(amax); }
   template <int N> __device__ static __forceinline__ void pack(const float* f, const MxScale& sc, uint32_t* q) {
 #pragma unroll
     for (int d = 0; d < N / 4; ++d) {
@@ -298,7 +278,9 @@ template <> struct MxFmt<MxFormat::FP4_E2M1> {
   static constexpr int kPayload = 16;
   static constexpr bool kLanes = false;
   template <int N> static constexpr int kWords = (N + 7) / 8;
-  __device__ static __forceinline__ MxScale scale(uint32_t amax) { return mx4_scale(amax); }
+  // the largest magnitude is 6 = 1.5 2^2: e = k - 2 for m <= 1.5 and k - 1 above; the lower clamp keeps
+  // 0.5 2^e a normal f32, the upper one is never reached (k <= 127)
+  __device__ static __forceinline__ MxScale scale(uint32_t amax) { return mx_scale_of<2, 0x400000u, -125, 126>(amax); }
   template <int N> __device__ static __forceinline__ void pack(const float* f, const MxScale& sc, uint32_t* q) {
 #pragma unroll
     for (int d = 0; d < (N + 7) / 8; ++d) {
@@ -342,7 +324,9 @@ template <> struct MxFmt<MxFormat::FP6_E2M3> {
   static constexpr int kPayload = 24;
   static constexpr bool kLanes = true;
   template <int N> static constexpr int kWords = (6 * N + 31) / 32;  // 4: 24 bits, 8: 48, 16: 96, 32: 192
-  __device__ static __forceinline__ MxScale scale(uint32_t amax) { return mx6_scale(amax); }
+  // the largest magnitude is 7.5 = 1.875 2^2: e = k - 2 for m <= 1.875 and k - 1 above; the lower clamp
+  // keeps 0.125 2^e a normal f32, the upper one is never reached (k <= 127)
+  __device__ static __forceinline__ MxScale scale(uint32_t amax) { return mx_scale_of<2, 0x700000u, -123, 126>(amax); }
   template <int N> __device__ static __forceinline__ void pack(const float* f, const MxScale& sc, uint32_t* q) {
     // 2^-(e + 6) from the scale byte e + 127: a subnormal for e > 120, where every |x| that does not round
     // to 0 still has a normal, exact product
@@ -1103,218 +1087,162 @@ inline uint32_t mx_grid_x(uint64_t nvec, int per, size_t rows, uint64_t most) {
 namespace kern {
 
 namespace {
-bool mx_al16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
-// cb: a multiple of 16, and a chunk's lanes are counted in 32 bits
-bool mx_cb_ok(size_t cb) { return cb > 0 && cb % kMxScaleAlign == 0 && cb <= (size_t(1) << 27); }
-bool mx_fmt_ok(MxFormat f) { return f == MxFormat::FP8_E4M3 || f == MxFormat::FP4_E2M1 || f == MxFormat::FP6_E2M3; }
+bool mx_al16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }  // (null counts as aligned)
+// What every launch checks: the format is one of the three; cb is a multiple of 16, and a chunk's lanes are
+// counted in 32 bits; a quantizer takes a residual or stochastic rounding, not both, and the other kernels
+// neither; the residual and the buffers `a` and `b` are 16-byte aligned.
+bool mx_args_ok(const MxOpts& o, bool quantizer, size_t cb, const void* a, const void* b) {
+  const bool fmt = o.fmt == MxFormat::FP8_E4M3 || o.fmt == MxFormat::FP4_E2M1 || o.fmt == MxFormat::FP6_E2M3;
+  const bool opts = quantizer ? !(o.residual && o.sr) : !o.residual && !o.sr;
+  return fmt && opts && cb > 0 && cb % kMxScaleAlign == 0 && cb <= (size_t(1) << 27) && mx_al16(o.residual) &&
+         mx_al16(a) && mx_al16(b);
+}
 size_t mx_esize(DType t) { return t == DType::F32 ? 4 : 2; }
 bool mx_dtype_ok(DType t) { return t == DType::F32 || t == DType::BF16 || t == DType::F16; }
-// the shard arguments: m elements per shard fit the chunk, and the whole tensor's size is a size_t
-bool mx_shards_ok(size_t m, size_t cb, size_t nchunks) {
-  return mx_cb_ok(cb) && m > 0 && m <= cb * kMxBlock && nchunks > 0 && nchunks <= 65535;
+bool mx_chunks_ok(size_t nchunks) { return nchunks > 0 && nchunks <= 65535; }  // (a chunk is a grid row)
+// the shard arguments (after mx_args_ok): m elements per shard fit the chunk, and the whole tensor's size is a size_t
+bool mx_shards_ok(size_t m, size_t cb, size_t nchunks) { return m > 0 && m <= cb * kMxBlock && mx_chunks_ok(nchunks); }
+// the sources and the op of reduce and fold
+bool mx_fold_ok(int nsrc, RedOp op, int avg_div) {
+  return nsrc >= 1 && nsrc <= kMaxRanks && (op == RedOp::SUM || (op == RedOp::AVG && avg_div >= 1));
 }
+// the word indices index_offset .. index_offset + numel of a stochastic call fit 64 bits
+bool mx_sr_fits(const MxOpts& o, size_t numel) { return !o.sr || o.sr->index_offset + numel >= o.sr->index_offset; }
 dim3 mx_stream_grid(size_t cb, DType t, size_t nchunks) {
   const int lpb = t == DType::F32 ? 8 : 4;
   return dim3(dev::mx_grid_x((uint64_t)cb * lpb, dev::kMxUnroll, nchunks, dev::kMxGridStream), (uint32_t)nchunks);
 }
-
-// key and index base of a stochastic call (mx_sr.h); null: round to nearest
-struct MxSr {
+// key and index base of a stochastic call (mx_sr.h); zeros without one
+struct MxSrKey {
   uint32_t key;
   uint64_t base;
 };
-// quantize / dequantize of one format and dtype: the dealt kernel, or the shard one with or without vectors
-template <MxFormat F, DType DT, bool EF, bool SR, bool ROT>
-void mx_quantize_ef_go(bool shard, bool vec, const dim3& grid, const char* s, size_t numel, char* w, uint32_t cb,
-                       size_t m, float* res, uint32_t key, uint64_t base, uint32_t signs, hipStream_t stream) {
-  if (!shard) hipLaunchKernelGGL((dev::k_mx_quantize<F, DT, false, true, EF, SR, ROT>), grid, dim3(256), 0, stream, s, numel, w, cb, m, res, key, base, signs);
-  else if (vec) hipLaunchKernelGGL((dev::k_mx_quantize<F, DT, true, true, EF, SR, ROT>), grid, dim3(256), 0, stream, s, numel, w, cb, m, res, key, base, signs);
-  else hipLaunchKernelGGL((dev::k_mx_quantize<F, DT, true, false, EF, SR, ROT>), grid, dim3(256), 0, stream, s, numel, w, cb, m, res, key, base, signs);
+MxSrKey mx_sr_key_of(const MxOpts& o) {
+  return o.sr ? MxSrKey{mx_sr_key(o.sr->seed, o.sr->stream), o.sr->index_offset} : MxSrKey{0u, 0u};
 }
-// (`sr`: the stochastic kernels; else `res` null: the plain kernels; otherwise the error-feedback ones)
-template <MxFormat F, DType DT, bool ROT>
-void mx_quantize_rot_go(bool shard, bool vec, const dim3& grid, const char* s, size_t numel, char* w, uint32_t cb, size_t m,
-                        float* res, const MxSr* sr, uint32_t signs, hipStream_t stream) {
-  if (sr) mx_quantize_ef_go<F, DT, false, true, ROT>(shard, vec, grid, s, numel, w, cb, m, nullptr, sr->key, sr->base, signs, stream);
-  else if (res) mx_quantize_ef_go<F, DT, true, false, ROT>(shard, vec, grid, s, numel, w, cb, m, res, 0u, 0u, signs, stream);
-  else mx_quantize_ef_go<F, DT, false, false, ROT>(shard, vec, grid, s, numel, w, cb, m, res, 0u, 0u, signs, stream);
-}
-// (`rot`: the sign word of the rotated kernels; null: the kernels without the rotation)
-template <MxFormat F, DType DT>
-void mx_quantize_go(bool shard, bool vec, const dim3& grid, const char* s, size_t numel, char* w, uint32_t cb, size_t m,
-                    float* res, const MxSr* sr, const uint32_t* rot, hipStream_t stream) {
-  if (rot) mx_quantize_rot_go<F, DT, true>(shard, vec, grid, s, numel, w, cb, m, res, sr, *rot, stream);
-  else mx_quantize_rot_go<F, DT, false>(shard, vec, grid, s, numel, w, cb, m, res, sr, 0u, stream);
-}
-template <MxFormat F, DType DT, bool ROT>
-void mx_dequantize_rot_go(bool shard, bool vec, const dim3& grid, const char* w, uint32_t cb, char* d, size_t numel, size_t m,
-                          uint32_t signs, hipStream_t stream) {
-  if (!shard) hipLaunchKernelGGL((dev::k_mx_dequantize<F, DT, false, true, ROT>), grid, dim3(256), 0, stream, w, cb, d, numel, m, signs);
-  else if (vec) hipLaunchKernelGGL((dev::k_mx_dequantize<F, DT, true, true, ROT>), grid, dim3(256), 0, stream, w, cb, d, numel, m, signs);
-  else hipLaunchKernelGGL((dev::k_mx_dequantize<F, DT, true, false, ROT>), grid, dim3(256), 0, stream, w, cb, d, numel, m, signs);
-}
-template <MxFormat F, DType DT>
-void mx_dequantize_go(bool shard, bool vec, const dim3& grid, const char* w, uint32_t cb, char* d, size_t numel, size_t m,
-                      const uint32_t* rot, hipStream_t stream) {
-  if (rot) mx_dequantize_rot_go<F, DT, true>(shard, vec, grid, w, cb, d, numel, m, *rot, stream);
-  else mx_dequantize_rot_go<F, DT, false>(shard, vec, grid, w, cb, d, numel, m, 0u, stream);
-}
-template <MxFormat F, class... A>
-void mx_quantize_dt(DType t, A... a) {
-  switch (t) {
-    case DType::F32: mx_quantize_go<F, DType::F32>(a...); break;
-    case DType::BF16: mx_quantize_go<F, DType::BF16>(a...); break;
-    default: mx_quantize_go<F, DType::F16>(a...); break;
+
+// ---- from a runtime value to a template argument: each helper calls the generic `fn` with the value as a tag (an
+// integral_constant; PDCC_V reads it back), so a launch function below is nested lifts around one launch.
+// The callers have checked the values: what is not listed cannot arrive.
+template <auto V>
+using MxTag = std::integral_constant<decltype(V), V>;
+#define PDCC_V(tag) decltype(tag)::value
+template <class Fn>
+void mx_lift_fmt(MxFormat f, Fn&& fn) {
+  switch (f) {
+    case MxFormat::FP4_E2M1: return fn(MxTag<MxFormat::FP4_E2M1>{});
+    case MxFormat::FP6_E2M3: return fn(MxTag<MxFormat::FP6_E2M3>{});
+    default: return fn(MxTag<MxFormat::FP8_E4M3>{});
   }
 }
-template <MxFormat F, class... A>
-void mx_dequantize_dt(DType t, A... a) {
+template <class Fn>
+void mx_lift_dtype(DType t, Fn&& fn) {
   switch (t) {
-    case DType::F32: mx_dequantize_go<F, DType::F32>(a...); break;
-    case DType::BF16: mx_dequantize_go<F, DType::BF16>(a...); break;
-    default: mx_dequantize_go<F, DType::F16>(a...); break;
+    case DType::F32: return fn(MxTag<DType::F32>{});
+    case DType::BF16: return fn(MxTag<DType::BF16>{});
+    default: return fn(MxTag<DType::F16>{});
   }
 }
-hipError_t mx_quantize_any(MxFormat fmt, DType t, bool shard, bool vec, const void* src, size_t numel, void* wire,
-                           size_t cb, size_t nchunks, size_t m, hipStream_t stream, const uint32_t* rot,
-                           float* res = nullptr, const MxSr* sr = nullptr) {
+template <class Fn>
+void mx_lift_bool(bool b, Fn&& fn) {
+  if (b) fn(MxTag<true>{});
+  else fn(MxTag<false>{});
+}
+template <class Fn>
+void mx_lift_nsrc(int nsrc, Fn&& fn) {
+  switch (nsrc) {
+    case 1: return fn(MxTag<1>{});
+    case 2: return fn(MxTag<2>{});
+    case 3: return fn(MxTag<3>{});
+    case 4: return fn(MxTag<4>{});
+    case 5: return fn(MxTag<5>{});
+    case 6: return fn(MxTag<6>{});
+    case 7: return fn(MxTag<7>{});
+    default: return fn(MxTag<8>{});
+  }
+}
+// what a quantizer does besides rounding to nearest: nothing, error feedback (a residual) or stochastic
+// rounding -- one tag of three values, because the kernels have no instantiation with both
+enum class MxMode { PLAIN, EF, SR };
+template <class Fn>
+void mx_lift_mode(const MxOpts& o, Fn&& fn) {
+  if (o.sr) fn(MxTag<MxMode::SR>{});
+  else if (o.residual) fn(MxTag<MxMode::EF>{});
+  else fn(MxTag<MxMode::PLAIN>{});
+}
+// the dealt kernel, or the shard one with or without vectors (there is no dealt kernel without them): 16-byte
+// vectors when every shard, and its slice of a residual, starts 16-byte aligned
+enum class MxLayout { DEALT, SHARD_VEC, SHARD_SCALAR };
+MxLayout mx_shard_layout(size_t m, DType t) {
+  return m * mx_esize(t) % 16 == 0 ? MxLayout::SHARD_VEC : MxLayout::SHARD_SCALAR;
+}
+template <class Fn>
+void mx_lift_layout(MxLayout l, Fn&& fn) {
+  switch (l) {
+    case MxLayout::DEALT: return fn(MxTag<MxLayout::DEALT>{});
+    case MxLayout::SHARD_VEC: return fn(MxTag<MxLayout::SHARD_VEC>{});
+    default: return fn(MxTag<MxLayout::SHARD_SCALAR>{});
+  }
+}
+
+// ---- one launch function per kernel family
+// quantize / dequantize of `numel` elements in all: dealt, or shards of `m` elements (the dealt kernels ignore m)
+hipError_t mx_quantize_launch(MxLayout layout, const void* src, size_t numel, size_t m, DType t, void* wire, size_t cb,
+                              size_t nchunks, hipStream_t stream, const MxOpts& o) {
   const dim3 grid = mx_stream_grid(cb, t, nchunks);
   const char* s = static_cast<const char*>(src);
   char* w = static_cast<char*>(wire);
-  if (fmt == MxFormat::FP4_E2M1) mx_quantize_dt<MxFormat::FP4_E2M1>(t, shard, vec, grid, s, numel, w, (uint32_t)cb, m, res, sr, rot, stream);
-  else if (fmt == MxFormat::FP6_E2M3) mx_quantize_dt<MxFormat::FP6_E2M3>(t, shard, vec, grid, s, numel, w, (uint32_t)cb, m, res, sr, rot, stream);
-  else mx_quantize_dt<MxFormat::FP8_E4M3>(t, shard, vec, grid, s, numel, w, (uint32_t)cb, m, res, sr, rot, stream);
+  const MxSrKey sr = mx_sr_key_of(o);
+  const uint32_t c = (uint32_t)cb, signs = o.rot_signs ? *o.rot_signs : 0u;
+  mx_lift_fmt(o.fmt, [&](auto f) {
+    mx_lift_dtype(t, [&](auto dt) {
+      mx_lift_layout(layout, [&](auto l) {
+        mx_lift_mode(o, [&](auto mode) {
+          mx_lift_bool(o.rot_signs != nullptr, [&](auto rot) {
+            constexpr bool shard = PDCC_V(l) != MxLayout::DEALT, vec = PDCC_V(l) != MxLayout::SHARD_SCALAR;
+            constexpr bool ef = PDCC_V(mode) == MxMode::EF, st = PDCC_V(mode) == MxMode::SR;
+            hipLaunchKernelGGL((dev::k_mx_quantize<PDCC_V(f), PDCC_V(dt), shard, vec, ef, st, PDCC_V(rot)>), grid, dim3(256),
+                               0, stream, s, numel, w, c, m, o.residual, sr.key, sr.base, signs);
+          });
+        });
+      });
+    });
+  });
   return hipGetLastError();
 }
-hipError_t mx_dequantize_any(MxFormat fmt, DType t, bool shard, bool vec, const void* wire, size_t cb, size_t nchunks,
-                             void* dst, size_t numel, size_t m, hipStream_t stream, const uint32_t* rot) {
+hipError_t mx_dequantize_launch(MxLayout layout, const void* wire, size_t cb, size_t nchunks, void* dst, size_t numel,
+                                size_t m, DType t, hipStream_t stream, const MxOpts& o) {
   const dim3 grid = mx_stream_grid(cb, t, nchunks);
   const char* w = static_cast<const char*>(wire);
   char* d = static_cast<char*>(dst);
-  if (fmt == MxFormat::FP4_E2M1) mx_dequantize_dt<MxFormat::FP4_E2M1>(t, shard, vec, grid, w, (uint32_t)cb, d, numel, m, rot, stream);
-  else if (fmt == MxFormat::FP6_E2M3) mx_dequantize_dt<MxFormat::FP6_E2M3>(t, shard, vec, grid, w, (uint32_t)cb, d, numel, m, rot, stream);
-  else mx_dequantize_dt<MxFormat::FP8_E4M3>(t, shard, vec, grid, w, (uint32_t)cb, d, numel, m, rot, stream);
+  const uint32_t c = (uint32_t)cb, signs = o.rot_signs ? *o.rot_signs : 0u;
+  mx_lift_fmt(o.fmt, [&](auto f) {
+    mx_lift_dtype(t, [&](auto dt) {
+      mx_lift_layout(layout, [&](auto l) {
+        mx_lift_bool(o.rot_signs != nullptr, [&](auto rot) {
+          constexpr bool shard = PDCC_V(l) != MxLayout::DEALT, vec = PDCC_V(l) != MxLayout::SHARD_SCALAR;
+          hipLaunchKernelGGL((dev::k_mx_dequantize<PDCC_V(f), PDCC_V(dt), shard, vec, PDCC_V(rot)>), grid, dim3(256), 0,
+                             stream, w, c, d, numel, m, signs);
+        });
+      });
+    });
+  });
   return hipGetLastError();
-}
-}  // namespace
-
-hipError_t mx_quantize(const void* src, size_t numel, DType t, void* wire, size_t cb, size_t nchunks,
-                       hipStream_t stream, MxFormat fmt, const uint32_t* rot_signs) {
-  if (!mx_fmt_ok(fmt) || !mx_dtype_ok(t)) return hipErrorInvalidValue;
-  if (!mx_cb_ok(cb) || nchunks == 0 || nchunks > 65535 || !mx_al16(wire) || (numel && !mx_al16(src)))
-    return hipErrorInvalidValue;
-  if (numel > cb * nchunks * kMxBlock) return hipErrorInvalidValue;
-  return mx_quantize_any(fmt, t, false, true, src, numel, wire, cb, nchunks, 0, stream, rot_signs);
-}
-
-hipError_t mx_dequantize(const void* wire, size_t cb, size_t nchunks, void* dst, size_t numel, DType t,
-                         hipStream_t stream, MxFormat fmt, const uint32_t* rot_signs) {
-  if (!mx_fmt_ok(fmt) || !mx_dtype_ok(t)) return hipErrorInvalidValue;
-  if (!mx_cb_ok(cb) || nchunks == 0 || nchunks > 65535 || !mx_al16(wire) || (numel && !mx_al16(dst)))
-    return hipErrorInvalidValue;
-  if (numel > cb * nchunks * kMxBlock) return hipErrorInvalidValue;
-  if (numel == 0) return hipSuccess;
-  return mx_dequantize_any(fmt, t, false, true, wire, cb, nchunks, dst, numel, 0, stream, rot_signs);
-}
-
-hipError_t mx_quantize_shards(const void* src, size_t m, DType t, void* wire, size_t cb, size_t nchunks,
-                              hipStream_t stream, MxFormat fmt, const uint32_t* rot_signs) {
-  if (!mx_fmt_ok(fmt) || !mx_dtype_ok(t)) return hipErrorInvalidValue;
-  if (!mx_shards_ok(m, cb, nchunks) || !mx_al16(wire) || !mx_al16(src)) return hipErrorInvalidValue;
-  const bool vec = m * mx_esize(t) % 16 == 0;  // every shard starts 16-byte aligned
-  return mx_quantize_any(fmt, t, true, vec, src, m * nchunks, wire, cb, nchunks, m, stream, rot_signs);
-}
-
-hipError_t mx_quantize_ef(const void* src, size_t numel, DType t, float* residual, void* wire, size_t cb,
-                          size_t nchunks, hipStream_t stream, MxFormat fmt, const uint32_t* rot_signs) {
-  if (!mx_fmt_ok(fmt) || !mx_dtype_ok(t)) return hipErrorInvalidValue;
-  if (!mx_cb_ok(cb) || nchunks == 0 || nchunks > 65535 || !mx_al16(wire) || (numel && !mx_al16(src)))
-    return hipErrorInvalidValue;
-  if (numel > cb * nchunks * kMxBlock || (numel && (!residual || !mx_al16(residual)))) return hipErrorInvalidValue;
-  // (no elements: no residual to update, the wire is all padding blocks)
-  return mx_quantize_any(fmt, t, false, true, src, numel, wire, cb, nchunks, 0, stream, rot_signs, numel ? residual : nullptr);
-}
-
-hipError_t mx_quantize_shards_ef(const void* src, size_t m, DType t, float* residual, void* wire, size_t cb,
-                                 size_t nchunks, hipStream_t stream, MxFormat fmt, const uint32_t* rot_signs) {
-  if (!mx_fmt_ok(fmt) || !mx_dtype_ok(t)) return hipErrorInvalidValue;
-  if (!mx_shards_ok(m, cb, nchunks) || !mx_al16(wire) || !mx_al16(src) || !residual || !mx_al16(residual))
-    return hipErrorInvalidValue;
-  const bool vec = m * mx_esize(t) % 16 == 0;  // every shard, and its slice of the residual, starts 16-byte aligned
-  return mx_quantize_any(fmt, t, true, vec, src, m * nchunks, wire, cb, nchunks, m, stream, rot_signs, residual);
-}
-
-hipError_t mx_quantize_sr(const void* src, size_t numel, DType t, void* wire, size_t cb, size_t nchunks,
-                          uint64_t seed, uint32_t sr_stream, uint64_t index_offset, hipStream_t stream, MxFormat fmt,
-                          const uint32_t* rot_signs) {
-  if (!mx_fmt_ok(fmt) || !mx_dtype_ok(t)) return hipErrorInvalidValue;
-  if (!mx_cb_ok(cb) || nchunks == 0 || nchunks > 65535 || !mx_al16(wire) || (numel && !mx_al16(src)))
-    return hipErrorInvalidValue;
-  if (numel > cb * nchunks * kMxBlock || index_offset + numel < index_offset) return hipErrorInvalidValue;
-  const MxSr sr{mx_sr_key(seed, sr_stream), index_offset};
-  return mx_quantize_any(fmt, t, false, true, src, numel, wire, cb, nchunks, 0, stream, rot_signs, nullptr, &sr);
-}
-
-hipError_t mx_quantize_shards_sr(const void* src, size_t m, DType t, void* wire, size_t cb, size_t nchunks,
-                                 uint64_t seed, uint32_t sr_stream, uint64_t index_offset, hipStream_t stream,
-                                 MxFormat fmt, const uint32_t* rot_signs) {
-  if (!mx_fmt_ok(fmt) || !mx_dtype_ok(t)) return hipErrorInvalidValue;
-  if (!mx_shards_ok(m, cb, nchunks) || !mx_al16(wire) || !mx_al16(src)) return hipErrorInvalidValue;
-  if (index_offset + m * nchunks < index_offset) return hipErrorInvalidValue;
-  const bool vec = m * mx_esize(t) % 16 == 0;
-  const MxSr sr{mx_sr_key(seed, sr_stream), index_offset};
-  return mx_quantize_any(fmt, t, true, vec, src, m * nchunks, wire, cb, nchunks, m, stream, rot_signs, nullptr, &sr);
-}
-
-hipError_t mx_dequantize_shards(const void* wire, size_t cb, size_t nchunks, void* dst, size_t m, DType t,
-                                hipStream_t stream, MxFormat fmt, const uint32_t* rot_signs) {
-  if (!mx_fmt_ok(fmt) || !mx_dtype_ok(t)) return hipErrorInvalidValue;
-  if (!mx_shards_ok(m, cb, nchunks) || !mx_al16(wire) || !mx_al16(dst)) return hipErrorInvalidValue;
-  const bool vec = m * mx_esize(t) % 16 == 0;
-  return mx_dequantize_any(fmt, t, true, vec, wire, cb, nchunks, dst, m * nchunks, m, stream, rot_signs);
 }
 
 // ---- tensor lists: one launch per kMaxMxListDescs tensors that own a block
-namespace {
-template <MxFormat F, DType DT, bool ROT>
-void mx_quantize_list_go(const dim3& grid, const dev::MxListArgs& a, char* w, uint32_t cb, uint32_t spc, uint32_t s0,
-                         uint32_t s1, float* res, const MxSr* sr, hipStream_t stream, uint32_t signs) {
-  if (sr) hipLaunchKernelGGL((dev::k_mx_quantize_list<F, DT, false, true, ROT>), grid, dim3(256), 0, stream, a, w, cb, spc, s0, s1, nullptr, sr->key, sr->base, signs);
-  else if (res) hipLaunchKernelGGL((dev::k_mx_quantize_list<F, DT, true, false, ROT>), grid, dim3(256), 0, stream, a, w, cb, spc, s0, s1, res, 0u, 0u, signs);
-  else hipLaunchKernelGGL((dev::k_mx_quantize_list<F, DT, false, false, ROT>), grid, dim3(256), 0, stream, a, w, cb, spc, s0, s1, res, 0u, 0u, signs);
-}
-template <MxFormat F, DType DT, bool ROT>
-void mx_dequantize_list_go(const dim3& grid, const dev::MxListArgs& a, char* w, uint32_t cb, uint32_t spc, uint32_t s0,
-                           uint32_t s1, float*, const MxSr*, hipStream_t stream, uint32_t signs) {
-  hipLaunchKernelGGL((dev::k_mx_dequantize_list<F, DT, ROT>), grid, dim3(256), 0, stream, a, w, cb, spc, s0, s1, signs);
-}
-template <bool QUANT, MxFormat F, DType DT, class... A>
-void mx_list_rot(const uint32_t* rot, A... a) {
-  if constexpr (QUANT) {
-    if (rot) mx_quantize_list_go<F, DT, true>(a..., *rot);
-    else mx_quantize_list_go<F, DT, false>(a..., 0u);
-  } else {
-    if (rot) mx_dequantize_list_go<F, DT, true>(a..., *rot);
-    else mx_dequantize_list_go<F, DT, false>(a..., 0u);
-  }
-}
-template <bool QUANT, MxFormat F, class... A>
-void mx_list_dt(DType t, A... a) {
-  switch (t) {
-    case DType::F32: mx_list_rot<QUANT, F, DType::F32>(a...); break;
-    case DType::BF16: mx_list_rot<QUANT, F, DType::BF16>(a...); break;
-    default: mx_list_rot<QUANT, F, DType::F16>(a...); break;
-  }
-}
 // Quantize (QUANT) or dequantize the list in launches of up to kMaxMxListDescs tensors. A launch owns the
 // blocks from its first tensor's to the next launch's; the last one of a quantize also owns the padding
 // blocks up to cb * nchunks, and a list without a block is one launch of padding alone.
 template <bool QUANT>
-hipError_t mx_list_run(const MxListTensor* ts, size_t k, DType t, char* wire, size_t cb, size_t nchunks, MxFormat fmt,
-                       const uint32_t* rot, float* res, const MxSr* sr, hipStream_t stream) {
-  if (!mx_fmt_ok(fmt) || !mx_dtype_ok(t) || !mx_cb_ok(cb) || nchunks == 0 || nchunks > 65535 || !mx_al16(wire))
-    return hipErrorInvalidValue;
-  if (k > 65535 || (k && !ts)) return hipErrorInvalidValue;
+hipError_t mx_list_run(const MxListTensor* ts, size_t k, DType t, char* wire, size_t cb, size_t nchunks,
+                       hipStream_t stream, const MxOpts& opts) {
+  if (!mx_args_ok(opts, QUANT, cb, wire, nullptr) || !mx_dtype_ok(t) || !mx_chunks_ok(nchunks)) return hipErrorInvalidValue;
+  if (k > 65535 || (k && !ts) || !mx_sr_fits(opts, mx_list_numel(ts, k))) return hipErrorInvalidValue;
+  MxOpts o = opts;
+  if (mx_list_blocks(ts, k) == 0 && !o.sr) o.residual = nullptr;  // (no block: no residual to update, the wire is all padding blocks)
+  const MxSrKey sr = mx_sr_key_of(o);
+  const uint32_t signs = o.rot_signs ? *o.rot_signs : 0u;
   const uint64_t total = (uint64_t)cb * nchunks;  // blocks on the wire; the kernels count them in 32 bits
   if (total >= (uint64_t(1) << 32) || mx_list_blocks(ts, k) > total) return hipErrorInvalidValue;
   for (size_t i = 0; i < k; ++i)
@@ -1341,147 +1269,127 @@ hipError_t mx_list_run(const MxListTensor* ts, size_t k, DType t, char* wire, si
     const uint32_t s0 = span_of(a.g0), s1 = span_of(a.g1 - 1) + 1;
     const dim3 grid((uint32_t)std::min<uint64_t>(s1 - s0, dev::kMxGridStream));
     const uint32_t c = (uint32_t)cb;
-    if (fmt == MxFormat::FP4_E2M1) mx_list_dt<QUANT, MxFormat::FP4_E2M1>(t, rot, grid, a, wire, c, spc, s0, s1, res, sr, stream);
-    else if (fmt == MxFormat::FP6_E2M3) mx_list_dt<QUANT, MxFormat::FP6_E2M3>(t, rot, grid, a, wire, c, spc, s0, s1, res, sr, stream);
-    else mx_list_dt<QUANT, MxFormat::FP8_E4M3>(t, rot, grid, a, wire, c, spc, s0, s1, res, sr, stream);
+    mx_lift_fmt(o.fmt, [&](auto f) {
+      mx_lift_dtype(t, [&](auto dt) {
+        mx_lift_bool(o.rot_signs != nullptr, [&](auto rot) {
+          if constexpr (QUANT) {
+            mx_lift_mode(o, [&](auto mode) {
+              constexpr bool ef = PDCC_V(mode) == MxMode::EF, st = PDCC_V(mode) == MxMode::SR;
+              hipLaunchKernelGGL((dev::k_mx_quantize_list<PDCC_V(f), PDCC_V(dt), ef, st, PDCC_V(rot)>), grid, dim3(256), 0,
+                                 stream, a, wire, c, spc, s0, s1, o.residual, sr.key, sr.base, signs);
+            });
+          } else {
+            hipLaunchKernelGGL((dev::k_mx_dequantize_list<PDCC_V(f), PDCC_V(dt), PDCC_V(rot)>), grid, dim3(256), 0, stream, a,
+                               wire, c, spc, s0, s1, signs);
+          }
+        });
+      });
+    });
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
   }
   return hipSuccess;
 }
+
+// reduce: lanes per block from the payload bytes of a lane, 16 (FP6: 24)
+hipError_t mx_reduce_launch(const void* wire_in, int nsrc, size_t cb, RedOp op, int avg_div, void* wire_out,
+                            hipStream_t stream, const MxOpts& o) {
+  const char* in = static_cast<const char*>(wire_in);
+  char* out = static_cast<char*>(wire_out);
+  const uint32_t c = (uint32_t)cb, key = mx_sr_key_of(o).key;
+  const int lpb = o.fmt == MxFormat::FP8_E4M3 ? 2 : 1;
+  const dim3 grid(dev::mx_grid_x((uint64_t)cb * lpb, 1, 1, dev::kMxGridReduce));
+  mx_lift_fmt(o.fmt, [&](auto f) {
+    mx_lift_bool(op == RedOp::AVG, [&](auto avg) {
+      mx_lift_mode(o, [&](auto mode) {
+        mx_lift_nsrc(nsrc, [&](auto n) {
+          constexpr bool ef = PDCC_V(mode) == MxMode::EF, st = PDCC_V(mode) == MxMode::SR;
+          hipLaunchKernelGGL((dev::k_mx_reduce<PDCC_V(f), PDCC_V(n), PDCC_V(avg), ef, st>), grid, dim3(256), 0, stream, in, c,
+                             avg_div, out, o.residual, key);
+        });
+      });
+    });
+  });
+  return hipGetLastError();
+}
+hipError_t mx_fold_launch(const void* wire_in, int nsrc, size_t cb, RedOp op, int avg_div, void* dst, size_t numel, DType t,
+                          hipStream_t stream, const MxOpts& o) {
+  const char* in = static_cast<const char*>(wire_in);
+  char* d = static_cast<char*>(dst);
+  const uint32_t c = (uint32_t)cb, signs = o.rot_signs ? *o.rot_signs : 0u;
+  const uint64_t epl = 16 / mx_esize(t), nvec = (numel + epl - 1) / epl;
+  mx_lift_fmt(o.fmt, [&](auto f) {
+    mx_lift_dtype(t, [&](auto dt) {
+      mx_lift_nsrc(nsrc, [&](auto n) {
+        mx_lift_bool(op == RedOp::AVG, [&](auto avg) {
+          mx_lift_bool(o.rot_signs != nullptr, [&](auto rot) {
+            const dim3 grid(dev::mx_grid_x(nvec, dev::kMxFoldUnroll<PDCC_V(n)>, 1, dev::kMxGridReduce));
+            hipLaunchKernelGGL((dev::k_mx_fold<PDCC_V(f), PDCC_V(dt), PDCC_V(n), PDCC_V(avg), PDCC_V(rot)>), grid, dim3(256), 0,
+                               stream, in, c, avg_div, d, numel, signs);
+          });
+        });
+      });
+    });
+  });
+  return hipGetLastError();
+}
+#undef PDCC_V
 }  // namespace
 
+hipError_t mx_quantize(const void* src, size_t numel, DType t, void* wire, size_t cb, size_t nchunks, hipStream_t stream,
+                       const MxOpts& opts) {
+  MxOpts o = opts;
+  if (numel == 0 && !o.sr) o.residual = nullptr;  // (no elements: no residual to update, the wire is all padding blocks)
+  if (!mx_args_ok(o, true, cb, wire, numel ? src : nullptr) || !mx_dtype_ok(t) || !mx_chunks_ok(nchunks))
+    return hipErrorInvalidValue;
+  if (numel > cb * nchunks * kMxBlock || !mx_sr_fits(o, numel)) return hipErrorInvalidValue;
+  return mx_quantize_launch(MxLayout::DEALT, src, numel, 0, t, wire, cb, nchunks, stream, o);
+}
+
+hipError_t mx_quantize_shards(const void* src, size_t m, DType t, void* wire, size_t cb, size_t nchunks,
+                              hipStream_t stream, const MxOpts& o) {
+  if (!mx_args_ok(o, true, cb, wire, src) || !mx_dtype_ok(t) || !mx_shards_ok(m, cb, nchunks)) return hipErrorInvalidValue;
+  if (!mx_sr_fits(o, m * nchunks)) return hipErrorInvalidValue;
+  return mx_quantize_launch(mx_shard_layout(m, t), src, m * nchunks, m, t, wire, cb, nchunks, stream, o);
+}
+
 hipError_t mx_quantize_list(const MxListTensor* ts, size_t k, DType t, void* wire, size_t cb, size_t nchunks,
-                            hipStream_t stream, MxFormat fmt, const uint32_t* rot_signs, float* residual,
-                            const MxListSr* sr) {
-  if (residual && sr) return hipErrorInvalidValue;
-  const size_t n = mx_list_numel(ts, k);
-  if (residual && !mx_al16(residual)) return hipErrorInvalidValue;
-  if (sr && sr->index_offset + n < sr->index_offset) return hipErrorInvalidValue;
-  const MxSr s{sr ? mx_sr_key(sr->seed, sr->stream) : 0u, sr ? sr->index_offset : 0u};
-  // (no block: no residual to update, the wire is all padding blocks)
-  return mx_list_run<true>(ts, k, t, static_cast<char*>(wire), cb, nchunks, fmt, rot_signs, n ? residual : nullptr,
-                           sr ? &s : nullptr, stream);
+                            hipStream_t stream, const MxOpts& o) {
+  return mx_list_run<true>(ts, k, t, static_cast<char*>(wire), cb, nchunks, stream, o);
+}
+
+hipError_t mx_reduce(const void* wire_in, int nsrc, size_t cb, RedOp op, int avg_div, void* wire_out, hipStream_t stream,
+                     const MxOpts& o) {
+  if (!mx_args_ok(o, true, cb, wire_in, wire_out) || !mx_fold_ok(nsrc, op, avg_div)) return hipErrorInvalidValue;
+  if (o.sr && o.sr->index_offset) return hipErrorInvalidValue;  // (the word index is the element's index in the chunk)
+  return mx_reduce_launch(wire_in, nsrc, cb, op, avg_div, wire_out, stream, o);
+}
+
+hipError_t mx_dequantize(const void* wire, size_t cb, size_t nchunks, void* dst, size_t numel, DType t,
+                         hipStream_t stream, const MxOpts& o) {
+  if (!mx_args_ok(o, false, cb, wire, numel ? dst : nullptr) || !mx_dtype_ok(t) || !mx_chunks_ok(nchunks))
+    return hipErrorInvalidValue;
+  if (numel > cb * nchunks * kMxBlock) return hipErrorInvalidValue;
+  if (numel == 0) return hipSuccess;
+  return mx_dequantize_launch(MxLayout::DEALT, wire, cb, nchunks, dst, numel, 0, t, stream, o);
+}
+
+hipError_t mx_dequantize_shards(const void* wire, size_t cb, size_t nchunks, void* dst, size_t m, DType t,
+                                hipStream_t stream, const MxOpts& o) {
+  if (!mx_args_ok(o, false, cb, wire, dst) || !mx_dtype_ok(t) || !mx_shards_ok(m, cb, nchunks)) return hipErrorInvalidValue;
+  return mx_dequantize_launch(mx_shard_layout(m, t), wire, cb, nchunks, dst, m * nchunks, m, t, stream, o);
 }
 
 hipError_t mx_dequantize_list(const void* wire, size_t cb, size_t nchunks, const MxListTensor* ts, size_t k, DType t,
-                              hipStream_t stream, MxFormat fmt, const uint32_t* rot_signs) {
-  return mx_list_run<false>(ts, k, t, const_cast<char*>(static_cast<const char*>(wire)), cb, nchunks, fmt, rot_signs,
-                            nullptr, nullptr, stream);
+                              hipStream_t stream, const MxOpts& o) {
+  return mx_list_run<false>(ts, k, t, const_cast<char*>(static_cast<const char*>(wire)), cb, nchunks, stream, o);
 }
-
-namespace {
-template <MxFormat F, bool AVG, bool EF, bool SR>
-hipError_t mx_reduce_go(const char* in, int nsrc, uint32_t cb, int avg_div, char* out, float* res, uint32_t key,
-                        hipStream_t stream) {
-  constexpr int lpb = F == MxFormat::FP8_E4M3 ? 2 : 1;  // lanes per block: 16 (FP6: 24) payload bytes per lane
-  const dim3 grid(dev::mx_grid_x((uint64_t)cb * lpb, 1, 1, dev::kMxGridReduce)), block(256);
-  switch (nsrc) {
-#define PDCC_MX_N(N) \
-  case N: hipLaunchKernelGGL((dev::k_mx_reduce<F, N, AVG, EF, SR>), grid, block, 0, stream, in, cb, avg_div, out, res, key); break;
-    PDCC_MX_N(1) PDCC_MX_N(2) PDCC_MX_N(3) PDCC_MX_N(4) PDCC_MX_N(5) PDCC_MX_N(6) PDCC_MX_N(7) PDCC_MX_N(8)
-#undef PDCC_MX_N
-    default: return hipErrorInvalidValue;
-  }
-  return hipGetLastError();
-}
-// (`key`: the stochastic kernels; else `res` null: the plain kernels; otherwise the error-feedback ones)
-template <MxFormat F>
-hipError_t mx_reduce_op(const char* in, int nsrc, uint32_t cb, RedOp op, int avg_div, char* out, float* res,
-                        const uint32_t* key, hipStream_t stream) {
-  if (key)
-    return op == RedOp::AVG ? mx_reduce_go<F, true, false, true>(in, nsrc, cb, avg_div, out, nullptr, *key, stream)
-                            : mx_reduce_go<F, false, false, true>(in, nsrc, cb, avg_div, out, nullptr, *key, stream);
-  if (res)
-    return op == RedOp::AVG ? mx_reduce_go<F, true, true, false>(in, nsrc, cb, avg_div, out, res, 0u, stream)
-                            : mx_reduce_go<F, false, true, false>(in, nsrc, cb, avg_div, out, res, 0u, stream);
-  return op == RedOp::AVG ? mx_reduce_go<F, true, false, false>(in, nsrc, cb, avg_div, out, res, 0u, stream)
-                          : mx_reduce_go<F, false, false, false>(in, nsrc, cb, avg_div, out, res, 0u, stream);
-}
-hipError_t mx_reduce_any(const void* wire_in, int nsrc, size_t cb, RedOp op, int avg_div, void* wire_out, float* res,
-                         hipStream_t stream, MxFormat fmt, const uint32_t* key = nullptr) {
-  if (!mx_fmt_ok(fmt) || !mx_cb_ok(cb) || nsrc < 1 || nsrc > kMaxRanks || !mx_al16(wire_in) || !mx_al16(wire_out))
-    return hipErrorInvalidValue;
-  if (op != RedOp::SUM && op != RedOp::AVG) return hipErrorInvalidValue;
-  if (op == RedOp::AVG && avg_div < 1) return hipErrorInvalidValue;
-  const char* in = static_cast<const char*>(wire_in);
-  char* out = static_cast<char*>(wire_out);
-  if (fmt == MxFormat::FP6_E2M3) return mx_reduce_op<MxFormat::FP6_E2M3>(in, nsrc, (uint32_t)cb, op, avg_div, out, res, key, stream);
-  return fmt == MxFormat::FP4_E2M1 ? mx_reduce_op<MxFormat::FP4_E2M1>(in, nsrc, (uint32_t)cb, op, avg_div, out, res, key, stream)
-                                   : mx_reduce_op<MxFormat::FP8_E4M3>(in, nsrc, (uint32_t)cb, op, avg_div, out, res, key, stream);
-}
-}  // namespace
-
-hipError_t mx_reduce(const void* wire_in, int nsrc, size_t cb, RedOp op, int avg_div, void* wire_out,
-                     hipStream_t stream, MxFormat fmt) {
-  return mx_reduce_any(wire_in, nsrc, cb, op, avg_div, wire_out, nullptr, stream, fmt);
-}
-
-hipError_t mx_reduce_ef(const void* wire_in, int nsrc, size_t cb, RedOp op, int avg_div, float* residual,
-                        void* wire_out, hipStream_t stream, MxFormat fmt) {
-  if (!residual || !mx_al16(residual)) return hipErrorInvalidValue;
-  return mx_reduce_any(wire_in, nsrc, cb, op, avg_div, wire_out, residual, stream, fmt);
-}
-
-hipError_t mx_reduce_sr(const void* wire_in, int nsrc, size_t cb, RedOp op, int avg_div, void* wire_out, uint64_t seed,
-                        uint32_t sr_stream, hipStream_t stream, MxFormat fmt) {
-  const uint32_t key = mx_sr_key(seed, sr_stream);
-  return mx_reduce_any(wire_in, nsrc, cb, op, avg_div, wire_out, nullptr, stream, fmt, &key);
-}
-
-namespace {
-template <MxFormat F, DType DT, bool AVG, bool ROT>
-hipError_t mx_fold_go(const char* in, int nsrc, uint32_t cb, int avg_div, char* dst, size_t numel, uint32_t signs,
-                      hipStream_t stream) {
-  constexpr int epl = 16 / (int)sizeof(typename dev::Tr<DT>::S);
-  const uint64_t nvec = (numel + epl - 1) / epl;
-  const dim3 block(256);
-  switch (nsrc) {
-#define PDCC_MX_N(N)                                                                                                       \
-  case N: {                                                                                                                \
-    const dim3 grid(dev::mx_grid_x(nvec, dev::kMxFoldUnroll<N>, 1, dev::kMxGridReduce));                                   \
-    hipLaunchKernelGGL((dev::k_mx_fold<F, DT, N, AVG, ROT>), grid, block, 0, stream, in, cb, avg_div, dst, numel, signs); \
-    break;                                                                                                                 \
-  }
-    PDCC_MX_N(1) PDCC_MX_N(2) PDCC_MX_N(3) PDCC_MX_N(4) PDCC_MX_N(5) PDCC_MX_N(6) PDCC_MX_N(7) PDCC_MX_N(8)
-#undef PDCC_MX_N
-    default: return hipErrorInvalidValue;
-  }
-  return hipGetLastError();
-}
-template <MxFormat F, DType DT>
-hipError_t mx_fold_op(const char* in, int nsrc, uint32_t cb, RedOp op, int avg_div, char* dst, size_t numel,
-                      const uint32_t* rot, hipStream_t stream) {
-  if (rot)
-    return op == RedOp::AVG ? mx_fold_go<F, DT, true, true>(in, nsrc, cb, avg_div, dst, numel, *rot, stream)
-                            : mx_fold_go<F, DT, false, true>(in, nsrc, cb, avg_div, dst, numel, *rot, stream);
-  return op == RedOp::AVG ? mx_fold_go<F, DT, true, false>(in, nsrc, cb, avg_div, dst, numel, 0u, stream)
-                          : mx_fold_go<F, DT, false, false>(in, nsrc, cb, avg_div, dst, numel, 0u, stream);
-}
-template <MxFormat F>
-hipError_t mx_fold_dt(DType t, const char* in, int nsrc, uint32_t cb, RedOp op, int avg_div, char* d, size_t numel,
-                      const uint32_t* rot, hipStream_t stream) {
-  switch (t) {
-    case DType::F32: return mx_fold_op<F, DType::F32>(in, nsrc, cb, op, avg_div, d, numel, rot, stream);
-    case DType::BF16: return mx_fold_op<F, DType::BF16>(in, nsrc, cb, op, avg_div, d, numel, rot, stream);
-    case DType::F16: return mx_fold_op<F, DType::F16>(in, nsrc, cb, op, avg_div, d, numel, rot, stream);
-    default: return hipErrorInvalidValue;
-  }
-}
-}  // namespace
 
 hipError_t mx_fold(const void* wire_in, int nsrc, size_t cb, RedOp op, int avg_div, void* dst, size_t numel, DType t,
-                   hipStream_t stream, MxFormat fmt, const uint32_t* rot_signs) {
-  if (!mx_fmt_ok(fmt) || !mx_cb_ok(cb) || nsrc < 1 || nsrc > kMaxRanks || !mx_al16(wire_in) || !mx_al16(dst))
-    return hipErrorInvalidValue;
+                   hipStream_t stream, const MxOpts& o) {
+  if (!mx_args_ok(o, false, cb, wire_in, dst) || !mx_dtype_ok(t) || !mx_fold_ok(nsrc, op, avg_div)) return hipErrorInvalidValue;
   if (numel == 0 || numel > cb * kMxBlock) return hipErrorInvalidValue;
-  if (op != RedOp::SUM && op != RedOp::AVG) return hipErrorInvalidValue;
-  if (op == RedOp::AVG && avg_div < 1) return hipErrorInvalidValue;
-  const char* in = static_cast<const char*>(wire_in);
-  char* d = static_cast<char*>(dst);
-  if (fmt == MxFormat::FP6_E2M3) return mx_fold_dt<MxFormat::FP6_E2M3>(t, in, nsrc, (uint32_t)cb, op, avg_div, d, numel, rot_signs, stream);
-  return fmt == MxFormat::FP4_E2M1 ? mx_fold_dt<MxFormat::FP4_E2M1>(t, in, nsrc, (uint32_t)cb, op, avg_div, d, numel, rot_signs, stream)
-                                   : mx_fold_dt<MxFormat::FP8_E4M3>(t, in, nsrc, (uint32_t)cb, op, avg_div, d, numel, rot_signs, stream);
+  return mx_fold_launch(wire_in, nsrc, cb, op, avg_div, dst, numel, t, stream, o);
 }
 
 }  // namespace kern

@@ -44,7 +44,7 @@ the plain-PyTorch fp32 references the tests compare against.
 """
 from __future__ import annotations
 
-from typing import Sequence
+from typing import NamedTuple, Sequence
 
 import torch
 
@@ -157,21 +157,36 @@ def unpack(flat: torch.Tensor, tensors: Sequence[torch.Tensor]) -> None:
 # wire tensor itself it is positional-only (``w``), so the keyword is free for the format's name.
 MX_BLOCK = 32
 MX_DTYPES = (torch.float32, torch.bfloat16, torch.float16)
-MX_WIRES = ("mxfp8_e4m3", "mxfp4_e2m1", "mxfp6_e2m3")
-_MX_PAYLOAD = {"mxfp8_e4m3": 32, "mxfp4_e2m1": 16, "mxfp6_e2m3": 24}  # payload bytes per block; one scale byte follows
+
+class _MxFormat(NamedTuple):
+    """What the Python side knows of a wire format (the kernels' table: MxFmt in csrc/kernels/mx_wire.hip)."""
+    payload: int    # payload bytes per block; one scale byte follows
+    mant: int       # mantissa bits of a code
+    fmin: int       # f32 exponent field of the smallest normal magnitude
+    bias: int       # the scale rule: e = k - bias for amax = m 2^k, 1 <= m < 2 ...
+    switch: float   # ... and one more where frexp's mantissa m / 2 is above this
+    emin: int       # lower and upper clamp of e
+    emax: int
+    sign: int       # the sign's bit in a code
 
 
-def _mx_payload(wire, who: str) -> int:
-    """Payload bytes per block of a wire format; ValueError for a name that is not one."""
-    if not isinstance(wire, str) or wire not in _MX_PAYLOAD:
+_MX_FORMATS = {"mxfp8_e4m3": _MxFormat(32, 3, 121, 8, 0.875, -117, 120, 7),
+               "mxfp4_e2m1": _MxFormat(16, 1, 127, 2, 0.75, -125, 126, 3),
+               "mxfp6_e2m3": _MxFormat(24, 3, 127, 2, 0.9375, -123, 126, 5)}
+MX_WIRES = tuple(_MX_FORMATS)
+
+
+def _mx_format(wire, who: str) -> _MxFormat:
+    """The table row of a wire format; ValueError for a name that is not one."""
+    if not isinstance(wire, str) or wire not in _MX_FORMATS:
         raise ValueError(f"{who}: unknown wire format {wire!r} (supported: {', '.join(MX_WIRES)})")
-    return _MX_PAYLOAD[wire]
+    return _MX_FORMATS[wire]
 
 
 def mx_chunk_blocks(numel: int, world: int = 1, *, wire: str = "mxfp8_e4m3") -> int:
     """Blocks per chunk when ``numel`` elements are dealt to ``world`` chunks (csrc/kernels/mx_layout.h):
     a multiple of 16, and of 4096 once a chunk's wire (33, 17 or 25 bytes per block) reaches 1 MiB."""
-    bw = _mx_payload(wire, "mx_chunk_blocks") + 1
+    bw = _mx_format(wire, "mx_chunk_blocks").payload + 1
     world = max(1, int(world))
     blocks = (int(numel) + MX_BLOCK - 1) // MX_BLOCK
     cb = max(16, ((blocks + world - 1) // world + 15) // 16 * 16)
@@ -183,7 +198,7 @@ def mx_chunk_blocks(numel: int, world: int = 1, *, wire: str = "mxfp8_e4m3") -> 
 def mx_wire_bytes(numel: int, world: int = 1, *, wire: str = "mxfp8_e4m3") -> int:
     """Bytes of the wire of ``numel`` elements in ``world`` chunks: ``world`` x (32 cb payload + cb scales);
     16 cb payload bytes for ``mxfp4_e2m1``, 24 cb for ``mxfp6_e2m3``."""
-    return (_mx_payload(wire, "mx_wire_bytes") + 1) * mx_chunk_blocks(numel, world, wire=wire) * max(1, int(world))
+    return (_mx_format(wire, "mx_wire_bytes").payload + 1) * mx_chunk_blocks(numel, world, wire=wire) * max(1, int(world))
 
 
 def mx_shard_blocks(m: int, *, wire: str = "mxfp8_e4m3") -> int:
@@ -194,7 +209,7 @@ def mx_shard_blocks(m: int, *, wire: str = "mxfp8_e4m3") -> int:
 
 def mx_shard_wire_bytes(m: int, world: int = 1, *, wire: str = "mxfp8_e4m3") -> int:
     """Bytes of the shard wire of ``world`` shards of ``m`` elements."""
-    return (_mx_payload(wire, "mx_shard_wire_bytes") + 1) * mx_shard_blocks(m, wire=wire) * max(1, int(world))
+    return (_mx_format(wire, "mx_shard_wire_bytes").payload + 1) * mx_shard_blocks(m, wire=wire) * max(1, int(world))
 
 
 def _mx_check_dtype(dt, who):
@@ -208,23 +223,23 @@ def mx_owner_residual_numel(numel: int, world: int = 1, *, wire: str = "mxfp8_e4
     return MX_BLOCK * mx_chunk_blocks(numel, world, wire=wire)
 
 
-def _mx_check_residual(residual, numel: int, device, who: str) -> None:
+def _mx_check_residual(residual, numel: int, device, who: str, name: str = "the residual", data: str = "data") -> None:
     """An error-feedback residual (docs/collectives.md "Error feedback") is updated in place, which rules
     out the copy the other arguments may go through: float32, ``numel`` elements, on ``device``,
-    contiguous and 16-byte aligned."""
+    contiguous and 16-byte aligned. ``name``, ``data``: what the messages call it and what it belongs to."""
     if residual is None:
         return
     if not isinstance(residual, torch.Tensor) or residual.dtype != torch.float32:
-        raise TypeError(f"{who}: the residual must be a float32 tensor, got "
+        raise TypeError(f"{who}: {name} must be a float32 tensor, got "
                         f"{residual.dtype if isinstance(residual, torch.Tensor) else type(residual).__name__}")
     if residual.numel() != int(numel):
-        raise ValueError(f"{who}: the residual has {residual.numel()} elements, {int(numel)} expected")
+        raise ValueError(f"{who}: {name} has {residual.numel()} elements, {int(numel)} expected")
     if residual.device != device:
-        raise ValueError(f"{who}: the residual is on {residual.device}, the data on {device}")
+        raise ValueError(f"{who}: {name} is on {residual.device}, the {data} on {device}")
     if not residual.is_contiguous():
-        raise ValueError(f"{who}: the residual must be contiguous")
+        raise ValueError(f"{who}: {name} must be contiguous")
     if residual.data_ptr() % 16:
-        raise ValueError(f"{who}: the residual must be 16-byte aligned")
+        raise ValueError(f"{who}: {name} must be 16-byte aligned")
 
 
 MX_ROUNDINGS = ("nearest", "stochastic")
@@ -252,16 +267,26 @@ MX_ROTATIONS = ("hadamard",)
 _MX_ROT_STREAM = 0x52484431  # the stream of the sign word ("RHD1"), no rank's stream
 
 
-def _mx_check_rotation(rotation, rotation_seed, who: str) -> dict:
-    """The rotation arguments (docs/collectives.md "Hadamard rotation") -> the keywords of the native call: none
-    without a rotation, so that call is what it was. The seed is checked whatever the rotation is."""
+def _mx_check_rotation(rotation, rotation_seed, who: str) -> bool:
+    """The rotation arguments (docs/collectives.md "Hadamard rotation"); True for a rotation. The seed is checked
+    whatever the rotation is."""
     if rotation is not None and (not isinstance(rotation, str) or rotation not in MX_ROTATIONS):
         raise ValueError(f"{who}: unknown rotation {rotation!r} (supported: None, {', '.join(MX_ROTATIONS)})")
     if isinstance(rotation_seed, bool) or not isinstance(rotation_seed, int):
         raise TypeError(f"{who}: rotation_seed must be an int, got {type(rotation_seed).__name__}")
     if not 0 <= rotation_seed < 1 << 64:
         raise ValueError(f"{who}: rotation_seed must be in [0, 2^64), got {rotation_seed}")
-    return {} if rotation is None else {"rot": True, "rot_seed": rotation_seed}
+    return rotation is not None
+
+
+def _mx_quantizer_args(who: str, wire, residual, numel: int, device, rounding, seed, stream, index_offset=0,
+                       rot=False, rotation_seed=0) -> tuple:
+    """The options of a quantizer after the caller's look at the format and (``rot``: what ``_mx_check_rotation``
+    returned) the rotation: the rounding, then the residual (of ``numel`` elements on ``device``). Returns the
+    trailing arguments of the native call: ``(wire, residual, sr, seed, stream, index_offset, rot, rot_seed)``."""
+    sr = _mx_check_rounding(rounding, seed, stream, index_offset, numel, residual, who)
+    _mx_check_residual(residual, numel, device, who)
+    return wire, None if residual is None else residual.detach(), sr, seed, stream, index_offset, rot, rotation_seed
 
 
 def mx_rotation_signs(seed: int) -> int:
@@ -293,15 +318,11 @@ def mx_quantize(x: torch.Tensor, world: int = 1, out: torch.Tensor | None = None
     scale, the rounding and the residual all belong to the rotated block; :func:`mx_dequantize` and
     :func:`mx_fold` with the same two arguments rotate back. Wire layout and size are unchanged."""
     _mx_check_dtype(x.dtype, "mx_quantize")
-    _mx_payload(wire, "mx_quantize")
+    _mx_format(wire, "mx_quantize")
     rot = _mx_check_rotation(rotation, rotation_seed, "mx_quantize")
-    if _mx_check_rounding(rounding, seed, stream, index_offset, x.numel(), residual, "mx_quantize"):
-        return _C().mx_quantize(x.detach().reshape(-1), int(world), out, wire, None, True, seed, stream, index_offset,
-                                **rot)
-    if residual is None:
-        return _C().mx_quantize(x.detach().reshape(-1), int(world), out, wire, **rot)
-    _mx_check_residual(residual, x.numel(), x.device, "mx_quantize")
-    return _C().mx_quantize(x.detach().reshape(-1), int(world), out, wire, residual.detach(), **rot)
+    args = _mx_quantizer_args("mx_quantize", wire, residual, x.numel(), x.device, rounding, seed, stream, index_offset,
+                              rot, rotation_seed)
+    return _C().mx_quantize(x.detach().reshape(-1), int(world), out, *args)
 
 
 def mx_reduce(w: torch.Tensor, /, nsrc: int, op: str = "sum", out: torch.Tensor | None = None, *,
@@ -317,13 +338,10 @@ def mx_reduce(w: torch.Tensor, /, nsrc: int, op: str = "sum", out: torch.Tensor 
     chunk)``; a single finite source comes back as its own bytes. Not together with ``residual``."""
     if op not in ("sum", "avg"):
         raise ValueError(f"mx_reduce: op must be 'sum' or 'avg', got {op!r}")
-    pb = _mx_payload(wire, "mx_reduce")
-    if _mx_check_rounding(rounding, seed, stream, 0, 0, residual, "mx_reduce"):
-        return _C().mx_reduce(w, int(nsrc), op, out, wire, None, True, seed, stream)
-    if residual is None:
-        return _C().mx_reduce(w, int(nsrc), op, out, wire)
-    _mx_check_residual(residual, w.numel() // ((pb + 1) * max(1, int(nsrc))) * MX_BLOCK, w.device, "mx_reduce")
-    return _C().mx_reduce(w, int(nsrc), op, out, wire, residual.detach())
+    bw = _mx_format(wire, "mx_reduce").payload + 1
+    n = 0 if residual is None else w.numel() // (bw * max(1, int(nsrc))) * MX_BLOCK  # the elements of a chunk
+    args = _mx_quantizer_args("mx_reduce", wire, residual, n, w.device, rounding, seed, stream)
+    return _C().mx_reduce(w, int(nsrc), op, out, *args[:5])  # (no index offset, no rotation: rotated wires fold as they are)
 
 
 def mx_dequantize(w: torch.Tensor, /, numel: int, dtype: torch.dtype = torch.float32, world: int = 1,
@@ -333,7 +351,7 @@ def mx_dequantize(w: torch.Tensor, /, numel: int, dtype: torch.dtype = torch.flo
     into ``out`` (``numel`` elements, any shape) when given -- exactly those elements and nothing else.
     ``rotation``, ``rotation_seed``: those of the :func:`mx_quantize` that made the wire; every dequantized
     block is rotated back before it is rounded."""
-    _mx_payload(wire, "mx_dequantize")
+    _mx_format(wire, "mx_dequantize")
     rot = _mx_check_rotation(rotation, rotation_seed, "mx_dequantize")
     if out is None:
         _mx_check_dtype(dtype, "mx_dequantize")
@@ -342,7 +360,7 @@ def mx_dequantize(w: torch.Tensor, /, numel: int, dtype: torch.dtype = torch.flo
         _mx_check_dtype(out.dtype, "mx_dequantize")
         if out.numel() != int(numel):
             raise ValueError(f"mx_dequantize: out has {out.numel()} elements, numel is {numel}")
-    _C().mx_dequantize(w, int(world), out, wire, **rot)
+    _C().mx_dequantize(w, int(world), out, wire, rot, rotation_seed)
     return out
 
 
@@ -385,15 +403,12 @@ def mx_quantize_list(xs: Sequence[torch.Tensor], world: int = 1, out: torch.Tens
     positions past a tensor's end are left as +0. ``rounding``, ``seed``, ``stream``: as in :func:`mx_quantize`,
     the word index of an element being its position in the padded concatenation. ``rotation``: as there."""
     xs = _mx_check_list(xs, "mx_quantize_list")
-    _mx_payload(wire, "mx_quantize_list")
+    _mx_format(wire, "mx_quantize_list")
     n = mx_list_numel([x.numel() for x in xs])
     rot = _mx_check_rotation(rotation, rotation_seed, "mx_quantize_list")
-    if _mx_check_rounding(rounding, seed, stream, 0, n, residual, "mx_quantize_list"):
-        return _C().mx_quantize_list(xs, int(world), out, wire, None, True, seed, stream, **rot)
-    if residual is None:
-        return _C().mx_quantize_list(xs, int(world), out, wire, **rot)
-    _mx_check_residual(residual, n, xs[0].device, "mx_quantize_list")
-    return _C().mx_quantize_list(xs, int(world), out, wire, residual.detach(), **rot)
+    args = _mx_quantizer_args("mx_quantize_list", wire, residual, n, xs[0].device, rounding, seed, stream, 0, rot,
+                              rotation_seed)
+    return _C().mx_quantize_list(xs, int(world), out, *args[:5], *args[6:])  # (no index offset)
 
 
 def mx_dequantize_list(w: torch.Tensor, /, outs: Sequence[torch.Tensor], world: int = 1, *,
@@ -402,8 +417,9 @@ def mx_dequantize_list(w: torch.Tensor, /, outs: Sequence[torch.Tensor], world: 
     written where they are: exactly their elements and nothing else. ``rotation``, ``rotation_seed``: those of
     the :func:`mx_quantize_list` that made the wire."""
     outs = _mx_check_list(outs, "mx_dequantize_list")
-    _mx_payload(wire, "mx_dequantize_list")
-    _C().mx_dequantize_list(w, outs, int(world), wire, **_mx_check_rotation(rotation, rotation_seed, "mx_dequantize_list"))
+    _mx_format(wire, "mx_dequantize_list")
+    rot = _mx_check_rotation(rotation, rotation_seed, "mx_dequantize_list")
+    _C().mx_dequantize_list(w, outs, int(world), wire, rot, rotation_seed)
 
 
 def _mx_check_shards(numel: int, world: int, who: str) -> int:
@@ -424,16 +440,12 @@ def mx_quantize_shards(x: torch.Tensor, world: int, out: torch.Tensor | None = N
     ``x``, so it is rounded the same way in both layouts. ``rotation``, ``rotation_seed``: as in
     :func:`mx_quantize`, on the blocks counted from each shard's first element."""
     _mx_check_dtype(x.dtype, "mx_quantize_shards")
-    _mx_payload(wire, "mx_quantize_shards")
+    _mx_format(wire, "mx_quantize_shards")
     _mx_check_shards(x.numel(), world, "mx_quantize_shards")
     rot = _mx_check_rotation(rotation, rotation_seed, "mx_quantize_shards")
-    if _mx_check_rounding(rounding, seed, stream, index_offset, x.numel(), residual, "mx_quantize_shards"):
-        return _C().mx_quantize_shards(x.detach().reshape(-1), int(world), out, wire, None, True, seed, stream,
-                                       index_offset, **rot)
-    if residual is None:
-        return _C().mx_quantize_shards(x.detach().reshape(-1), int(world), out, wire, **rot)
-    _mx_check_residual(residual, x.numel(), x.device, "mx_quantize_shards")
-    return _C().mx_quantize_shards(x.detach().reshape(-1), int(world), out, wire, residual.detach(), **rot)
+    args = _mx_quantizer_args("mx_quantize_shards", wire, residual, x.numel(), x.device, rounding, seed, stream,
+                              index_offset, rot, rotation_seed)
+    return _C().mx_quantize_shards(x.detach().reshape(-1), int(world), out, *args)
 
 
 def mx_dequantize_shards(w: torch.Tensor, /, shard_numel: int, dtype: torch.dtype = torch.float32, world: int = 1,
@@ -442,7 +454,7 @@ def mx_dequantize_shards(w: torch.Tensor, /, shard_numel: int, dtype: torch.dtyp
     """A shard wire ``w`` of ``world`` chunks -> ``world * shard_numel`` elements: chunk ``r`` fills
     ``out[r * m:(r + 1) * m]``, rounded once to the dtype; nothing outside ``out`` is written.
     ``rotation``, ``rotation_seed``: as in :func:`mx_dequantize`."""
-    _mx_payload(wire, "mx_dequantize_shards")
+    _mx_format(wire, "mx_dequantize_shards")
     rot = _mx_check_rotation(rotation, rotation_seed, "mx_dequantize_shards")
     n = int(shard_numel) * int(world)
     if out is None:
@@ -454,7 +466,7 @@ def mx_dequantize_shards(w: torch.Tensor, /, shard_numel: int, dtype: torch.dtyp
             raise ValueError(f"mx_dequantize_shards: out has {out.numel()} elements, {world} shards of "
                              f"{shard_numel} are {n}")
     _mx_check_shards(n, world, "mx_dequantize_shards")
-    _C().mx_dequantize_shards(w, int(world), out, wire, **rot)
+    _C().mx_dequantize_shards(w, int(world), out, wire, rot, rotation_seed)
     return out
 
 
@@ -469,7 +481,7 @@ def mx_fold(w: torch.Tensor, /, nsrc: int, numel: int, dtype: torch.dtype = torc
     and before the rounding."""
     if op not in ("sum", "avg"):
         raise ValueError(f"mx_fold: op must be 'sum' or 'avg', got {op!r}")
-    _mx_payload(wire, "mx_fold")
+    _mx_format(wire, "mx_fold")
     rot = _mx_check_rotation(rotation, rotation_seed, "mx_fold")
     if out is None:
         _mx_check_dtype(dtype, "mx_fold")
@@ -478,7 +490,7 @@ def mx_fold(w: torch.Tensor, /, nsrc: int, numel: int, dtype: torch.dtype = torc
         _mx_check_dtype(out.dtype, "mx_fold")
         if out.numel() != int(numel):
             raise ValueError(f"mx_fold: out has {out.numel()} elements, numel is {numel}")
-    _C().mx_fold(w, int(nsrc), op, out, wire, **rot)
+    _C().mx_fold(w, int(nsrc), op, out, wire, rot, rotation_seed)
     return out
 
 
@@ -487,22 +499,32 @@ def _mx_exp2(e: torch.Tensor) -> torch.Tensor:
     return ((e.to(torch.int32) + 127) << 23).view(torch.float32)
 
 
-def _mx_quantize_blocks(xb: torch.Tensor):
-    """(blocks, 32) f32 -> ((blocks, 32) uint8 payload, (blocks,) uint8 scales), the FP8 contract's Q."""
+def _mx_block_scale(xb: torch.Tensor, fmt: _MxFormat):
+    """The scale rule of every format's Q on (blocks, 32) f32: ``(e, special, zero)`` -- the exponent of a
+    block's scale, and which blocks hold an inf or a NaN or are all zero (their payload is written as zeros)."""
     amax = xb.abs().amax(dim=1)
     special = ~torch.isfinite(xb).all(dim=1)
     zero = (amax == 0) & ~special
     # amax = m 2^k with 1 <= m < 2: frexp returns m / 2 and k + 1 (for a subnormal amax the true
     # exponent, below -126 either way: the clamp decides)
     m, ex = torch.frexp(torch.where(special | zero, torch.ones_like(amax), amax))
-    e = (ex.to(torch.int64) - 1) - 8 + (m > 0.875).to(torch.int64)
-    e = e.clamp(-117, 120)
+    e = ((ex.to(torch.int64) - 1) - fmt.bias + (m > fmt.switch).to(torch.int64)).clamp(fmt.emin, fmt.emax)
     e[zero] = 0
-    q = (xb * _mx_exp2(-e)[:, None]).to(torch.float8_e4m3fn).view(torch.uint8).clone()
-    q[special | zero] = 0
+    return e, special, zero
+
+
+def _mx_scale_bytes(e: torch.Tensor, special: torch.Tensor) -> torch.Tensor:
     s = (e + 127).to(torch.uint8)
     s[special] = 255
-    return q, s
+    return s
+
+
+def _mx_quantize_blocks(xb: torch.Tensor):
+    """(blocks, 32) f32 -> ((blocks, 32) uint8 payload, (blocks,) uint8 scales), the FP8 contract's Q."""
+    e, special, zero = _mx_block_scale(xb, _MX_FORMATS["mxfp8_e4m3"])
+    q = (xb * _mx_exp2(-e)[:, None]).to(torch.float8_e4m3fn).view(torch.uint8).clone()
+    q[special | zero] = 0
+    return q, _mx_scale_bytes(e, special)
 
 
 def _mx_scale_values(s: torch.Tensor) -> torch.Tensor:
@@ -523,13 +545,7 @@ _MX4_VALUES = (0.0, 0.5, 1.0, 1.5, 2.0, 3.0, 4.0, 6.0)  # magnitudes of the e2m1
 
 def _mx4_quantize_blocks(xb: torch.Tensor):
     """(blocks, 32) f32 -> ((blocks, 16) uint8 payload, (blocks,) uint8 scales), the FP4 contract's Q."""
-    amax = xb.abs().amax(dim=1)
-    special = ~torch.isfinite(xb).all(dim=1)
-    zero = (amax == 0) & ~special
-    m, ex = torch.frexp(torch.where(special | zero, torch.ones_like(amax), amax))
-    e = (ex.to(torch.int64) - 1) - 2 + (m > 0.75).to(torch.int64)  # m here is half the contract's m
-    e = e.clamp(-125, 126)
-    e[zero] = 0
+    e, special, zero = _mx_block_scale(xb, _MX_FORMATS["mxfp4_e2m1"])
     a = (xb * _mx_exp2(-e)[:, None]).abs()  # exact, or far below 0.25 where the product is subnormal
     # nearest code, ties to the even one: a midpoint belongs to the even neighbour
     code = ((a > 0.25).to(torch.uint8) + (a >= 0.75).to(torch.uint8) + (a > 1.25).to(torch.uint8)
@@ -537,10 +553,7 @@ def _mx4_quantize_blocks(xb: torch.Tensor):
             + (a > 5.0).to(torch.uint8))
     code = code | (torch.signbit(xb).to(torch.uint8) << 3)
     code[special | zero] = 0
-    q = (code[:, 0::2] | (code[:, 1::2] << 4)).contiguous()
-    s = (e + 127).to(torch.uint8)
-    s[special] = 255
-    return q, s
+    return (code[:, 0::2] | (code[:, 1::2] << 4)).contiguous(), _mx_scale_bytes(e, special)
 
 
 def _mx4_dequantize_blocks(q: torch.Tensor, s: torch.Tensor) -> torch.Tensor:
@@ -568,22 +581,14 @@ def _mx6_unpack(q: torch.Tensor) -> torch.Tensor:
 
 def _mx6_quantize_blocks(xb: torch.Tensor):
     """(blocks, 32) f32 -> ((blocks, 24) uint8 payload, (blocks,) uint8 scales), the FP6 contract's Q."""
-    amax = xb.abs().amax(dim=1)
-    special = ~torch.isfinite(xb).all(dim=1)
-    zero = (amax == 0) & ~special
-    m, ex = torch.frexp(torch.where(special | zero, torch.ones_like(amax), amax))
-    e = (ex.to(torch.int64) - 1) - 2 + (m > 0.9375).to(torch.int64)  # m here is half the contract's m
-    e = e.clamp(-123, 126)
-    e[zero] = 0
+    e, special, zero = _mx_block_scale(xb, _MX_FORMATS["mxfp6_e2m3"])
     # e2m3 is e4m3 with the exponent field cut to two bits: for |s| <= 7.5 the float8_e4m3fn byte of s / 64
     # (nearest even; both products exact, or far below half a grid step where they are subnormal) has bits 5
     # and 6 clear, and the code is its low five bits with its sign in bit 5
     b = ((xb * _mx_exp2(-e)[:, None]) * 0.015625).to(torch.float8_e4m3fn).view(torch.uint8).to(torch.int32)
     code = (b & 31) | ((b >> 7) << 5)
     code[special | zero] = 0
-    s = (e + 127).to(torch.uint8)
-    s[special] = 255
-    return _mx6_pack(code), s
+    return _mx6_pack(code), _mx_scale_bytes(e, special)
 
 
 def _mx6_dequantize_blocks(q: torch.Tensor, s: torch.Tensor) -> torch.Tensor:
@@ -597,11 +602,6 @@ def _mx6_dequantize_blocks(q: torch.Tensor, s: torch.Tensor) -> torch.Tensor:
 
 # ---- stochastic rounding (docs/collectives.md "Stochastic rounding"), integer arithmetic on int64 tensors
 _M32 = 0xFFFFFFFF
-# per payload size: mantissa bits, f32 exponent field of the smallest normal magnitude, the scale rule's
-# (exponent bias, switch point of frexp's mantissa, lower and upper clamp of e)
-_MX_SR_FORMAT = {32: (3, 121, 8, 0.875, -117, 120), 16: (1, 127, 2, 0.75, -125, 126),
-                 24: (3, 127, 2, 0.9375, -123, 126)}
-_MX_SR_SIGN = {32: 7, 16: 3, 24: 5}  # the sign's bit in a code
 
 
 def _mx_sr_mul(x: torch.Tensor, c: int) -> torch.Tensor:
@@ -632,17 +632,12 @@ def _mx_sr_words(key: int, first: int, count: int) -> torch.Tensor:
     return _mx_sr_mix((l & _M32) ^ kh)
 
 
-def _mx_sr_quantize_blocks(xb: torch.Tensor, u: torch.Tensor, pb: int):
+def _mx_sr_quantize_blocks(xb: torch.Tensor, u: torch.Tensor, fmt: _MxFormat):
     """(blocks, 32) f32 and (blocks, 32) words -> (payload, scale bytes): the contract's Q with the payload
     rounded stochastically. The scale is the nearest path's; the code of |s| is that of the grid point below
     it plus one where u < T, T = floor(t 2^32), read off the f32 bits of s."""
-    mb, fmin, bias, switch, emin, emax = _MX_SR_FORMAT[pb]
-    amax = xb.abs().amax(dim=1)
-    special = ~torch.isfinite(xb).all(dim=1)
-    zero = (amax == 0) & ~special
-    m, ex = torch.frexp(torch.where(special | zero, torch.ones_like(amax), amax))
-    e = ((ex.to(torch.int64) - 1) - bias + (m > switch).to(torch.int64)).clamp(emin, emax)
-    e[zero] = 0
+    mb, fmin, pb = fmt.mant, fmt.fmin, fmt.payload
+    e, special, zero = _mx_block_scale(xb, fmt)
     bits = (xb * _mx_exp2(-e)[:, None]).view(torch.int32).to(torch.int64) & _M32  # one f32 product
     a = bits & 0x7FFFFFFF
     field, mant = a >> 23, (a & 0x7FFFFF) | 0x800000
@@ -650,13 +645,11 @@ def _mx_sr_quantize_blocks(xb: torch.Tensor, u: torch.Tensor, pb: int):
     sh = 23 - mb + (fmin - field).clamp(0, 40)
     lo = torch.where(normal, (field - fmin) << mb, torch.zeros_like(a)) + (mant >> sh)
     thr = ((mant & ((torch.ones_like(sh) << sh) - 1)) << 32) >> sh
-    code = (lo + (u < thr).to(torch.int64)) | ((bits >> 31) << _MX_SR_SIGN[pb])
+    code = (lo + (u < thr).to(torch.int64)) | ((bits >> 31) << fmt.sign)
     code[special | zero] = 0
     code = code.to(torch.uint8)
     q = code if pb == 32 else (_mx6_pack(code) if pb == 24 else (code[:, 0::2] | (code[:, 1::2] << 4)).contiguous())
-    s = (e + 127).to(torch.uint8)
-    s[special] = 255
-    return q, s
+    return q, _mx_scale_bytes(e, special)
 
 
 # ---- Hadamard rotation (docs/collectives.md "Hadamard rotation"): f32 tensor operations in the defined order
@@ -688,10 +681,10 @@ def _mx_rot_inverse(db: torch.Tensor, signs: int) -> torch.Tensor:
 
 
 def _mx_blocks_fns(wire: str, who: str):
-    """(payload bytes per block, Q, D) of a format."""
-    pb = _mx_payload(wire, who)
-    return {32: (pb, _mx_quantize_blocks, _mx_dequantize_blocks), 16: (pb, _mx4_quantize_blocks, _mx4_dequantize_blocks),
-            24: (pb, _mx6_quantize_blocks, _mx6_dequantize_blocks)}[pb]
+    """(table row, Q, D) of a format."""
+    fmt = _mx_format(wire, who)
+    return {32: (fmt, _mx_quantize_blocks, _mx_dequantize_blocks), 16: (fmt, _mx4_quantize_blocks, _mx4_dequantize_blocks),
+            24: (fmt, _mx6_quantize_blocks, _mx6_dequantize_blocks)}[fmt.payload]
 
 
 def _mx_split(w: torch.Tensor, nchunks: int, pb: int = 32):
@@ -723,7 +716,7 @@ def mx_quantize_reference(x: torch.Tensor, world: int = 1, *, wire: str = "mxfp8
     ``rounding="stochastic"``: the contract of "Stochastic rounding"; with ``rotation``: the contract of
     "Hadamard rotation", every block rotated before any of that)."""
     _mx_check_dtype(x.dtype, "mx_quantize_reference")
-    pb, Q, D = _mx_blocks_fns(wire, "mx_quantize_reference")
+    fmt, Q, D = _mx_blocks_fns(wire, "mx_quantize_reference")
     world = max(1, int(world))
     flat = x.detach().reshape(-1).to(torch.float32)
     n = flat.numel()
@@ -736,7 +729,7 @@ def mx_quantize_reference(x: torch.Tensor, world: int = 1, *, wire: str = "mxfp8
         xb = _mx_rot_forward(xb.view(total, MX_BLOCK), mx_rotation_signs(rotation_seed)).reshape(-1)
     if sr:
         u = _mx_sr_words(mx_sr_key(seed, stream), index_offset, total * MX_BLOCK)
-        return _mx_join(*_mx_sr_quantize_blocks(xb.view(total, MX_BLOCK), u.view(total, MX_BLOCK), pb), world)
+        return _mx_join(*_mx_sr_quantize_blocks(xb.view(total, MX_BLOCK), u.view(total, MX_BLOCK), fmt), world)
     if residual is not None:  # (one float per element of x: what lies past the end counts as +0 and is dropped)
         _mx_check_residual(residual, n, x.device, "mx_quantize_reference")
         rb = torch.zeros_like(xb)
@@ -755,8 +748,8 @@ def mx_reduce_reference(w: torch.Tensor, /, nsrc: int, op: str = "sum", *, wire:
     ``stream``: as in :func:`mx_reduce`)."""
     if op not in ("sum", "avg"):
         raise ValueError(f"mx_reduce_reference: op must be 'sum' or 'avg', got {op!r}")
-    pb, Q, D = _mx_blocks_fns(wire, "mx_reduce_reference")
-    q, s = _mx_split(w, nsrc, pb)
+    fmt, Q, D = _mx_blocks_fns(wire, "mx_reduce_reference")
+    q, s = _mx_split(w, nsrc, fmt.payload)
     cb = s.numel() // nsrc
     d = D(q, s).view(nsrc, cb, MX_BLOCK)
     acc = d[0].clone()
@@ -766,7 +759,7 @@ def mx_reduce_reference(w: torch.Tensor, /, nsrc: int, op: str = "sum", *, wire:
         acc = acc / torch.tensor(float(nsrc), dtype=torch.float32)
     if _mx_check_rounding(rounding, seed, stream, 0, 0, residual, "mx_reduce_reference"):
         u = _mx_sr_words(mx_sr_key(seed, stream), 0, cb * MX_BLOCK).view(cb, MX_BLOCK)
-        return _mx_join(*_mx_sr_quantize_blocks(acc, u, pb), 1)
+        return _mx_join(*_mx_sr_quantize_blocks(acc, u, fmt), 1)
     if residual is None:
         return _mx_join(*Q(acc), 1)
     _mx_check_residual(residual, cb * MX_BLOCK, w.device, "mx_reduce_reference")
@@ -782,12 +775,12 @@ def mx_dequantize_reference(w: torch.Tensor, /, numel: int, dtype: torch.dtype =
     """Plain-PyTorch :func:`mx_dequantize` on a CPU wire."""
     _mx_check_dtype(dtype, "mx_dequantize_reference")
     rot = _mx_check_rotation(rotation, rotation_seed, "mx_dequantize_reference")
-    pb, _, D = _mx_blocks_fns(wire, "mx_dequantize_reference")
+    fmt, _, D = _mx_blocks_fns(wire, "mx_dequantize_reference")
     world = max(1, int(world))
     if w.numel() != mx_wire_bytes(numel, world, wire=wire):
         raise ValueError(f"the wire of {numel} elements in {world} chunks has "
                          f"{mx_wire_bytes(numel, world, wire=wire)} bytes, got {w.numel()}")
-    q, s = _mx_split(w, world, pb)
+    q, s = _mx_split(w, world, fmt.payload)
     d = D(q, s)
     if rot:
         d = _mx_rot_inverse(d, mx_rotation_signs(rotation_seed))
@@ -836,7 +829,7 @@ def mx_quantize_shards_reference(x: torch.Tensor, world: int, *, wire: str = "mx
     """Plain-PyTorch :func:`mx_quantize_shards` on a CPU tensor (``residual``: updated in place; ``rounding``,
     ``seed``, ``stream``, ``index_offset``, ``rotation``, ``rotation_seed``: as in :func:`mx_quantize_shards`)."""
     _mx_check_dtype(x.dtype, "mx_quantize_shards_reference")
-    _mx_payload(wire, "mx_quantize_shards_reference")
+    _mx_format(wire, "mx_quantize_shards_reference")
     m = _mx_check_shards(x.numel(), world, "mx_quantize_shards_reference")
     flat = x.detach().reshape(-1)
     _mx_check_rotation(rotation, rotation_seed, "mx_quantize_shards_reference")
@@ -864,13 +857,13 @@ def mx_dequantize_shards_reference(w: torch.Tensor, /, shard_numel: int, dtype: 
     """Plain-PyTorch :func:`mx_dequantize_shards` on a CPU wire."""
     _mx_check_dtype(dtype, "mx_dequantize_shards_reference")
     rot = _mx_check_rotation(rotation, rotation_seed, "mx_dequantize_shards_reference")
-    pb, _, D = _mx_blocks_fns(wire, "mx_dequantize_shards_reference")
+    fmt, _, D = _mx_blocks_fns(wire, "mx_dequantize_shards_reference")
     m, world = int(shard_numel), int(world)
     _mx_check_shards(m * world, world, "mx_dequantize_shards_reference")
     if w.numel() != mx_shard_wire_bytes(m, world, wire=wire):
         raise ValueError(f"the wire of {world} shards of {m} elements has "
                          f"{mx_shard_wire_bytes(m, world, wire=wire)} bytes, got {w.numel()}")
-    q, s = _mx_split(w, world, pb)
+    q, s = _mx_split(w, world, fmt.payload)
     d = D(q, s)
     if rot:
         d = _mx_rot_inverse(d, mx_rotation_signs(rotation_seed))
@@ -885,12 +878,12 @@ def mx_fold_reference(w: torch.Tensor, /, nsrc: int, numel: int, dtype: torch.dt
     if op not in ("sum", "avg"):
         raise ValueError(f"mx_fold_reference: op must be 'sum' or 'avg', got {op!r}")
     _mx_check_dtype(dtype, "mx_fold_reference")
-    pb, _, D = _mx_blocks_fns(wire, "mx_fold_reference")
+    fmt, _, D = _mx_blocks_fns(wire, "mx_fold_reference")
     nsrc, numel = int(nsrc), int(numel)
     if numel < 1 or w.numel() != mx_shard_wire_bytes(numel, nsrc, wire=wire):
         raise ValueError(f"{nsrc} chunk wires of {numel} elements have "
                          f"{mx_shard_wire_bytes(numel, nsrc, wire=wire)} bytes, got {w.numel()}")
-    q, s = _mx_split(w, nsrc, pb)
+    q, s = _mx_split(w, nsrc, fmt.payload)
     d = D(q, s).view(nsrc, -1)
     acc = d[0].clone()
     for r in range(1, nsrc):

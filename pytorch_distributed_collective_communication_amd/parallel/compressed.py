@@ -55,7 +55,7 @@ import torch.distributed as dist
 
 from .. import ops
 
-WIRES = ("mxfp8_e4m3", "mxfp4_e2m1", "mxfp6_e2m3")
+WIRES, ROUNDINGS, ROTATIONS = ops.MX_WIRES, ops.MX_ROUNDINGS, ops.MX_ROTATIONS  # (the names ddp.py and zero.py import)
 MAX_GPU_WORLD = 8  # ops.mx_reduce folds up to 8 sources (one xGMI node)
 
 _side_streams = {}
@@ -87,46 +87,49 @@ def _op_name(op) -> str:
     return None
 
 
-def _sequence(tensor, opn, group, world, quantize, reduce, dequantize):
-    n = tensor.numel()
-    wire = quantize(tensor, world)
-    recv = torch.empty_like(wire)
-    dist.all_to_all_single(recv, wire, group=group)  # chunk r of every rank -> rank r, in rank order
-    mine = reduce(recv, world, opn)
-    dist.all_gather_into_tensor(wire, mine, group=group)
-    dequantize(wire, n, world)
+def _dequantize_into(w, tensor, world, **kw):
+    ops.mx_dequantize(w, tensor.numel(), tensor.dtype, world, out=tensor, **kw)
 
 
-def _run_gpu(tensor, opn, group, world, wire, residual=None, owner_residual=None, sr=({}, {}), rot={}):
-    _sequence(tensor, opn, group, world,
-              lambda x, W: ops.mx_quantize(x, W, wire=wire, residual=residual, **sr[0], **rot),
-              lambda w, W, o: ops.mx_reduce(w, W, o, wire=wire, residual=owner_residual, **sr[1]),
-              lambda w, n, W: ops.mx_dequantize(w, n, tensor.dtype, W, out=tensor, wire=wire, **rot))
+def _dequantize_into_cpu(w, tensor, world, **kw):
+    tensor.copy_(ops.mx_dequantize_reference(w, tensor.numel(), tensor.dtype, world, **kw).view_as(tensor))
 
 
-def _run_cpu(tensor, opn, group, world, wire, residual=None, owner_residual=None, sr=({}, {}), rot={}):
-    def store(w, n, W):
-        tensor.copy_(ops.mx_dequantize_reference(w, n, tensor.dtype, W, wire=wire, **rot).view_as(tensor))
+# (quantize, reduce, dequantize into the data) by (a list of tensors?, on the GPU?); the CPU runs the
+# plain-PyTorch references of the kernels
+_ALL_REDUCE_OPS = {
+    (False, True): (ops.mx_quantize, ops.mx_reduce, _dequantize_into),
+    (False, False): (ops.mx_quantize_reference, ops.mx_reduce_reference, _dequantize_into_cpu),
+    (True, True): (ops.mx_quantize_list, ops.mx_reduce, ops.mx_dequantize_list),
+    (True, False): (ops.mx_quantize_list_reference, ops.mx_reduce_reference, ops.mx_dequantize_list_reference),
+}
 
-    _sequence(tensor, opn, group, world,
-              lambda x, W: ops.mx_quantize_reference(x, W, wire=wire, residual=residual, **sr[0], **rot),
-              lambda w, W, o: ops.mx_reduce_reference(w, W, o, wire=wire, residual=owner_residual, **sr[1]), store)
+
+def _all_reduce_sequence(data, gpu, opn, group, world, wire, residual, owner_residual, sr, rot):
+    """The all-reduce of ``data``, a tensor or a list of tensors, in place."""
+    quantize, reduce, dequantize = _ALL_REDUCE_OPS[isinstance(data, list), gpu]
+    w = quantize(data, world, wire=wire, residual=residual, **sr[0], **rot)
+    recv = torch.empty_like(w)
+    dist.all_to_all_single(recv, w, group=group)  # chunk r of every rank -> rank r, in rank order
+    mine = reduce(recv, world, opn, wire=wire, residual=owner_residual, **sr[1])
+    dist.all_gather_into_tensor(w, mine, group=group)
+    dequantize(w, data, world, wire=wire, **rot)
 
 
-ROUNDINGS = ("nearest", "stochastic")
+def _all_reduce_issue(data, tensors, async_op, *args):
+    """:func:`_all_reduce_sequence` on the CPU, or issued on the GPU; ``tensors``: what the call keeps alive."""
+    if not tensors[0].is_cuda:
+        with torch.no_grad():
+            _all_reduce_sequence(data, False, *args)
+        return _done(async_op)
+    return _issue_gpu(lambda: _all_reduce_sequence(data, True, *args), tensors, async_op)
 
 
 def _rounding_args(who, rounding, seed, group, residuals=()):
     """The rounding arguments of a collective, checked before any communication. Returns the keywords of this
     rank's quantization and of its requantization: none for ``"nearest"`` (the plain calls), else the seed
     with the streams ``2 rank`` and ``2 rank + 1``."""
-    if not isinstance(rounding, str) or rounding not in ROUNDINGS:
-        raise ValueError(f"{who}: unknown rounding {rounding!r} (supported: {', '.join(ROUNDINGS)})")
-    if isinstance(seed, bool) or not isinstance(seed, int):
-        raise TypeError(f"{who}: seed must be an int, got {type(seed).__name__}")
-    if not 0 <= seed < 1 << 64:
-        raise ValueError(f"{who}: seed must be in [0, 2^64), got {seed}")
-    if rounding == "nearest":
+    if not ops._mx_check_rounding(rounding, seed, 0, 0, 0, None, who):  # (the rounding's name and the seed)
         return {}, {}
     if any(r is not None for r in residuals):
         raise ValueError(f"{who}: rounding='stochastic' and a residual are alternatives, not both")
@@ -135,37 +138,15 @@ def _rounding_args(who, rounding, seed, group, residuals=()):
             dict(rounding=rounding, seed=seed, stream=2 * rank + 1))
 
 
-ROTATIONS = ("hadamard",)
-
-
 def _rotation_args(who, rotation, rotation_seed):
     """The rotation arguments of a collective, checked before any communication. Returns the keywords of the
     kernels that touch the tensor: none for ``None`` (the plain calls)."""
-    if rotation is not None and (not isinstance(rotation, str) or rotation not in ROTATIONS):
-        raise ValueError(f"{who}: unknown rotation {rotation!r} (supported: None, {', '.join(ROTATIONS)})")
-    if isinstance(rotation_seed, bool) or not isinstance(rotation_seed, int):
-        raise TypeError(f"{who}: rotation_seed must be an int, got {type(rotation_seed).__name__}")
-    if not 0 <= rotation_seed < 1 << 64:
-        raise ValueError(f"{who}: rotation_seed must be in [0, 2^64), got {rotation_seed}")
-    return {} if rotation is None else dict(rotation=rotation, rotation_seed=rotation_seed)
+    return dict(rotation=rotation, rotation_seed=rotation_seed) if ops._mx_check_rotation(rotation, rotation_seed, who) else {}
 
 
 def _check_residual(who, name, res, numel, device):
-    """An error-feedback residual, checked before any communication: float32, ``numel`` elements, on the
-    tensor's device, contiguous and 16-byte aligned (it is updated in place, so it cannot be copied)."""
-    if res is None:
-        return
-    if not isinstance(res, torch.Tensor) or res.dtype != torch.float32:
-        raise TypeError(f"{who}: {name} must be a float32 tensor, got "
-                        f"{res.dtype if isinstance(res, torch.Tensor) else type(res).__name__}")
-    if res.numel() != numel:
-        raise ValueError(f"{who}: {name} has {res.numel()} elements, {numel} expected")
-    if res.device != device:
-        raise ValueError(f"{who}: {name} is on {res.device}, the tensor on {device}")
-    if not res.is_contiguous():
-        raise ValueError(f"{who}: {name} must be contiguous")
-    if res.data_ptr() % 16:
-        raise ValueError(f"{who}: {name} must be 16-byte aligned")
+    """An error-feedback residual, checked before any communication (``ops._mx_check_residual``)."""
+    ops._mx_check_residual(res, numel, device, who, name, "tensor")
 
 
 def all_reduce_compressed(tensor: torch.Tensor, op=dist.ReduceOp.SUM, group=None, wire: str = "mxfp8_e4m3",
@@ -222,16 +203,11 @@ def all_reduce_compressed(tensor: torch.Tensor, op=dist.ReduceOp.SUM, group=None
     sr = _rounding_args("all_reduce_compressed", rounding, seed, group, (residual, owner_residual))
     rot = _rotation_args("all_reduce_compressed", rotation, rotation_seed)
     if world == 1 or tensor.numel() == 0:
-        return CompressedWork() if async_op else None
-    if not tensor.is_cuda:
-        with torch.no_grad():
-            _run_cpu(tensor, opn, group, world, wire, residual, owner_residual, sr, rot)
-        return CompressedWork() if async_op else None
-    if world > MAX_GPU_WORLD:
+        return _done(async_op)
+    if tensor.is_cuda and world > MAX_GPU_WORLD:
         raise ValueError(f"all_reduce_compressed: GPU groups of up to {MAX_GPU_WORLD} ranks, got {world}")
     held = tuple(t for t in (tensor, residual, owner_residual) if t is not None)
-    return _issue_gpu(lambda: _run_gpu(tensor, opn, group, world, wire, residual, owner_residual, sr, rot), held,
-                      async_op)
+    return _all_reduce_issue(tensor, held, async_op, opn, group, world, wire, residual, owner_residual, sr, rot)
 
 
 def _all_reduce_list(xs, opn, group, wire, async_op, residual, owner_residual, rounding, seed, rotation,
@@ -257,26 +233,10 @@ def _all_reduce_list(xs, opn, group, wire, async_op, residual, owner_residual, r
     rot = _rotation_args(who, rotation, rotation_seed)
     if world == 1 or n == 0:
         return _done(async_op)
-    gpu = xs[0].is_cuda
-    if gpu and world > MAX_GPU_WORLD:
+    if xs[0].is_cuda and world > MAX_GPU_WORLD:
         raise ValueError(f"{who}: GPU groups of up to {MAX_GPU_WORLD} ranks, got {world}")
-    quantize, reduce, dequantize = ((ops.mx_quantize_list, ops.mx_reduce, ops.mx_dequantize_list) if gpu else
-                                    (ops.mx_quantize_list_reference, ops.mx_reduce_reference,
-                                     ops.mx_dequantize_list_reference))
-
-    def run():
-        w = quantize(xs, world, wire=wire, residual=residual, **sr[0], **rot)
-        recv = torch.empty_like(w)
-        dist.all_to_all_single(recv, w, group=group)  # chunk r of every rank -> rank r, in rank order
-        mine = reduce(recv, world, opn, wire=wire, residual=owner_residual, **sr[1])
-        dist.all_gather_into_tensor(w, mine, group=group)
-        dequantize(w, xs, world, wire=wire, **rot)
-
-    if not gpu:
-        with torch.no_grad():
-            run()
-        return _done(async_op)
-    return _issue_gpu(run, tuple(xs) + tuple(t for t in (residual, owner_residual) if t is not None), async_op)
+    held = tuple(xs) + tuple(t for t in (residual, owner_residual) if t is not None)
+    return _all_reduce_issue(xs, held, async_op, opn, group, world, wire, residual, owner_residual, sr, rot)
 
 
 def _issue_gpu(run, tensors, async_op):
