@@ -408,6 +408,42 @@ void clip_scale(const at::Tensor& src, const at::Tensor& total, double max_norm,
   TORCH_CHECK(e == hipSuccess, who, " launch failed: ", hipGetErrorString(e));
 }
 
+// ---- fused AdamW step (kernels/adamw.hip, docs/collectives.md "Fused AdamW step"). `args`: the eight scalars of
+// kern::AdamWArgs in its order, computed by the caller in f64; each is rounded to f32 here, once.
+void adamw_step(const at::Tensor& grad, at::Tensor& master, at::Tensor& exp_avg, at::Tensor& exp_avg_sq,
+                const std::vector<double>& args, const c10::optional<at::Tensor>& param_out,
+                const c10::optional<at::Tensor>& total, double max_norm, int max_blocks) {
+  const char* who = "adamw_step";
+  TORCH_CHECK(grad.is_cuda(), who, ": GPU tensors only");
+  const at::Device dev = grad.device();
+  const auto gd = clip_dtype(grad, who);
+  TORCH_CHECK_VALUE(args.size() == 8, who, ": eight scalars expected, got ", args.size());
+  for (const at::Tensor* t : {&master, &exp_avg, &exp_avg_sq})
+    TORCH_CHECK_VALUE(t->scalar_type() == at::kFloat && t->device() == dev && t->numel() == grad.numel() &&
+                          t->is_contiguous(),
+                      who, ": master, exp_avg and exp_avg_sq must be contiguous float32 tensors of ", grad.numel(),
+                      " elements on ", dev);
+  TORCH_CHECK_VALUE(grad.is_contiguous(), who, ": grad must be contiguous");
+  auto pd = pdcc::kern::DType::F32;
+  if (param_out) {
+    pd = clip_dtype(*param_out, who);
+    TORCH_CHECK_VALUE(param_out->device() == dev && param_out->numel() == grad.numel() && param_out->is_contiguous(),
+                      who, ": param_out must be contiguous and hold ", grad.numel(), " elements on ", dev);
+    TORCH_CHECK_VALUE(pd == pdcc::kern::DType::F32 || pd == gd, who, ": param_out must be float32 or of grad's dtype, got ",
+                      param_out->scalar_type(), " for ", grad.scalar_type());
+  }
+  if (total) clip_check_total(*total, dev, who, "total");
+  const pdcc::kern::AdamWArgs a{(float)args[0], (float)args[1], (float)args[2], (float)args[3],
+                                (float)args[4], (float)args[5], (float)args[6], (float)args[7]};
+  c10::hip::HIPGuardMasqueradingAsCUDA g(dev);
+  hipStream_t s = c10::hip::getCurrentHIPStreamMasqueradingAsCUDA(dev.index()).stream();
+  hipError_t e = pdcc::kern::adamw_step(grad.data_ptr(), gd, master.data_ptr<float>(), exp_avg.data_ptr<float>(),
+                                        exp_avg_sq.data_ptr<float>(), param_out ? param_out->data_ptr() : nullptr, pd,
+                                        (size_t)grad.numel(), a, total ? total->data_ptr<double>() : nullptr,
+                                        (float)max_norm, s, max_blocks);
+  TORCH_CHECK(e == hipSuccess, who, " launch failed: ", hipGetErrorString(e));
+}
+
 // Peer links between every pair of visible GPUs, as the runtime reports them: HSA link
 // type (xGMI on an MI355X node, PCIe otherwise), hop count, P2P access / atomics and
 // the runtime's relative performance rank. Local queries only (no collective).
@@ -615,6 +651,12 @@ PYBIND11_MODULE(_C, m) {
         "out = src * min(1, max_norm / (sqrt(total) + 1e-6)) in f32, rounded once; the float64 total is read on the GPU");
   m.attr("SUMSQ_TILE") = pdcc::kern::kSumsqTile;
   m.attr("SUMSQ_CHAIN") = pdcc::kern::kSumsqChain;
+  m.def("adamw_step", &adamw_step, py::arg("grad"), py::arg("master"), py::arg("exp_avg"), py::arg("exp_avg_sq"),
+        py::arg("args"), py::arg("param_out") = py::none(), py::arg("total") = py::none(), py::arg("max_norm") = 0.0,
+        py::arg("max_blocks") = 0,
+        "one fused AdamW step on f32 master / exp_avg / exp_avg_sq in place from an f32 / bf16 / f16 gradient, with the "
+        "clip coefficient from the float64 total (read on the GPU) and the new master rounded once into param_out");
+  m.attr("ADAMW_SPAN") = (int64_t)pdcc::kern::kAdamWSpan;
   m.def("ipc_signal_bytes", &pdcc::kern::ipc_signal_bytes);
   m.def("device_links", &device_links,
         "peer links between every pair of visible GPUs: link type (xgmi/pcie), hops, p2p, atomics, perf_rank");

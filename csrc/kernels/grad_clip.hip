@@ -37,7 +37,7 @@
 // the end is masked element by element in both.
 #include <algorithm>
 
-#include "dev_common.h"
+#include "group_io.h"
 
 namespace pdcc {
 namespace dev {
@@ -46,68 +46,6 @@ namespace {
 
 constexpr int kT = kern::kSumsqTile;
 static_assert(kT == kern::kBlockThreads * 32 && kern::kSumsqChain == 32 + 6, "a lane's chain is 32 elements");
-
-typedef unsigned int v4u __attribute__((ext_vector_type(4)));
-typedef unsigned int v2u __attribute__((ext_vector_type(2)));
-
-template <DType DT>
-__device__ __forceinline__ float widen_bits(uint32_t b) {
-  if constexpr (DT == DType::BF16) return bf16_to_f32((uint16_t)b);
-  else return (float)__builtin_bit_cast(_Float16, (uint16_t)b);
-}
-template <DType DT>
-__device__ __forceinline__ uint32_t narrow_bits(float f) {
-  if constexpr (DT == DType::BF16) return f32_to_bf16(f);
-  else return __builtin_bit_cast(uint16_t, (_Float16)f);
-}
-
-// N elements of DT from N * sizeof(element) bytes (8 or 16, so aligned), non-temporal
-template <DType DT, int N>
-__device__ __forceinline__ void load_group(const char* p, float* f) {
-  constexpr int kBytes = N * (int)sizeof(typename Tr<DT>::S);
-  static_assert(kBytes == 8 || kBytes == 16, "a group is one 8- or 16-byte access");
-  uint32_t w[kBytes / 4];
-  if constexpr (kBytes == 16) {
-    const v4u x = __builtin_nontemporal_load(reinterpret_cast<const v4u*>(p));
-    w[0] = x[0], w[1] = x[1], w[2] = x[2], w[3] = x[3];
-  } else {
-    const v2u x = __builtin_nontemporal_load(reinterpret_cast<const v2u*>(p));
-    w[0] = x[0], w[1] = x[1];
-  }
-#pragma unroll
-  for (int i = 0; i < kBytes / 4; ++i) {
-    if constexpr (DT == DType::F32) f[i] = __uint_as_float(w[i]);
-    else f[2 * i] = widen_bits<DT>(w[i] & 0xffffu), f[2 * i + 1] = widen_bits<DT>(w[i] >> 16);
-  }
-}
-
-template <DType DT, int N>
-__device__ __forceinline__ void store_group(char* p, const float* f) {
-  constexpr int kBytes = N * (int)sizeof(typename Tr<DT>::S);
-  static_assert(kBytes == 16, "the output side of a group is 16 bytes");
-  v4u x;
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    if constexpr (DT == DType::F32) x[i] = __float_as_uint(f[i]);
-    else x[i] = narrow_bits<DT>(f[2 * i]) | (narrow_bits<DT>(f[2 * i + 1]) << 16);
-  }
-  *reinterpret_cast<v4u*>(p) = x;
-}
-
-// elements [i, i + N) of the tensor, those at or past `numel` as +0 and never read
-template <DType DT, int N>
-__device__ __forceinline__ void load_elems(const char* base, size_t i, size_t numel, float* f) {
-  using S = typename Tr<DT>::S;
-#pragma unroll
-  for (int j = 0; j < N; ++j) f[j] = i + j < numel ? Tr<DT>::in(reinterpret_cast<const S*>(base)[i + j]) : 0.0f;
-}
-template <DType DT, int N>
-__device__ __forceinline__ void store_elems(char* base, size_t i, size_t numel, const float* f) {
-  using S = typename Tr<DT>::S;
-#pragma unroll
-  for (int j = 0; j < N; ++j)
-    if (i + j < numel) reinterpret_cast<S*>(base)[i + j] = Tr<DT>::out(f[j]);
-}
 
 // x + (the DPP-selected lane's x); rows the mask leaves out add +0
 template <int CTRL, int ROWS = 0xf>
@@ -185,14 +123,6 @@ __global__ __launch_bounds__(256) void k_sumsq_fold(const double* __restrict__ p
     __syncthreads();
   }
   if (lane == 0) out[0] = s[0];
-}
-
-// torch.nn.utils.clip_grad_norm_'s coefficient, in f32 from the f64 total; a NaN stays a NaN
-__device__ __forceinline__ float clip_coef(const double* total, float max_norm) {
-#pragma clang fp contract(off)
-  const float norm = (float)sqrt(*total);
-  const float c = max_norm / (norm + 1e-6f);
-  return (c < 1.0f || c != c) ? c : 1.0f;
 }
 
 constexpr int kClipUnroll = 4;  // independent groups in flight per lane

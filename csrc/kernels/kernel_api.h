@@ -415,5 +415,29 @@ hipError_t sumsq(const SumsqTensor* ts, size_t k, double* partials, double* out,
 hipError_t clip_scale(const void* src, DType st, const double* total, float max_norm, void* out, DType ot,
                       size_t numel, hipStream_t stream);
 
+// ---------------------------------------------------------------- fused AdamW step (adamw.hip)
+// Contract: docs/collectives.md "Fused AdamW step". A single-GPU kernel on the caller's stream.
+// The eight scalars of one step, each computed in f64 on the host and rounded once to f32.
+struct AdamWArgs {
+  float beta1, one_minus_beta1;  // b1, 1 - b1
+  float beta2, one_minus_beta2;  // b2, 1 - b2
+  float decay;                   // 1 - lr * weight_decay
+  float step_size;               // lr / (1 - b1^step)
+  float inv_sqrt_bc2;            // 1 / sqrt(1 - b2^step)
+  float eps;
+};
+constexpr int kAdamWUnroll = 4;  // independent groups of four elements in flight per lane
+// elements one workgroup takes per trip of its grid-stride loop
+constexpr size_t kAdamWSpan = (size_t)256 * kAdamWUnroll * 4;
+// For i < numel, in f32 without contraction: g = (float)grad[i] * coef; m = b1 m + (1 - b1) g;
+// v = b2 v + (1 - b2) (g g); p = p decay; p = p - step_size (m / (sqrt(v) inv_sqrt_bc2 + eps)); m, v, p written
+// back in place and, with `param_out`, p rounded once to `pt` (F32 or `gt`). coef = 1 when `total` is null, else
+// clip_scale's, read on the device. `gt`: F32, BF16 or F16. Any alignment of the element size on every side (all
+// sides vector-aligned: 16-byte f32 and 8-byte 16-bit accesses; otherwise element by element, the same bits).
+// The five buffers do not overlap. `max_blocks` caps the grid (0: default).
+hipError_t adamw_step(const void* grad, DType gt, float* master, float* exp_avg, float* exp_avg_sq, void* param_out,
+                      DType pt, size_t numel, const AdamWArgs& a, const double* total, float max_norm,
+                      hipStream_t stream, int max_blocks = 0);
+
 }  // namespace kern
 }  // namespace pdcc

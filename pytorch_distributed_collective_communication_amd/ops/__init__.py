@@ -37,6 +37,8 @@
 * :func:`sumsq`, :func:`clip_scale` -- gradient clipping by global norm (docs/collectives.md "Gradient
   clipping"): a deterministic f64 sum of squares of a tensor list, and the cast that multiplies by the clip
   coefficient it computes on the device from that sum; ``ShardedOptimizer(max_grad_norm=...)``.
+* :func:`adamw_step` -- one AdamW step on a shard in one pass: gradient, clip coefficient, f32 state and the
+  parameter cast (docs/collectives.md "Fused AdamW step"); ``ShardedOptimizer(params, "adamw")``.
 
 Every function runs on the current HIP stream and raises if the native
 extension is missing (no silent eager fallback). ``*_reference`` functions are
@@ -44,6 +46,7 @@ the plain-PyTorch fp32 references the tests compare against.
 """
 from __future__ import annotations
 
+import math
 from typing import NamedTuple, Sequence
 
 import torch
@@ -961,15 +964,19 @@ def _clip_check_scale(src, total, max_norm, out, who: str) -> torch.Tensor:
     return out
 
 
+def _clip_coef(total: torch.Tensor, max_norm: float) -> torch.Tensor:
+    """The coefficient as a 0-d f32 tensor on ``total``'s device: f32 operations from the f64 total on."""
+    norm = total.detach().reshape(()).sqrt().to(torch.float32)
+    c = torch.tensor(float(max_norm), dtype=torch.float32, device=total.device) / (norm + 1e-6)
+    return torch.clamp(c, max=1.0)  # (a NaN stays a NaN)
+
+
 def clip_scale_reference(src: torch.Tensor, total: torch.Tensor, max_norm: float,
                          out: torch.Tensor | None = None) -> torch.Tensor:
     """Plain-PyTorch :func:`clip_scale`: the coefficient of ``torch.nn.utils.clip_grad_norm_`` in f32 from the f64
     ``total``, one f32 product per element, one rounding to ``out``'s dtype."""
     out = _clip_check_scale(src, total, max_norm, out, "clip_scale_reference")
-    norm = total.detach().reshape(()).sqrt().to(torch.float32)
-    c = torch.tensor(float(max_norm), dtype=torch.float32, device=src.device) / (norm + 1e-6)
-    coef = torch.clamp(c, max=1.0)  # (a NaN stays a NaN)
-    return out.copy_((src.detach().to(torch.float32) * coef).view_as(out))
+    return out.copy_((src.detach().to(torch.float32) * _clip_coef(total, max_norm)).view_as(out))
 
 
 def clip_scale(src: torch.Tensor, total: torch.Tensor, max_norm: float, out: torch.Tensor | None = None) -> torch.Tensor:
@@ -988,8 +995,92 @@ def clip_scale(src: torch.Tensor, total: torch.Tensor, max_norm: float, out: tor
     return out
 
 
+# ------------------------------------------ fused AdamW step (docs/collectives.md "Fused AdamW step")
+ADAMW_SPAN = 4096  # elements a workgroup takes per trip of its grid-stride loop (kernel_api.h kAdamWSpan)
+
+
+def _adamw_scalars(lr, betas, eps, weight_decay, step) -> tuple:
+    """The eight scalars of one step as Python floats (f64), in kern::AdamWArgs' order: b1, 1 - b1, b2, 1 - b2,
+    1 - lr wd, lr / (1 - b1^step), 1 / sqrt(1 - b2^step), eps. The kernel's binding and the reference round each
+    to f32 once."""
+    lr, (b1, b2), eps, wd, step = float(lr), (float(b) for b in betas), float(eps), float(weight_decay), int(step)
+    if step < 1 or not (0.0 <= b1 < 1.0 and 0.0 <= b2 < 1.0):
+        raise ValueError(f"adamw_step: step >= 1 and betas in [0, 1) expected, got step {step}, betas ({b1}, {b2})")
+    return (b1, 1.0 - b1, b2, 1.0 - b2, 1.0 - lr * wd, lr / (1.0 - b1 ** step), 1.0 / math.sqrt(1.0 - b2 ** step), eps)
+
+
+def _adamw_check(grad, master, exp_avg, exp_avg_sq, param_out, total, max_norm, who: str) -> None:
+    if not isinstance(grad, torch.Tensor) or grad.dtype not in CLIP_DTYPES:
+        raise ValueError(f"{who}: grad must be a float32, bfloat16 or float16 tensor")
+    for name, t in (("master", master), ("exp_avg", exp_avg), ("exp_avg_sq", exp_avg_sq)):
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or t.numel() != grad.numel() \
+                or t.device != grad.device:
+            raise ValueError(f"{who}: {name} must hold {grad.numel()} float32 elements on {grad.device}")
+    if param_out is not None and (param_out.dtype not in (torch.float32, grad.dtype)
+                                  or param_out.numel() != grad.numel() or param_out.device != grad.device):
+        raise ValueError(f"{who}: param_out must hold {grad.numel()} float32 or {grad.dtype} elements on {grad.device}")
+    if (total is None) != (max_norm is None):
+        raise ValueError(f"{who}: total and max_norm come together or not at all")
+    if total is not None:
+        _clip_check_total(total, grad.device, who, "total")
+        float(max_norm)
+
+
+def adamw_step_reference(grad: torch.Tensor, master: torch.Tensor, exp_avg: torch.Tensor, exp_avg_sq: torch.Tensor, *,
+                         lr: float, betas, eps: float, weight_decay: float, step: int,
+                         param_out: torch.Tensor | None = None, total: torch.Tensor | None = None,
+                         max_norm: float | None = None) -> None:
+    """Plain-PyTorch :func:`adamw_step`: the same sequence, one f32 operation per rounding, the scalars of the same
+    function rounded to f32 once."""
+    _adamw_check(grad, master, exp_avg, exp_avg_sq, param_out, total, max_norm, "adamw_step_reference")
+    b1, omb1, b2, omb2, decay, step_size, inv_sqrt_bc2, e = (
+        torch.tensor(x, dtype=torch.float32, device=grad.device) for x in _adamw_scalars(lr, betas, eps, weight_decay, step))
+    g = grad.detach().to(torch.float32).reshape(-1)
+    if total is not None:
+        g = g * _clip_coef(total, max_norm)
+    m = b1 * exp_avg.detach().reshape(-1) + omb1 * g
+    v = b2 * exp_avg_sq.detach().reshape(-1) + omb2 * (g * g)
+    p = master.detach().reshape(-1) * decay
+    p = p - step_size * (m / (v.sqrt() * inv_sqrt_bc2 + e))
+    for dst, src in ((exp_avg, m), (exp_avg_sq, v), (master, p)) + (() if param_out is None else ((param_out, p),)):
+        dst.detach().copy_(src.view_as(dst))
+
+
+def adamw_step(grad: torch.Tensor, master: torch.Tensor, exp_avg: torch.Tensor, exp_avg_sq: torch.Tensor, *,
+               lr: float, betas, eps: float, weight_decay: float, step: int, param_out: torch.Tensor | None = None,
+               total: torch.Tensor | None = None, max_norm: float | None = None, max_blocks: int = 0) -> None:
+    """One AdamW step (decoupled weight decay, torch's formula) on the float32 ``master``, ``exp_avg`` and
+    ``exp_avg_sq`` in place, from a float32 / bfloat16 / float16 ``grad`` read once; ``step`` counts from 1.
+
+    Per element, in f32 without contraction (docs/collectives.md "Fused AdamW step")::
+
+        g = float(grad) * coef
+        m = b1 * m + (1 - b1) * g
+        v = b2 * v + (1 - b2) * (g * g)
+        p = p * (1 - lr * wd)
+        p = p - lr / (1 - b1^step) * (m / (sqrt(v) / sqrt(1 - b2^step) + eps))
+
+    ``coef`` is 1, or with ``total`` (the float64 one-element sum of squares of :func:`sumsq`) and ``max_norm`` the
+    coefficient of :func:`clip_scale`, evaluated on the device. ``param_out`` (float32 or ``grad``'s dtype) receives
+    the new master rounded once. NaN and inf propagate as the arithmetic gives them. On the GPU this is one kernel
+    and one pass (contiguous tensors, any alignment, no overlap between the five buffers; ``max_blocks`` caps the
+    grid); CPU tensors: :func:`adamw_step_reference`."""
+    _adamw_check(grad, master, exp_avg, exp_avg_sq, param_out, total, max_norm, "adamw_step")
+    if grad.device.type == "cpu":
+        return adamw_step_reference(grad, master, exp_avg, exp_avg_sq, lr=lr, betas=betas, eps=eps,
+                                    weight_decay=weight_decay, step=step, param_out=param_out, total=total,
+                                    max_norm=max_norm)
+    if not all(t.is_contiguous() for t in (grad, master, exp_avg, exp_avg_sq) + (() if param_out is None else (param_out,))):
+        raise ValueError("adamw_step: the tensors must be contiguous")
+    _C().adamw_step(grad.detach(), master.detach(), exp_avg.detach(), exp_avg_sq.detach(),
+                    list(_adamw_scalars(lr, betas, eps, weight_decay, step)),
+                    None if param_out is None else param_out.detach(), None if total is None else total.detach(),
+                    0.0 if max_norm is None else float(max_norm), int(max_blocks))
+
+
 __all__ = ["reduce_nway", "reduce_nway_reference", "multi_copy", "pack", "unpack",
            "sumsq", "clip_scale", "sumsq_reference", "clip_scale_reference",
+           "adamw_step", "adamw_step_reference",
            "MX_WIRES", "MX_ROUNDINGS", "MX_ROTATIONS", "mx_sr_key", "mx_rotation_signs",
            "mx_quantize", "mx_reduce", "mx_dequantize", "mx_chunk_blocks", "mx_wire_bytes",
            "mx_owner_residual_numel",

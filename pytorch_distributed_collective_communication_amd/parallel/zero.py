@@ -174,6 +174,67 @@ class _FlatSpace:
             p.grad = view.view_as(p)
 
 
+class _FusedAdamW:
+    """The built-in step of ``ShardedOptimizer(params, "adamw")``: per space ``exp_avg`` / ``exp_avg_sq`` f32 shards,
+    one step counter, one parameter group read at every step, and ``ops.adamw_step`` -- one pass over the gradient
+    shard, the state and the master that also writes ``param_shard`` (docs/collectives.md "Fused AdamW step").
+    ``state`` / ``param_groups`` / ``state_dict()`` / ``load_state_dict()`` are those of ``torch.optim.AdamW`` over
+    the masters, one parameter per space, so checkpoints go either way."""
+
+    DEFAULTS = dict(lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2)
+    # what torch.optim.AdamW writes next to them, and the only values this step implements
+    TORCH_FLAGS = dict(amsgrad=False, maximize=False, foreach=None, capturable=False, differentiable=False, fused=None,
+                       decoupled_weight_decay=True)
+
+    def __init__(self, spaces, **kw):
+        unknown = sorted(set(kw) - set(self.DEFAULTS))
+        if unknown:
+            raise ValueError(f"ShardedOptimizer: 'adamw' takes {', '.join(self.DEFAULTS)}, got {', '.join(unknown)}")
+        for s in spaces:
+            if s.dtype not in (torch.float32, torch.bfloat16, torch.float16) or s.master.dtype != torch.float32:
+                raise ValueError(f"ShardedOptimizer: 'adamw' steps float32, bfloat16 and float16 parameters on a float32 "
+                                 f"master, got {s.dtype} parameters with a {s.master.dtype} master")
+        self.param_groups = [{**self.DEFAULTS, **kw}]
+        self.state = {i: {"exp_avg": torch.zeros_like(s.master), "exp_avg_sq": torch.zeros_like(s.master)}
+                      for i, s in enumerate(spaces)}
+        self.steps = 0
+
+    def step(self, spaces, total, max_norm) -> None:
+        from .. import ops
+
+        g = self.param_groups[0]
+        self.steps += 1
+        for i, s in enumerate(spaces):
+            ops.adamw_step(s.grad_shard, s.master, self.state[i]["exp_avg"], self.state[i]["exp_avg_sq"], lr=g["lr"],
+                           betas=g["betas"], eps=g["eps"], weight_decay=g["weight_decay"], step=self.steps,
+                           param_out=s.param_shard, total=total, max_norm=None if total is None else max_norm)
+
+    def state_dict(self) -> dict:
+        state = {i: {"step": torch.tensor(float(self.steps)), **st} for i, st in self.state.items()} if self.steps else {}
+        return {"state": state,
+                "param_groups": [{**self.param_groups[0], **self.TORCH_FLAGS, "params": list(range(len(self.state)))}]}
+
+    def load_state_dict(self, sd: dict) -> None:
+        (group,) = sd["param_groups"]
+        if len(group["params"]) != len(self.state):
+            raise ValueError(f"ShardedOptimizer: the checkpoint has {len(group['params'])} parameters, "
+                             f"'adamw' has {len(self.state)} spaces")
+        for k, v in self.TORCH_FLAGS.items():
+            if k in ("amsgrad", "maximize", "decoupled_weight_decay") and group.get(k, v) != v:
+                raise ValueError(f"ShardedOptimizer: 'adamw' cannot continue a checkpoint written with {k}={group[k]!r}")
+        self.param_groups[0].update({k: group[k] for k in self.DEFAULTS})
+        steps = {int(st["step"]) for st in sd["state"].values()}
+        if len(steps) > 1 or (steps and len(sd["state"]) != len(self.state)):
+            raise ValueError(f"ShardedOptimizer: 'adamw' keeps one step counter, the checkpoint has {sorted(steps)}")
+        self.steps = steps.pop() if steps else 0
+        for i, st in self.state.items():
+            for k, t in st.items():
+                if i in sd["state"]:
+                    t.copy_(sd["state"][i][k])
+                else:
+                    t.zero_()
+
+
 class ShardedOptimizer:
     """ZeRO-style (optimizer state + master weights sharded) data-parallel optimizer.
 
@@ -211,6 +272,14 @@ class ShardedOptimizer:
     cannot divide inside the reduction the shard is divided by the world size first, in its own dtype. Nothing of
     it is part of :meth:`state_dict`. One parameter group: the inner optimizer's hyper-parameters
     come from ``**opt_kwargs``.
+
+    ``optimizer_cls="adamw"`` (with ``lr``, ``betas``, ``eps``, ``weight_decay``; torch's defaults) selects the
+    built-in step instead of an inner torch optimizer: per space one ``ops.adamw_step`` reads the gradient shard, the
+    clip coefficient (with ``max_grad_norm``), ``exp_avg`` / ``exp_avg_sq`` and the master and writes the state, the
+    master and ``param_shard`` in one pass (docs/collectives.md "Fused AdamW step"). f32 / bf16 / f16 parameters and a
+    float32 master, else ``ValueError``. ``param_groups[0]`` is read at every step; ``state_dict()["inner"]`` has
+    ``torch.optim.AdamW.state_dict()``'s format, so a checkpoint of ``optimizer_cls=torch.optim.AdamW`` loads into
+    ``"adamw"`` and the reverse. Any other string raises ``ValueError``; a class behaves as it always did.
     """
 
     def __init__(self, params: Iterable[torch.nn.Parameter], optimizer_cls=torch.optim.SGD, group=None,
@@ -221,6 +290,10 @@ class ShardedOptimizer:
                  rotation_seed: int = 0, max_grad_norm: float | None = None, **opt_kwargs):
         from .compressed import ROUNDINGS, WIRES, _rotation_args
 
+        self._fused = isinstance(optimizer_cls, str)  # the built-in step, not an inner torch optimizer
+        if self._fused and optimizer_cls != "adamw":
+            raise ValueError(f"ShardedOptimizer: unknown built-in optimizer {optimizer_cls!r} (supported: 'adamw'; "
+                             "anything else is passed as a class)")
         if max_grad_norm is not None:
             if isinstance(max_grad_norm, bool) or not isinstance(max_grad_norm, (int, float)) \
                     or not 0 < max_grad_norm < float("inf"):
@@ -290,8 +363,11 @@ class ShardedOptimizer:
                     raise ValueError(f"ShardedOptimizer: with max_grad_norm the master_dtype is float32 or the "
                                      f"parameters' own ({s.dtype}), got {s.master.dtype}")
                 # the master gradient: the shard itself, scaled in place, or an f32 buffer the scaled cast fills
-                s.master_grad = s.grad_shard if s.master.dtype == s.dtype else torch.empty_like(s.master)
-        self.inner = optimizer_cls([s.master for s in self.spaces], **opt_kwargs)
+                # (the built-in step needs neither: its kernel takes the coefficient)
+                if not self._fused:
+                    s.master_grad = s.grad_shard if s.master.dtype == s.dtype else torch.empty_like(s.master)
+        self.inner = (_FusedAdamW(self.spaces, **opt_kwargs) if self._fused
+                      else optimizer_cls([s.master for s in self.spaces], **opt_kwargs))
         self._avg = self._fused_avg()
         self._op = dist.ReduceOp.AVG if self._avg else dist.ReduceOp.SUM
         self._sync = True
@@ -391,39 +467,55 @@ class ShardedOptimizer:
                 b.work.wait()
                 b.work = None
                 b.pending = len(b.idx)
-            if self.max_grad_norm is not None:  # (_clip below sets every master gradient)
-                if not self._avg and self.world > 1 and not self._on_wire(s, self.grad_wire):
+            if self.max_grad_norm is not None or self._fused:  # (_clip below sets every master gradient; the
+                if not self._avg and self.world > 1 and not self._on_wire(s, self.grad_wire):  # built-in step needs none)
                     s.grad_shard.div_(self.world)
                 continue
             g = s.grad_shard if s.master.dtype == s.dtype else s.grad_shard.to(s.master.dtype)
             if not self._avg and self.world > 1 and not self._on_wire(s, self.grad_wire):  # (a wire divides inside)
                 g = g / self.world
             s.master.grad = g
+        if self._fused:  # one kernel per space: coefficient, update and the cast into param_shard
+            total = self._sumsq_total() if self.max_grad_norm is not None else None
+            self.grad_rounding_step += 1
+            self.inner.step(self.spaces, total, self.max_grad_norm)
+            self._gather(cast=False)
+            return
         if self.max_grad_norm is not None:
             self._clip()
         self.grad_rounding_step += 1
         self.inner.step()
         self._gather()
 
-    def _clip(self) -> None:
-        """Clip by global norm (docs/collectives.md "Gradient clipping"): the f64 sum of squares of this rank's
-        shards (their padding is zeros), summed over the ranks, then per space the cast to the master dtype with
-        the coefficient on it. Everything stays on the device."""
+    def _sumsq_total(self) -> torch.Tensor:
+        """The f64 sum of squares of this rank's gradient shards (their padding is zeros), summed over the ranks: one
+        element on the device, the same bits on every rank. Sets ``grad_norm``."""
         from .. import ops
 
         total = ops.sumsq([s.grad_shard for s in self.spaces])
         self._fence(self.spaces[0])
         dist.all_reduce(total, op=dist.ReduceOp.SUM, group=self.group)
+        self.grad_norm = total[0].sqrt().to(torch.float32)
+        return total
+
+    def _clip(self) -> None:
+        """Clip by global norm (docs/collectives.md "Gradient clipping"): the total of :meth:`_sumsq_total`, then
+        per space the cast to the master dtype with the coefficient on it. Everything stays on the device."""
+        from .. import ops
+
+        total = self._sumsq_total()
         for s in self.spaces:
             ops.clip_scale(s.grad_shard, total, self.max_grad_norm, out=s.master_grad)
             s.master.grad = s.master_grad
-        self.grad_norm = total[0].sqrt().to(torch.float32)
 
     @torch.no_grad()
-    def _gather(self) -> None:
+    def _gather(self, cast: bool = True) -> None:
+        """All-gather the parameter shards; ``cast``: fill them from the masters first (the built-in step's kernel
+        has written them already)."""
         works = []
         for s in self.spaces:
-            s.param_shard.copy_(s.master)
+            if cast:
+                s.param_shard.copy_(s.master)
             for b in s.buckets:
                 if self._on_wire(s, self.param_wire):
                     from .compressed import all_gather_compressed
