@@ -409,20 +409,30 @@ void clip_scale(const at::Tensor& src, const at::Tensor& total, double max_norm,
 }
 
 // ---- fused AdamW step (kernels/adamw.hip, docs/collectives.md "Fused AdamW step"). `args`: the eight scalars of
-// kern::AdamWArgs in its order, computed by the caller in f64; each is rounded to f32 here, once.
-void adamw_step(const at::Tensor& grad, at::Tensor& master, at::Tensor& exp_avg, at::Tensor& exp_avg_sq,
-                const std::vector<double>& args, const c10::optional<at::Tensor>& param_out,
-                const c10::optional<at::Tensor>& total, double max_norm, int max_blocks) {
-  const char* who = "adamw_step";
+// kern::AdamWArgs in its order, computed by the caller in f64; each is rounded to f32 here, once. `packed`: exp_avg and
+// exp_avg_sq are the uint8 wires of "8-bit AdamW state" (kernels/adamw8.hip), the second one holding sqrt(exp_avg_sq).
+static void adamw_launch(const char* who, bool packed, const at::Tensor& grad, at::Tensor& master, at::Tensor& exp_avg,
+                         at::Tensor& exp_avg_sq, const std::vector<double>& args,
+                         const c10::optional<at::Tensor>& param_out, const c10::optional<at::Tensor>& total,
+                         double max_norm, int max_blocks) {
   TORCH_CHECK(grad.is_cuda(), who, ": GPU tensors only");
   const at::Device dev = grad.device();
   const auto gd = clip_dtype(grad, who);
   TORCH_CHECK_VALUE(args.size() == 8, who, ": eight scalars expected, got ", args.size());
-  for (const at::Tensor* t : {&master, &exp_avg, &exp_avg_sq})
+  const int64_t wire = (int64_t)pdcc::kern::mx_wire_bytes(pdcc::kern::mx_chunk_blocks((size_t)grad.numel(), 1), 1);
+  for (const at::Tensor* t : {&master, &exp_avg, &exp_avg_sq}) {
+    if (packed && t != &master) {
+      TORCH_CHECK_VALUE(t->scalar_type() == at::kByte && t->device() == dev && t->numel() == wire && t->is_contiguous() &&
+                            reinterpret_cast<uintptr_t>(t->data_ptr()) % 16 == 0,
+                        who, ": exp_avg and exp_avg_sq must be contiguous 16-byte aligned uint8 wires of ", wire,
+                        " bytes on ", dev);
+      continue;
+    }
     TORCH_CHECK_VALUE(t->scalar_type() == at::kFloat && t->device() == dev && t->numel() == grad.numel() &&
                           t->is_contiguous(),
                       who, ": master, exp_avg and exp_avg_sq must be contiguous float32 tensors of ", grad.numel(),
                       " elements on ", dev);
+  }
   TORCH_CHECK_VALUE(grad.is_contiguous(), who, ": grad must be contiguous");
   auto pd = pdcc::kern::DType::F32;
   if (param_out) {
@@ -437,11 +447,26 @@ void adamw_step(const at::Tensor& grad, at::Tensor& master, at::Tensor& exp_avg,
                                 (float)args[4], (float)args[5], (float)args[6], (float)args[7]};
   c10::hip::HIPGuardMasqueradingAsCUDA g(dev);
   hipStream_t s = c10::hip::getCurrentHIPStreamMasqueradingAsCUDA(dev.index()).stream();
-  hipError_t e = pdcc::kern::adamw_step(grad.data_ptr(), gd, master.data_ptr<float>(), exp_avg.data_ptr<float>(),
-                                        exp_avg_sq.data_ptr<float>(), param_out ? param_out->data_ptr() : nullptr, pd,
-                                        (size_t)grad.numel(), a, total ? total->data_ptr<double>() : nullptr,
-                                        (float)max_norm, s, max_blocks);
+  void* po = param_out ? param_out->data_ptr() : nullptr;
+  const double* tot = total ? total->data_ptr<double>() : nullptr;
+  hipError_t e =
+      packed ? pdcc::kern::adamw8_step(grad.data_ptr(), gd, master.data_ptr<float>(), exp_avg.data_ptr<uint8_t>(),
+                                       exp_avg_sq.data_ptr<uint8_t>(), po, pd, (size_t)grad.numel(), a, tot,
+                                       (float)max_norm, s, max_blocks)
+             : pdcc::kern::adamw_step(grad.data_ptr(), gd, master.data_ptr<float>(), exp_avg.data_ptr<float>(),
+                                      exp_avg_sq.data_ptr<float>(), po, pd, (size_t)grad.numel(), a, tot,
+                                      (float)max_norm, s, max_blocks);
   TORCH_CHECK(e == hipSuccess, who, " launch failed: ", hipGetErrorString(e));
+}
+void adamw_step(const at::Tensor& grad, at::Tensor& master, at::Tensor& exp_avg, at::Tensor& exp_avg_sq,
+                const std::vector<double>& args, const c10::optional<at::Tensor>& param_out,
+                const c10::optional<at::Tensor>& total, double max_norm, int max_blocks) {
+  adamw_launch("adamw_step", false, grad, master, exp_avg, exp_avg_sq, args, param_out, total, max_norm, max_blocks);
+}
+void adamw8_step(const at::Tensor& grad, at::Tensor& master, at::Tensor& exp_avg, at::Tensor& exp_avg_sq,
+                 const std::vector<double>& args, const c10::optional<at::Tensor>& param_out,
+                 const c10::optional<at::Tensor>& total, double max_norm, int max_blocks) {
+  adamw_launch("adamw8_step", true, grad, master, exp_avg, exp_avg_sq, args, param_out, total, max_norm, max_blocks);
 }
 
 // Peer links between every pair of visible GPUs, as the runtime reports them: HSA link
@@ -656,6 +681,11 @@ PYBIND11_MODULE(_C, m) {
         py::arg("max_blocks") = 0,
         "one fused AdamW step on f32 master / exp_avg / exp_avg_sq in place from an f32 / bf16 / f16 gradient, with the "
         "clip coefficient from the float64 total (read on the GPU) and the new master rounded once into param_out");
+  m.def("adamw8_step", &adamw8_step, py::arg("grad"), py::arg("master"), py::arg("exp_avg"), py::arg("exp_avg_sq"),
+        py::arg("args"), py::arg("param_out") = py::none(), py::arg("total") = py::none(), py::arg("max_norm") = 0.0,
+        py::arg("max_blocks") = 0,
+        "adamw_step on block-scaled 8-bit state: exp_avg and sqrt(exp_avg_sq) as uint8 mxfp8_e4m3 wires of one chunk, "
+        "dequantized, stepped and requantized in place in the same pass");
   m.attr("ADAMW_SPAN") = (int64_t)pdcc::kern::kAdamWSpan;
   m.def("ipc_signal_bytes", &pdcc::kern::ipc_signal_bytes);
   m.def("device_links", &device_links,

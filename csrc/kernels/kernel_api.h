@@ -438,6 +438,16 @@ constexpr size_t kAdamWSpan = (size_t)256 * kAdamWUnroll * 4;
 hipError_t adamw_step(const void* grad, DType gt, float* master, float* exp_avg, float* exp_avg_sq, void* param_out,
                       DType pt, size_t numel, const AdamWArgs& a, const double* total, float max_norm,
                       hipStream_t stream, int max_blocks = 0);
+// The same step on block-scaled 8-bit state (adamw8.hip; docs/collectives.md "8-bit AdamW state"). `exp_avg` holds m
+// and `exp_avg_sqrt` holds s = sqrt(v), each as the dealt `mxfp8_e4m3` wire of one chunk of `numel` elements
+// (mx_layout.h: mx_wire_bytes(mx_chunk_blocks(numel, 1), 1) bytes, 16-byte aligned, else hipErrorInvalidValue), read
+// and rewritten in place: m0 = D(exp_avg), v0 = s0 s0 with s0 = D(exp_avg_sqrt), then the sequence above with
+// s = sqrt(v) computed once; the master and `param_out` take the unquantized m and s, exp_avg <- Q(m) and
+// exp_avg_sqrt <- Q(s) by the wire's rule, except that a positive s is never stored as code 0 (its scaled value is
+// raised to 2^-9). Positions past `numel` count as +0. grad, master and param_out as above.
+hipError_t adamw8_step(const void* grad, DType gt, float* master, uint8_t* exp_avg, uint8_t* exp_avg_sqrt,
+                       void* param_out, DType pt, size_t numel, const AdamWArgs& a, const double* total,
+                       float max_norm, hipStream_t stream, int max_blocks = 0);
 
 }  // namespace kern
 }  // namespace pdcc

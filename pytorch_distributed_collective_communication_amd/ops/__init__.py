@@ -38,7 +38,9 @@
   clipping"): a deterministic f64 sum of squares of a tensor list, and the cast that multiplies by the clip
   coefficient it computes on the device from that sum; ``ShardedOptimizer(max_grad_norm=...)``.
 * :func:`adamw_step` -- one AdamW step on a shard in one pass: gradient, clip coefficient, f32 state and the
-  parameter cast (docs/collectives.md "Fused AdamW step"); ``ShardedOptimizer(params, "adamw")``.
+  parameter cast (docs/collectives.md "Fused AdamW step"); ``ShardedOptimizer(params, "adamw")``. With
+  ``state_format="mxfp8_e4m3"`` the two moments are block-scaled 8-bit buffers (:func:`adamw_state_pack`,
+  :func:`adamw_state_unpack`; docs/collectives.md "8-bit AdamW state").
 
 Every function runs on the current HIP stream and raises if the native
 extension is missing (no silent eager fallback). ``*_reference`` functions are
@@ -997,6 +999,7 @@ def clip_scale(src: torch.Tensor, total: torch.Tensor, max_norm: float, out: tor
 
 # ------------------------------------------ fused AdamW step (docs/collectives.md "Fused AdamW step")
 ADAMW_SPAN = 4096  # elements a workgroup takes per trip of its grid-stride loop (kernel_api.h kAdamWSpan)
+ADAMW_STATE_FORMATS = ("mxfp8_e4m3",)  # state_format= of adamw_step (docs/collectives.md "8-bit AdamW state")
 
 
 def _adamw_scalars(lr, betas, eps, weight_decay, step) -> tuple:
@@ -1009,11 +1012,25 @@ def _adamw_scalars(lr, betas, eps, weight_decay, step) -> tuple:
     return (b1, 1.0 - b1, b2, 1.0 - b2, 1.0 - lr * wd, lr / (1.0 - b1 ** step), 1.0 / math.sqrt(1.0 - b2 ** step), eps)
 
 
-def _adamw_check(grad, master, exp_avg, exp_avg_sq, param_out, total, max_norm, who: str) -> None:
+def _adamw_state_format(state_format, who: str) -> bool:
+    """Whether the state is packed; ``None``: the f32 state."""
+    if state_format is not None and state_format not in ADAMW_STATE_FORMATS:
+        raise ValueError(f"{who}: unknown state_format {state_format!r} (supported: None, "
+                         f"{', '.join(map(repr, ADAMW_STATE_FORMATS))})")
+    return state_format is not None
+
+
+def _adamw_check(grad, master, exp_avg, exp_avg_sq, param_out, total, max_norm, who: str, packed: bool = False) -> None:
     if not isinstance(grad, torch.Tensor) or grad.dtype not in CLIP_DTYPES:
         raise ValueError(f"{who}: grad must be a float32, bfloat16 or float16 tensor")
     for name, t in (("master", master), ("exp_avg", exp_avg), ("exp_avg_sq", exp_avg_sq)):
-        if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or t.numel() != grad.numel() \
+        if packed and name != "master":
+            nb = mx_wire_bytes(grad.numel(), 1)
+            if not isinstance(t, torch.Tensor) or t.dtype != torch.uint8 or t.numel() != nb or t.device != grad.device \
+                    or not t.is_contiguous() or t.data_ptr() % 16:
+                raise ValueError(f"{who}: with state_format {name} must be a contiguous, 16-byte aligned uint8 wire of "
+                                 f"{nb} bytes on {grad.device}")
+        elif not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or t.numel() != grad.numel() \
                 or t.device != grad.device:
             raise ValueError(f"{who}: {name} must hold {grad.numel()} float32 elements on {grad.device}")
     if param_out is not None and (param_out.dtype not in (torch.float32, grad.dtype)
@@ -1026,29 +1043,75 @@ def _adamw_check(grad, master, exp_avg, exp_avg_sq, param_out, total, max_norm, 
         float(max_norm)
 
 
+def _adamw_pack_one(x: torch.Tensor, never_zero: bool) -> torch.Tensor:
+    """n f32 elements -> their dealt ``mxfp8_e4m3`` wire of one chunk, on ``x``'s device. ``never_zero``: the rule
+    of the stored square root, a positive value's scaled product is raised to 2^-9 (the smallest e4m3 subnormal)."""
+    cb = mx_chunk_blocks(x.numel(), 1)
+    xb = torch.zeros(cb * MX_BLOCK, dtype=torch.float32, device=x.device)
+    xb[:x.numel()] = x.detach().reshape(-1)
+    xb = xb.view(cb, MX_BLOCK)
+    if not never_zero:
+        return _mx_join(*_mx_quantize_blocks(xb), 1)
+    e, special, zero = _mx_block_scale(xb, _MX_FORMATS["mxfp8_e4m3"])
+    t = xb * _mx_exp2(-e)[:, None]
+    t = torch.where((xb > 0) & (t < 2.0 ** -9), torch.full_like(t, 2.0 ** -9), t)
+    q = t.to(torch.float8_e4m3fn).view(torch.uint8).clone()
+    q[special | zero] = 0
+    return _mx_join(q, _mx_scale_bytes(e, special), 1)
+
+
+def adamw_state_pack(exp_avg: torch.Tensor, exp_avg_sq: torch.Tensor) -> tuple:
+    """The f32 moments of a shard -> the two uint8 buffers of ``state_format="mxfp8_e4m3"`` (docs/collectives.md
+    "8-bit AdamW state"): ``exp_avg`` as ``mx_quantize_reference(exp_avg, 1)`` has it, ``exp_avg_sq`` as the wire of
+    its f32 square root in which a positive root is never stored as code 0. Plain torch on any device."""
+    for t in (exp_avg, exp_avg_sq):
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or t.numel() != exp_avg.numel():
+            raise ValueError("adamw_state_pack: two float32 tensors of one size expected")
+    return _adamw_pack_one(exp_avg, False), _adamw_pack_one(exp_avg_sq.detach().sqrt(), True)
+
+
+def adamw_state_unpack(exp_avg: torch.Tensor, exp_avg_sq: torch.Tensor, numel: int) -> tuple:
+    """The two uint8 buffers of :func:`adamw_state_pack` -> ``(m, v)`` in f32, ``v = s * s`` (one rounding) from the
+    stored root ``s``. Plain torch on any device."""
+    out = []
+    for w in (exp_avg, exp_avg_sq):
+        if w.numel() != mx_wire_bytes(numel, 1):
+            raise ValueError(f"adamw_state_unpack: the state of {numel} elements has {mx_wire_bytes(numel, 1)} bytes, "
+                             f"got {w.numel()}")
+        out.append(_mx_dequantize_blocks(*_mx_split(w.detach(), 1)).reshape(-1)[:int(numel)])
+    return out[0], out[1] * out[1]
+
+
 def adamw_step_reference(grad: torch.Tensor, master: torch.Tensor, exp_avg: torch.Tensor, exp_avg_sq: torch.Tensor, *,
                          lr: float, betas, eps: float, weight_decay: float, step: int,
                          param_out: torch.Tensor | None = None, total: torch.Tensor | None = None,
-                         max_norm: float | None = None) -> None:
+                         max_norm: float | None = None, state_format: str | None = None) -> None:
     """Plain-PyTorch :func:`adamw_step`: the same sequence, one f32 operation per rounding, the scalars of the same
-    function rounded to f32 once."""
-    _adamw_check(grad, master, exp_avg, exp_avg_sq, param_out, total, max_norm, "adamw_step_reference")
+    function rounded to f32 once. With ``state_format`` the state is unpacked, stepped and packed again."""
+    packed = _adamw_state_format(state_format, "adamw_step_reference")
+    _adamw_check(grad, master, exp_avg, exp_avg_sq, param_out, total, max_norm, "adamw_step_reference", packed)
     b1, omb1, b2, omb2, decay, step_size, inv_sqrt_bc2, e = (
         torch.tensor(x, dtype=torch.float32, device=grad.device) for x in _adamw_scalars(lr, betas, eps, weight_decay, step))
     g = grad.detach().to(torch.float32).reshape(-1)
     if total is not None:
         g = g * _clip_coef(total, max_norm)
-    m = b1 * exp_avg.detach().reshape(-1) + omb1 * g
-    v = b2 * exp_avg_sq.detach().reshape(-1) + omb2 * (g * g)
+    m0, v0 = (adamw_state_unpack(exp_avg, exp_avg_sq, g.numel()) if packed
+              else (exp_avg.detach().reshape(-1), exp_avg_sq.detach().reshape(-1)))
+    m = b1 * m0 + omb1 * g
+    v = b2 * v0 + omb2 * (g * g)
     p = master.detach().reshape(-1) * decay
-    p = p - step_size * (m / (v.sqrt() * inv_sqrt_bc2 + e))
+    s = v.sqrt()
+    p = p - step_size * (m / (s * inv_sqrt_bc2 + e))
+    if packed:
+        m, v = _adamw_pack_one(m, False), _adamw_pack_one(s, True)
     for dst, src in ((exp_avg, m), (exp_avg_sq, v), (master, p)) + (() if param_out is None else ((param_out, p),)):
         dst.detach().copy_(src.view_as(dst))
 
 
 def adamw_step(grad: torch.Tensor, master: torch.Tensor, exp_avg: torch.Tensor, exp_avg_sq: torch.Tensor, *,
                lr: float, betas, eps: float, weight_decay: float, step: int, param_out: torch.Tensor | None = None,
-               total: torch.Tensor | None = None, max_norm: float | None = None, max_blocks: int = 0) -> None:
+               total: torch.Tensor | None = None, max_norm: float | None = None, max_blocks: int = 0,
+               state_format: str | None = None) -> None:
     """One AdamW step (decoupled weight decay, torch's formula) on the float32 ``master``, ``exp_avg`` and
     ``exp_avg_sq`` in place, from a float32 / bfloat16 / float16 ``grad`` read once; ``step`` counts from 1.
 
@@ -1064,23 +1127,31 @@ def adamw_step(grad: torch.Tensor, master: torch.Tensor, exp_avg: torch.Tensor, 
     coefficient of :func:`clip_scale`, evaluated on the device. ``param_out`` (float32 or ``grad``'s dtype) receives
     the new master rounded once. NaN and inf propagate as the arithmetic gives them. On the GPU this is one kernel
     and one pass (contiguous tensors, any alignment, no overlap between the five buffers; ``max_blocks`` caps the
-    grid); CPU tensors: :func:`adamw_step_reference`."""
-    _adamw_check(grad, master, exp_avg, exp_avg_sq, param_out, total, max_norm, "adamw_step")
+    grid); CPU tensors: :func:`adamw_step_reference`.
+
+    ``state_format="mxfp8_e4m3"`` (default ``None``: the f32 state above, the same kernels as ever): ``exp_avg`` and
+    ``exp_avg_sq`` are the 16-byte aligned uint8 buffers of :func:`adamw_state_pack`, ``mx_wire_bytes(numel, 1)``
+    bytes each, the second one holding ``sqrt(exp_avg_sq)``. The kernel dequantizes them (``v = s * s``), runs the
+    sequence above, gives ``master`` and ``param_out`` the unquantized ``m`` and ``sqrt(v)`` of this step, and
+    requantizes both moments in place in the same pass (docs/collectives.md "8-bit AdamW state")."""
+    packed = _adamw_state_format(state_format, "adamw_step")
+    _adamw_check(grad, master, exp_avg, exp_avg_sq, param_out, total, max_norm, "adamw_step", packed)
     if grad.device.type == "cpu":
         return adamw_step_reference(grad, master, exp_avg, exp_avg_sq, lr=lr, betas=betas, eps=eps,
                                     weight_decay=weight_decay, step=step, param_out=param_out, total=total,
-                                    max_norm=max_norm)
+                                    max_norm=max_norm, state_format=state_format)
     if not all(t.is_contiguous() for t in (grad, master, exp_avg, exp_avg_sq) + (() if param_out is None else (param_out,))):
         raise ValueError("adamw_step: the tensors must be contiguous")
-    _C().adamw_step(grad.detach(), master.detach(), exp_avg.detach(), exp_avg_sq.detach(),
-                    list(_adamw_scalars(lr, betas, eps, weight_decay, step)),
-                    None if param_out is None else param_out.detach(), None if total is None else total.detach(),
-                    0.0 if max_norm is None else float(max_norm), int(max_blocks))
+    fn = _C().adamw8_step if packed else _C().adamw_step
+    fn(grad.detach(), master.detach(), exp_avg.detach(), exp_avg_sq.detach(),
+       list(_adamw_scalars(lr, betas, eps, weight_decay, step)),
+       None if param_out is None else param_out.detach(), None if total is None else total.detach(),
+       0.0 if max_norm is None else float(max_norm), int(max_blocks))
 
 
 __all__ = ["reduce_nway", "reduce_nway_reference", "multi_copy", "pack", "unpack",
            "sumsq", "clip_scale", "sumsq_reference", "clip_scale_reference",
-           "adamw_step", "adamw_step_reference",
+           "adamw_step", "adamw_step_reference", "ADAMW_STATE_FORMATS", "adamw_state_pack", "adamw_state_unpack",
            "MX_WIRES", "MX_ROUNDINGS", "MX_ROTATIONS", "mx_sr_key", "mx_rotation_signs",
            "mx_quantize", "mx_reduce", "mx_dequantize", "mx_chunk_blocks", "mx_wire_bytes",
            "mx_owner_residual_numel",

@@ -179,14 +179,20 @@ class _FusedAdamW:
     one step counter, one parameter group read at every step, and ``ops.adamw_step`` -- one pass over the gradient
     shard, the state and the master that also writes ``param_shard`` (docs/collectives.md "Fused AdamW step").
     ``state`` / ``param_groups`` / ``state_dict()`` / ``load_state_dict()`` are those of ``torch.optim.AdamW`` over
-    the masters, one parameter per space, so checkpoints go either way."""
+    the masters, one parameter per space, so checkpoints go either way. ``state_format="mxfp8_e4m3"`` keeps the two
+    moments as the uint8 buffers of ``ops.adamw_state_pack`` (docs/collectives.md "8-bit AdamW state"); ``state_dict()``
+    unpacks them to f32 and ``load_state_dict()`` packs, so the checkpoint format stays torch's."""
 
     DEFAULTS = dict(lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2)
     # what torch.optim.AdamW writes next to them, and the only values this step implements
     TORCH_FLAGS = dict(amsgrad=False, maximize=False, foreach=None, capturable=False, differentiable=False, fused=None,
                        decoupled_weight_decay=True)
 
-    def __init__(self, spaces, **kw):
+    def __init__(self, spaces, state_format=None, **kw):
+        from .. import ops
+
+        self.packed = ops._adamw_state_format(state_format, "ShardedOptimizer")
+        self.state_format = state_format
         unknown = sorted(set(kw) - set(self.DEFAULTS))
         if unknown:
             raise ValueError(f"ShardedOptimizer: 'adamw' takes {', '.join(self.DEFAULTS)}, got {', '.join(unknown)}")
@@ -195,9 +201,18 @@ class _FusedAdamW:
                 raise ValueError(f"ShardedOptimizer: 'adamw' steps float32, bfloat16 and float16 parameters on a float32 "
                                  f"master, got {s.dtype} parameters with a {s.master.dtype} master")
         self.param_groups = [{**self.DEFAULTS, **kw}]
-        self.state = {i: {"exp_avg": torch.zeros_like(s.master), "exp_avg_sq": torch.zeros_like(s.master)}
-                      for i, s in enumerate(spaces)}
+        self.masters = [s.master for s in spaces]
+        self.state = {i: dict(zip(("exp_avg", "exp_avg_sq"), self._fresh(s.master))) for i, s in enumerate(spaces)}
         self.steps = 0
+
+    def _fresh(self, master, exp_avg=None, exp_avg_sq=None):
+        """The two moments of a space as this optimizer holds them, zeros unless given (f32, any device). The packed
+        state of zeros is not zero bytes: an all-zero block carries scale byte 127."""
+        from .. import ops
+
+        m, v = (torch.zeros_like(master) if t is None else t.to(device=master.device, dtype=torch.float32).reshape(-1)
+                for t in (exp_avg, exp_avg_sq))
+        return ops.adamw_state_pack(m, v) if self.packed else (m, v)
 
     def step(self, spaces, total, max_norm) -> None:
         from .. import ops
@@ -207,10 +222,20 @@ class _FusedAdamW:
         for i, s in enumerate(spaces):
             ops.adamw_step(s.grad_shard, s.master, self.state[i]["exp_avg"], self.state[i]["exp_avg_sq"], lr=g["lr"],
                            betas=g["betas"], eps=g["eps"], weight_decay=g["weight_decay"], step=self.steps,
-                           param_out=s.param_shard, total=total, max_norm=None if total is None else max_norm)
+                           param_out=s.param_shard, total=total, max_norm=None if total is None else max_norm,
+                           **({"state_format": self.state_format} if self.packed else {}))
+
+    def _f32_state(self, i) -> dict:
+        from .. import ops
+
+        st = self.state[i]
+        if not self.packed:
+            return st
+        return dict(zip(("exp_avg", "exp_avg_sq"),
+                        ops.adamw_state_unpack(st["exp_avg"], st["exp_avg_sq"], self.masters[i].numel())))
 
     def state_dict(self) -> dict:
-        state = {i: {"step": torch.tensor(float(self.steps)), **st} for i, st in self.state.items()} if self.steps else {}
+        state = {i: {"step": torch.tensor(float(self.steps)), **self._f32_state(i)} for i in self.state} if self.steps else {}
         return {"state": state,
                 "param_groups": [{**self.param_groups[0], **self.TORCH_FLAGS, "params": list(range(len(self.state)))}]}
 
@@ -228,11 +253,10 @@ class _FusedAdamW:
             raise ValueError(f"ShardedOptimizer: 'adamw' keeps one step counter, the checkpoint has {sorted(steps)}")
         self.steps = steps.pop() if steps else 0
         for i, st in self.state.items():
-            for k, t in st.items():
-                if i in sd["state"]:
-                    t.copy_(sd["state"][i][k])
-                else:
-                    t.zero_()
+            saved = sd["state"].get(i, {})
+            fresh = self._fresh(self.masters[i], saved.get("exp_avg"), saved.get("exp_avg_sq"))
+            for t, new in zip((st["exp_avg"], st["exp_avg_sq"]), fresh):
+                t.copy_(new.view_as(t))
 
 
 class ShardedOptimizer:
@@ -280,6 +304,12 @@ class ShardedOptimizer:
     float32 master, else ``ValueError``. ``param_groups[0]`` is read at every step; ``state_dict()["inner"]`` has
     ``torch.optim.AdamW.state_dict()``'s format, so a checkpoint of ``optimizer_cls=torch.optim.AdamW`` loads into
     ``"adamw"`` and the reverse. Any other string raises ``ValueError``; a class behaves as it always did.
+
+    ``state_format="mxfp8_e4m3"`` (with ``"adamw"`` only; default ``None``: f32 state) holds ``exp_avg`` and the square
+    root of ``exp_avg_sq`` as block-scaled 8-bit buffers, 2 x 33/32 bytes per element instead of 8, read and
+    requantized by the same one pass (docs/collectives.md "8-bit AdamW state"). ``state_dict()["inner"]`` still has
+    torch's f32 format; :meth:`sharded_state_bytes` counts the packed buffers. Any other string, or a
+    ``state_format`` next to an inner optimizer class, raises ``ValueError``.
     """
 
     def __init__(self, params: Iterable[torch.nn.Parameter], optimizer_cls=torch.optim.SGD, group=None,
@@ -287,13 +317,22 @@ class ShardedOptimizer:
                  bucket_bytes: int = 256 << 20, overlap: bool = True, grad_wire: str | None = None,
                  param_wire: str | None = None, grad_error_feedback: bool = False, grad_rounding: str = "nearest",
                  grad_seed: int = 0, grad_rotation: str | None = None, param_rotation: str | None = None,
-                 rotation_seed: int = 0, max_grad_norm: float | None = None, **opt_kwargs):
+                 rotation_seed: int = 0, max_grad_norm: float | None = None, state_format: str | None = None,
+                 **opt_kwargs):
         from .compressed import ROUNDINGS, WIRES, _rotation_args
 
         self._fused = isinstance(optimizer_cls, str)  # the built-in step, not an inner torch optimizer
         if self._fused and optimizer_cls != "adamw":
             raise ValueError(f"ShardedOptimizer: unknown built-in optimizer {optimizer_cls!r} (supported: 'adamw'; "
                              "anything else is passed as a class)")
+        if state_format is not None:
+            from .. import ops
+
+            ops._adamw_state_format(state_format, "ShardedOptimizer")
+            if not self._fused:
+                raise ValueError("ShardedOptimizer: state_format is the built-in 'adamw' step's; an inner optimizer "
+                                 "class keeps its own state")
+            opt_kwargs["state_format"] = state_format
         if max_grad_norm is not None:
             if isinstance(max_grad_norm, bool) or not isinstance(max_grad_norm, (int, float)) \
                     or not 0 < max_grad_norm < float("inf"):

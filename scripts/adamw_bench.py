@@ -5,6 +5,8 @@ rounds, medians; nothing here is a pass / fail gate).
 One process, GPU 0. At 64 MiB and 1 GiB of parameter shard, for f32 and bf16 parameters, three ways of taking a shard
 from (gradient shard, f64 total) to (new state, new master, param_shard):
   * hip:      one ops.adamw_step(grad, master, exp_avg, exp_avg_sq, total=..., param_out=param_shard);
+  * hip8:     the same call with state_format="mxfp8_e4m3": the two moments as block-scaled 8-bit buffers
+              (docs/collectives.md "8-bit AdamW state"), dequantized and requantized in the same pass;
   * foreach:  ops.clip_scale(grad, total, c, out=f32 master gradient; in place for f32) + torch.optim.AdamW(foreach=True)
               .step() on the master + param_shard.copy_(master): what ShardedOptimizer(torch.optim.AdamW,
               max_grad_norm=c) runs today;
@@ -48,6 +50,18 @@ def ways_for(mib, dtn, ops, torch, dev):
         ops.adamw_step(grad, master, m, v, step=count[0], param_out=shard, total=total, max_norm=1.0, **HP)
 
     ways["hip"] = hip
+    master8 = torch.randn(n, device=dev)
+    nb = ops.mx_wire_bytes(n, 1)  # (the state of zeros: payload 0, scale bytes 127)
+    m8, s8 = (torch.cat([torch.zeros(nb - nb // 33, dtype=torch.uint8, device=dev),
+                         torch.full((nb // 33,), 127, dtype=torch.uint8, device=dev)]) for _ in range(2))
+    count8 = [0]
+
+    def hip8():
+        count8[0] += 1
+        ops.adamw_step(grad, master8, m8, s8, step=count8[0], param_out=shard, total=total, max_norm=1.0,
+                       state_format="mxfp8_e4m3", **HP)
+
+    ways["hip8"] = hip8
     for name, kw in (("foreach", dict(foreach=True)), ("fused", dict(fused=True))):
         mw = torch.randn(n, device=dev)
         mg = grad.clone() if dt == torch.float32 else torch.empty(n, device=dev)
@@ -61,7 +75,7 @@ def ways_for(mib, dtn, ops, torch, dev):
             shard.copy_(mw)
 
         ways[name] = composed
-    return ways, n * (esize + 12 + 12 + esize)
+    return ways, n * (esize + 12 + 12 + esize), n * (esize + 4 + 4 + esize) + 4 * nb
 
 
 def main():
@@ -80,7 +94,7 @@ def main():
     rows = {}
     for mib in a.sizes:
         for dtn in ("f32", "bf16"):
-            ways, nbytes = ways_for(mib, dtn, ops, torch, dev)
+            ways, nbytes, nbytes8 = ways_for(mib, dtn, ops, torch, dev)
             raw = {k: [] for k in ways}
             iters = 20 if mib <= 64 else 5
             for _ in range(a.rounds):
@@ -90,6 +104,12 @@ def main():
                        "us_max": round(max(v), 2), "us_rounds": [round(u, 2) for u in v]} for k, v in raw.items()}
             row["bytes"] = nbytes
             row["hip_tb_per_s"] = round(nbytes / row["hip"]["us_median"] / 1e6, 3)
+            row["bytes_hip8"] = nbytes8
+            row["hip8_tb_per_s"] = round(nbytes8 / row["hip8"]["us_median"] / 1e6, 3)
+            row["time_ratio_hip8_over_hip"] = round(row["hip8"]["us_median"] / row["hip"]["us_median"], 3)
+            row["bytes_ratio_hip8_over_hip"] = round(nbytes8 / nbytes, 3)
+            row["beyond_the_spread_hip8"] = (row["hip8"]["us_max"] < row["hip"]["us_min"]
+                                             or row["hip"]["us_max"] < row["hip8"]["us_min"])
             for other in ("foreach", "fused"):
                 row[f"time_ratio_hip_over_{other}"] = round(row["hip"]["us_median"] / row[other]["us_median"], 3)
                 row[f"beyond_the_spread_{other}"] = (row["hip"]["us_max"] < row[other]["us_min"]
@@ -103,6 +123,8 @@ def main():
                 "same shapes: device-event microseconds per call (median, min, max over interleaved rounds), the hip "
                 "kernel's bytes over its median, and the ratios of the medians. One GPU; the whole ZeRO step across "
                 "GPUs is not measured",
+        "hip8": "ops.adamw_step(state_format='mxfp8_e4m3') in the same rounds: its own bytes (grad, master read and "
+                "written, two state wires read and written, param_shard), TB/s, and the ratio of its median to hip's",
         "rounds": a.rounds, "device": torch.cuda.get_device_name(0), "rows": rows,
     }
     os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
@@ -110,7 +132,8 @@ def main():
         json.dump(doc, f, indent=1, sort_keys=True)
         f.write("\n")
     print(json.dumps({k: [v["hip_tb_per_s"], v["time_ratio_hip_over_foreach"], v["time_ratio_hip_over_fused"],
-                          v["beyond_the_spread_foreach"], v["beyond_the_spread_fused"]] for k, v in rows.items()}))
+                          v["beyond_the_spread_foreach"], v["beyond_the_spread_fused"], v["hip8_tb_per_s"],
+                          v["time_ratio_hip8_over_hip"], v["beyond_the_spread_hip8"]] for k, v in rows.items()}))
 
 
 if __name__ == "__main__":
