@@ -414,12 +414,29 @@ void clip_scale(const at::Tensor& src, const at::Tensor& total, double max_norm,
 static void adamw_launch(const char* who, bool packed, const at::Tensor& grad, at::Tensor& master, at::Tensor& exp_avg,
                          at::Tensor& exp_avg_sq, const std::vector<double>& args,
                          const c10::optional<at::Tensor>& param_out, const c10::optional<at::Tensor>& total,
-                         double max_norm, int max_blocks) {
+                         double max_norm, int max_blocks, const c10::optional<at::Tensor>& wire_out,
+                         const std::string& wire_fmt, const std::string& wire_dtype,
+                         const c10::optional<int64_t>& state_offset) {
   TORCH_CHECK(grad.is_cuda(), who, ": GPU tensors only");
   const at::Device dev = grad.device();
   const auto gd = clip_dtype(grad, who);
   TORCH_CHECK_VALUE(args.size() == 8, who, ": eight scalars expected, got ", args.size());
-  const int64_t wire = (int64_t)pdcc::kern::mx_wire_bytes(pdcc::kern::mx_chunk_blocks((size_t)grad.numel(), 1), 1);
+  const int64_t n = grad.numel(), blk = pdcc::kern::kMxBlock;
+  int64_t wire = (int64_t)pdcc::kern::mx_wire_bytes(pdcc::kern::mx_chunk_blocks((size_t)n, 1), 1);
+  size_t block0 = 0, state_cb = 0;
+  if (state_offset) {  // a span of the shard whose packed state the two buffers are
+    TORCH_CHECK_VALUE(packed, who, ": state_offset comes with the packed state only");
+    wire = exp_avg.numel();
+    TORCH_CHECK_VALUE(wire > 0 && wire % (int64_t)pdcc::kern::kMxBlockWire == 0 && exp_avg_sq.numel() == wire, who,
+                      ": with state_offset exp_avg and exp_avg_sq are whole chunks of one size, got ", exp_avg.numel(),
+                      " and ", exp_avg_sq.numel(), " bytes");
+    state_cb = (size_t)(wire / (int64_t)pdcc::kern::kMxBlockWire);
+    TORCH_CHECK_VALUE(*state_offset >= 0 && *state_offset % blk == 0 && n % blk == 0 &&
+                          *state_offset + n <= blk * (int64_t)state_cb,
+                      who, ": state_offset (", *state_offset, ") and numel (", n, ") must be multiples of ", blk,
+                      " inside the state's ", blk * (int64_t)state_cb, " elements");
+    block0 = (size_t)(*state_offset / blk);
+  }
   for (const at::Tensor* t : {&master, &exp_avg, &exp_avg_sq}) {
     if (packed && t != &master) {
       TORCH_CHECK_VALUE(t->scalar_type() == at::kByte && t->device() == dev && t->numel() == wire && t->is_contiguous() &&
@@ -443,6 +460,27 @@ static void adamw_launch(const char* who, bool packed, const at::Tensor& grad, a
                       param_out->scalar_type(), " for ", grad.scalar_type());
   }
   if (total) clip_check_total(*total, dev, who, "total");
+  pdcc::kern::AdamWWire w;
+  if (wire_out) {  // the parameter wire from the same pass: the vector path or nothing
+    w.fmt = mx_format(wire_fmt, who);
+    TORCH_CHECK_VALUE(param_out || !wire_dtype.empty(), who, ": wire_out without param_out needs wire_dtype");
+    TORCH_CHECK_VALUE(wire_dtype.empty() || wire_dtype == "float32" || wire_dtype == "bfloat16" || wire_dtype == "float16",
+                      who, ": wire_dtype is 'float32', 'bfloat16' or 'float16', got '", wire_dtype, "'");
+    w.dt = wire_dtype.empty() ? pd : kdtype(wire_dtype == "float32" ? at::kFloat : wire_dtype == "bfloat16" ? at::kBFloat16 : at::kHalf);
+    TORCH_CHECK_VALUE((w.dt == pdcc::kern::DType::F32 || w.dt == gd) && (!param_out || w.dt == pd), who,
+                      ": wire_dtype must be float32 or grad's dtype, and param_out's when both are given");
+    const int64_t wb = (int64_t)pdcc::kern::mx_wire_bytes(w.fmt, pdcc::kern::mx_chunk_blocks(w.fmt, (size_t)n, 1), 1);
+    TORCH_CHECK_VALUE(wire_out->scalar_type() == at::kByte && wire_out->device() == dev && wire_out->numel() == wb &&
+                          wire_out->is_contiguous(),
+                      who, ": wire_out must be a contiguous uint8 tensor of ", wb, " bytes on ", dev);
+    const auto al = [](const at::Tensor& t, uintptr_t a) { return reinterpret_cast<uintptr_t>(t.data_ptr()) % a == 0; };
+    bool vec = al(*wire_out, 16) && al(master, 16) && al(grad, 4 * grad.element_size()) &&
+               (!param_out || al(*param_out, 4 * param_out->element_size()));
+    if (!packed) vec = vec && al(exp_avg, 16) && al(exp_avg_sq, 16);
+    TORCH_CHECK_VALUE(vec, who, ": with wire_out every float32 side and wire_out must be 16-byte aligned and every "
+                      "16-bit side 8-byte aligned");
+    w.out = n ? wire_out->data_ptr() : nullptr;
+  }
   const pdcc::kern::AdamWArgs a{(float)args[0], (float)args[1], (float)args[2], (float)args[3],
                                 (float)args[4], (float)args[5], (float)args[6], (float)args[7]};
   c10::hip::HIPGuardMasqueradingAsCUDA g(dev);
@@ -452,21 +490,27 @@ static void adamw_launch(const char* who, bool packed, const at::Tensor& grad, a
   hipError_t e =
       packed ? pdcc::kern::adamw8_step(grad.data_ptr(), gd, master.data_ptr<float>(), exp_avg.data_ptr<uint8_t>(),
                                        exp_avg_sq.data_ptr<uint8_t>(), po, pd, (size_t)grad.numel(), a, tot,
-                                       (float)max_norm, s, max_blocks)
+                                       (float)max_norm, s, max_blocks, w, block0, state_cb)
              : pdcc::kern::adamw_step(grad.data_ptr(), gd, master.data_ptr<float>(), exp_avg.data_ptr<float>(),
                                       exp_avg_sq.data_ptr<float>(), po, pd, (size_t)grad.numel(), a, tot,
-                                      (float)max_norm, s, max_blocks);
+                                      (float)max_norm, s, max_blocks, w);
   TORCH_CHECK(e == hipSuccess, who, " launch failed: ", hipGetErrorString(e));
 }
 void adamw_step(const at::Tensor& grad, at::Tensor& master, at::Tensor& exp_avg, at::Tensor& exp_avg_sq,
                 const std::vector<double>& args, const c10::optional<at::Tensor>& param_out,
-                const c10::optional<at::Tensor>& total, double max_norm, int max_blocks) {
-  adamw_launch("adamw_step", false, grad, master, exp_avg, exp_avg_sq, args, param_out, total, max_norm, max_blocks);
+                const c10::optional<at::Tensor>& total, double max_norm, int max_blocks,
+                const c10::optional<at::Tensor>& wire_out, const std::string& wire,
+                const std::string& wire_dtype) {
+  adamw_launch("adamw_step", false, grad, master, exp_avg, exp_avg_sq, args, param_out, total, max_norm, max_blocks,
+               wire_out, wire, wire_dtype, c10::nullopt);
 }
 void adamw8_step(const at::Tensor& grad, at::Tensor& master, at::Tensor& exp_avg, at::Tensor& exp_avg_sq,
                  const std::vector<double>& args, const c10::optional<at::Tensor>& param_out,
-                 const c10::optional<at::Tensor>& total, double max_norm, int max_blocks) {
-  adamw_launch("adamw8_step", true, grad, master, exp_avg, exp_avg_sq, args, param_out, total, max_norm, max_blocks);
+                 const c10::optional<at::Tensor>& total, double max_norm, int max_blocks,
+                 const c10::optional<at::Tensor>& wire_out, const std::string& wire,
+                 const std::string& wire_dtype, const c10::optional<int64_t>& state_offset) {
+  adamw_launch("adamw8_step", true, grad, master, exp_avg, exp_avg_sq, args, param_out, total, max_norm, max_blocks,
+               wire_out, wire, wire_dtype, state_offset);
 }
 
 // Peer links between every pair of visible GPUs, as the runtime reports them: HSA link
@@ -678,14 +722,18 @@ PYBIND11_MODULE(_C, m) {
   m.attr("SUMSQ_CHAIN") = pdcc::kern::kSumsqChain;
   m.def("adamw_step", &adamw_step, py::arg("grad"), py::arg("master"), py::arg("exp_avg"), py::arg("exp_avg_sq"),
         py::arg("args"), py::arg("param_out") = py::none(), py::arg("total") = py::none(), py::arg("max_norm") = 0.0,
-        py::arg("max_blocks") = 0,
+        py::arg("max_blocks") = 0, py::arg("wire_out") = py::none(), py::arg("wire") = "mxfp8_e4m3",
+        py::arg("wire_dtype") = "",
         "one fused AdamW step on f32 master / exp_avg / exp_avg_sq in place from an f32 / bf16 / f16 gradient, with the "
-        "clip coefficient from the float64 total (read on the GPU) and the new master rounded once into param_out");
+        "clip coefficient from the float64 total (read on the GPU) and the new master rounded once into param_out; "
+        "wire_out: the one-chunk wire (format `wire`) of the new master rounded to wire_dtype, from the same pass");
   m.def("adamw8_step", &adamw8_step, py::arg("grad"), py::arg("master"), py::arg("exp_avg"), py::arg("exp_avg_sq"),
         py::arg("args"), py::arg("param_out") = py::none(), py::arg("total") = py::none(), py::arg("max_norm") = 0.0,
-        py::arg("max_blocks") = 0,
+        py::arg("max_blocks") = 0, py::arg("wire_out") = py::none(), py::arg("wire") = "mxfp8_e4m3",
+        py::arg("wire_dtype") = "", py::arg("state_offset") = py::none(),
         "adamw_step on block-scaled 8-bit state: exp_avg and sqrt(exp_avg_sq) as uint8 mxfp8_e4m3 wires of one chunk, "
-        "dequantized, stepped and requantized in place in the same pass");
+        "dequantized, stepped and requantized in place in the same pass; state_offset: the tensors are the span of the "
+        "state's shard that starts at that element");
   m.attr("ADAMW_SPAN") = (int64_t)pdcc::kern::kAdamWSpan;
   m.def("ipc_signal_bytes", &pdcc::kern::ipc_signal_bytes);
   m.def("device_links", &device_links,

@@ -32,6 +32,7 @@
 
 #include "group_io.h"
 #include "mx_block.h"
+#include "mx_fmt.h"
 #include "mx_layout.h"
 
 #ifndef PDCC_ADAMW_NT_STATE
@@ -53,19 +54,32 @@ static_assert(kLanes == 8 && 256 % kLanes == 0, "a block is eight adjacent lanes
 // the scale of a block of e4m3 codes (largest magnitude 448 = 1.75 2^8; mx_wire.hip MxFmt<FP8_E4M3>::scale)
 __device__ __forceinline__ MxScale scale8(uint32_t amax) { return mx_scale_of<8, 0x600000u, -117, 120>(amax); }
 
-// GD: the gradient's dtype. PD: param_out's; HASP = false: no param_out (PD unused). exp_avg / exp_avg_sqrt: the wires
-template <DType GD, DType PD, bool HASP, bool VEC>
+// GD: the gradient's dtype. PD: the parameter dtype, param_out's; HASP = false: no param_out (PD unused). exp_avg /
+// exp_avg_sqrt: the state wires, chunks of cb blocks; the tensors hold the span that starts at block `block0` of them
+// (0, with cb = mx_chunk_blocks(numel, 1): the whole shard), so the span's payload starts at byte 32 block0 and its
+// scale bytes at 32 cb + block0.
+// WF: kNoWire, or the MxFormat of the parameter wire the same pass emits, as in k_adamw (adamw.hip): the loop then
+// runs over the 8 cbw groups of that wire (cbw >= the span's blocks, and no relation to cb), the groups past the span's
+// blocks touch nothing of the state and emit zeros. Vector path only; param_out is stored when given.
+template <DType GD, DType PD, bool HASP, bool VEC, int WF = kNoWire>
 __global__ __launch_bounds__(256) void k_adamw8(const char* grad, char* master, char* exp_avg, char* exp_avg_sqrt,
-                                                char* param_out, size_t numel, size_t cb, const kern::AdamWArgs a,
-                                                const double* __restrict__ total, float max_norm) {
+                                                char* param_out, size_t numel, size_t cb, size_t block0,
+                                                const kern::AdamWArgs a, const double* __restrict__ total,
+                                                float max_norm, char* wire, size_t cbw) {
 #pragma clang fp contract(off)
   using G = typename Tr<GD>::S;
   using P = typename Tr<PD>::S;
   constexpr DType F = DType::F32;
+  constexpr bool WIRE = WF != kNoWire;
+  static_assert(!WIRE || (VEC && HASP), "the wire variants: vector path, PD always meaningful");
+  const bool sp = HASP && (!WIRE || param_out != nullptr);
   const float coef = total ? clip_coef(total, max_norm) : 1.0f;
   const size_t ngroups = kern::mx_blocks(numel) * kLanes;  // whole blocks
-  const size_t scales = kern::mx_scale_off(cb, 0);
-  for (size_t g0 = (size_t)blockIdx.x * (256 * kU); g0 < ngroups; g0 += (size_t)gridDim.x * (256 * kU)) {
+  const size_t nloop = WIRE ? cbw * kLanes : ngroups;
+  const size_t scales = kern::mx_scale_off(cb, block0) - kern::mx_payload_off(block0);  // from the span's payload
+  exp_avg += kern::mx_payload_off(block0);
+  exp_avg_sqrt += kern::mx_payload_off(block0);
+  for (size_t g0 = (size_t)blockIdx.x * (256 * kU); g0 < nloop; g0 += (size_t)gridDim.x * (256 * kU)) {
     float g[kU][kE], p[kU][kE];
     uint32_t qm[kU], qs[kU], em[kU], es[kU];
 #pragma unroll
@@ -124,10 +138,22 @@ __global__ __launch_bounds__(256) void k_adamw8(const char* grad, char* master, 
         }
         if (VEC && i + kE <= numel) {
           store_group<F, kE, kNtMaster>(master + i * 4, p[u]);
-          if constexpr (HASP) store_group<PD, kE>(param_out + i * sizeof(P), p[u]);
+          if constexpr (HASP) {
+            if (sp) store_group<PD, kE>(param_out + i * sizeof(P), p[u]);
+          }
         } else {
           store_elems<F, kE>(master, i, numel, p[u]);
-          if constexpr (HASP) store_elems<PD, kE>(param_out, i, numel, p[u]);
+          if constexpr (HASP) {
+            if (sp) store_elems<PD, kE>(param_out, i, numel, p[u]);
+          }
+        }
+      }
+      if constexpr (WIRE) {
+        if (gi < nloop) {  // (the same for a whole wave: 8 cbw is a multiple of 128)
+          float r[kE];
+#pragma unroll
+          for (int j = 0; j < kE; ++j) r[j] = i + j < numel ? round_as<PD>(p[u][j]) : 0.0f;
+          mx_emit4<(kern::MxFormat)WF>(wire, cbw, gi, r);
         }
       }
     }
@@ -141,22 +167,32 @@ struct Launch {
   float* master;
   uint8_t *exp_avg, *exp_avg_sqrt;
   void* param_out;
-  size_t numel, cb;
+  size_t numel, cb, block0;
   const kern::AdamWArgs* a;
   const double* total;
   float max_norm;
   int grid;
   hipStream_t stream;
+  void* wire;
+  size_t cbw;
 };
+
+template <DType GD, DType PD>
+bool adamw8_vec(const Launch& l, bool hasp) {
+  return aligned(l.grad, kE * sizeof(typename Tr<GD>::S)) && aligned(l.master, 16) &&
+         (!hasp || aligned(l.param_out, kE * sizeof(typename Tr<PD>::S)));
+}
+template <class K>
+hipError_t adamw8_launch(K k, const Launch& l) {
+  hipLaunchKernelGGL(k, dim3(l.grid), dim3(256), 0, l.stream, (const char*)l.grad, (char*)l.master, (char*)l.exp_avg,
+                     (char*)l.exp_avg_sqrt, (char*)l.param_out, l.numel, l.cb, l.block0, *l.a, l.total, l.max_norm,
+                     (char*)l.wire, l.cbw);
+  return hipGetLastError();
+}
 
 template <DType GD, DType PD, bool HASP>
 hipError_t adamw8_go(const Launch& l) {
-  const bool vec = aligned(l.grad, kE * sizeof(typename Tr<GD>::S)) && aligned(l.master, 16) &&
-                   (!HASP || aligned(l.param_out, kE * sizeof(typename Tr<PD>::S)));
-  auto k = vec ? k_adamw8<GD, PD, HASP, true> : k_adamw8<GD, PD, HASP, false>;
-  hipLaunchKernelGGL(k, dim3(l.grid), dim3(256), 0, l.stream, (const char*)l.grad, (char*)l.master, (char*)l.exp_avg,
-                     (char*)l.exp_avg_sqrt, (char*)l.param_out, l.numel, l.cb, *l.a, l.total, l.max_norm);
-  return hipGetLastError();
+  return adamw8_launch(adamw8_vec<GD, PD>(l, HASP) ? k_adamw8<GD, PD, HASP, true> : k_adamw8<GD, PD, HASP, false>, l);
 }
 
 template <DType GD>
@@ -164,6 +200,24 @@ hipError_t adamw8_pick(const Launch& l, DType pt) {
   if (!l.param_out) return adamw8_go<GD, DType::F32, false>(l);
   if (pt == DType::F32) return adamw8_go<GD, DType::F32, true>(l);
   return adamw8_go<GD, GD, true>(l);
+}
+
+// the wire variants: the vector path or nothing
+template <DType GD, DType PD>
+hipError_t adamw8_wire_go(const Launch& l, kern::MxFormat f) {
+  if (!adamw8_vec<GD, PD>(l, l.param_out != nullptr) || !aligned(l.wire, 16)) return hipErrorInvalidValue;
+  switch (f) {
+    case kern::MxFormat::FP8_E4M3: return adamw8_launch(k_adamw8<GD, PD, true, true, (int)kern::MxFormat::FP8_E4M3>, l);
+    case kern::MxFormat::FP4_E2M1: return adamw8_launch(k_adamw8<GD, PD, true, true, (int)kern::MxFormat::FP4_E2M1>, l);
+    default: return adamw8_launch(k_adamw8<GD, PD, true, true, (int)kern::MxFormat::FP6_E2M3>, l);
+  }
+}
+template <DType GD>
+hipError_t adamw8_wire_pick(const Launch& l, const kern::AdamWWire& w) {
+  if constexpr (GD != DType::F32) {
+    if (w.dt == GD) return adamw8_wire_go<GD, GD>(l, w.fmt);
+  }
+  return adamw8_wire_go<GD, DType::F32>(l, w.fmt);
 }
 
 }  // namespace
@@ -175,17 +229,28 @@ constexpr int kAdamW8Grid = 4096;  // as k_adamw's
 
 hipError_t adamw8_step(const void* grad, DType gt, float* master, uint8_t* exp_avg, uint8_t* exp_avg_sqrt,
                        void* param_out, DType pt, size_t numel, const AdamWArgs& a, const double* total,
-                       float max_norm, hipStream_t stream, int max_blocks) {
+                       float max_norm, hipStream_t stream, int max_blocks, const AdamWWire& wire, size_t block0,
+                       size_t state_cb) {
   if (gt != DType::F32 && gt != DType::BF16 && gt != DType::F16) return hipErrorInvalidValue;
   if (param_out && pt != DType::F32 && pt != gt) return hipErrorInvalidValue;
+  if (wire.out && ((wire.dt != DType::F32 && wire.dt != gt) || (param_out && pt != wire.dt))) return hipErrorInvalidValue;
+  if (state_cb ? (numel % kMxBlock != 0 || block0 + numel / kMxBlock > state_cb) : block0 != 0) return hipErrorInvalidValue;
   if (numel == 0) return hipSuccess;
   if (!grad || !master || !exp_avg || !exp_avg_sqrt) return hipErrorInvalidValue;
   if (!dev::aligned(exp_avg, 16) || !dev::aligned(exp_avg_sqrt, 16)) return hipErrorInvalidValue;
   const size_t cap = max_blocks > 0 ? (size_t)max_blocks : (size_t)kAdamW8Grid;
-  const size_t covered = mx_blocks(numel) * kMxBlock;  // whole blocks
+  const size_t cbw = wire.out ? mx_chunk_blocks(wire.fmt, numel, 1) : 0;
+  const size_t covered = (wire.out ? cbw : mx_blocks(numel)) * kMxBlock;  // whole blocks; the wire's blank tail too
   const int grid = (int)std::min<size_t>((covered + kAdamWSpan - 1) / kAdamWSpan, cap);
-  const dev::Launch l{grad, master, exp_avg, exp_avg_sqrt, param_out, numel, mx_chunk_blocks(numel, 1), &a, total,
-                      max_norm, grid, stream};
+  const dev::Launch l{grad, master, exp_avg, exp_avg_sqrt, param_out, numel, state_cb ? state_cb : mx_chunk_blocks(numel, 1),
+                      block0, &a, total, max_norm, grid, stream, wire.out, cbw};
+  if (wire.out) {
+    switch (gt) {
+      case DType::F32: return dev::adamw8_wire_pick<DType::F32>(l, wire);
+      case DType::BF16: return dev::adamw8_wire_pick<DType::BF16>(l, wire);
+      default: return dev::adamw8_wire_pick<DType::F16>(l, wire);
+    }
+  }
   switch (gt) {
     case DType::F32: return dev::adamw8_pick<DType::F32>(l, pt);
     case DType::BF16: return dev::adamw8_pick<DType::BF16>(l, pt);

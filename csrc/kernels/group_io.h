@@ -21,6 +21,13 @@ __device__ __forceinline__ uint32_t narrow_bits(float f) {
   else return __builtin_bit_cast(uint16_t, (_Float16)f);
 }
 
+// f rounded once to DT and widened again: the value a store of DT leaves behind
+template <DType DT>
+__device__ __forceinline__ float round_as(float f) {
+  if constexpr (DT == DType::F32) return f;
+  else return widen_bits<DT>(narrow_bits<DT>(f));
+}
+
 // N elements of DT from N * sizeof(element) bytes (8 or 16, so aligned); NT: non-temporal (read once)
 template <DType DT, int N, bool NT = true>
 __device__ __forceinline__ void load_group(const char* p, float* f) {

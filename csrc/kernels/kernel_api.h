@@ -435,19 +435,36 @@ constexpr size_t kAdamWSpan = (size_t)256 * kAdamWUnroll * 4;
 // clip_scale's, read on the device. `gt`: F32, BF16 or F16. Any alignment of the element size on every side (all
 // sides vector-aligned: 16-byte f32 and 8-byte 16-bit accesses; otherwise element by element, the same bits).
 // The five buffers do not overlap. `max_blocks` caps the grid (0: default).
+//
+// `wire.out` (docs/collectives.md "Parameter wire from the step"): the same pass also writes the one-chunk wire of
+// the new master rounded once to `wire.dt` (F32 or `gt`; with `param_out`, `pt`), byte for byte what mx_quantize of
+// those values writes: mx_wire_bytes(wire.fmt, cb, 1) bytes with cb = mx_chunk_blocks(wire.fmt, numel, 1), the blocks
+// past the data blank (payload 0, scale byte 127). Then every side must be vector-aligned and wire.out 16-byte
+// aligned, else hipErrorInvalidValue; `param_out` may be null.
+struct AdamWWire {
+  void* out = nullptr;
+  MxFormat fmt = MxFormat::FP8_E4M3;
+  DType dt = DType::F32;
+};
 hipError_t adamw_step(const void* grad, DType gt, float* master, float* exp_avg, float* exp_avg_sq, void* param_out,
                       DType pt, size_t numel, const AdamWArgs& a, const double* total, float max_norm,
-                      hipStream_t stream, int max_blocks = 0);
+                      hipStream_t stream, int max_blocks = 0, const AdamWWire& wire = {});
 // The same step on block-scaled 8-bit state (adamw8.hip; docs/collectives.md "8-bit AdamW state"). `exp_avg` holds m
 // and `exp_avg_sqrt` holds s = sqrt(v), each as the dealt `mxfp8_e4m3` wire of one chunk of `numel` elements
 // (mx_layout.h: mx_wire_bytes(mx_chunk_blocks(numel, 1), 1) bytes, 16-byte aligned, else hipErrorInvalidValue), read
 // and rewritten in place: m0 = D(exp_avg), v0 = s0 s0 with s0 = D(exp_avg_sqrt), then the sequence above with
 // s = sqrt(v) computed once; the master and `param_out` take the unquantized m and s, exp_avg <- Q(m) and
 // exp_avg_sqrt <- Q(s) by the wire's rule, except that a positive s is never stored as code 0 (its scaled value is
-// raised to 2^-9). Positions past `numel` count as +0. grad, master and param_out as above.
+// raised to 2^-9). Positions past `numel` count as +0. grad, master, param_out and `wire` as above.
+//
+// A span (`state_cb` > 0): grad, master, param_out and the wire hold elements [32 block0, 32 block0 + numel) of the
+// shard whose state the two buffers are, chunks of `state_cb` blocks each (mx_wire_bytes(state_cb, 1) bytes); numel
+// is a multiple of 32 and block0 + numel / 32 <= state_cb, else hipErrorInvalidValue. The span's payload starts at
+// byte 32 block0 and its scale bytes at 32 state_cb + block0; nothing else of the state is touched.
 hipError_t adamw8_step(const void* grad, DType gt, float* master, uint8_t* exp_avg, uint8_t* exp_avg_sqrt,
                        void* param_out, DType pt, size_t numel, const AdamWArgs& a, const double* total,
-                       float max_norm, hipStream_t stream, int max_blocks = 0);
+                       float max_norm, hipStream_t stream, int max_blocks = 0, const AdamWWire& wire = {},
+                       size_t block0 = 0, size_t state_cb = 0);
 
 }  // namespace kern
 }  // namespace pdcc

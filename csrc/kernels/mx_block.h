@@ -39,7 +39,7 @@ struct MxScale {
 };
 // amax = m 2^k, 1 <= m < 2 (k = -127 for a subnormal: the clamp decides). With the format's largest
 // magnitude (1 + SWITCH 2^-23) 2^BIAS, the smallest e with amax 2^-e <= that is k - BIAS for a mantissa
-// field <= SWITCH and one more above; e is clamped to [EMIN, EMAX] (the four constants: MxFmt in mx_wire.hip).
+// field <= SWITCH and one more above; e is clamped to [EMIN, EMAX] (the four constants: MxFmt in mx_fmt.h).
 template <int BIAS, uint32_t SWITCH, int EMIN, int EMAX>
 __device__ __forceinline__ MxScale mx_scale_of(uint32_t amax) {
   int e = (int)(amax >> 23) - 127 - BIAS + ((amax & 0x7fffffu) > SWITCH ? 1 : 0);

@@ -1020,12 +1020,40 @@ def _adamw_state_format(state_format, who: str) -> bool:
     return state_format is not None
 
 
-def _adamw_check(grad, master, exp_avg, exp_avg_sq, param_out, total, max_norm, who: str, packed: bool = False) -> None:
+def _adamw_check_wire(grad, param_out, wire_out, wire, wire_dtype, who: str):
+    """The parameter-wire keywords of :func:`adamw_step`; returns the dtype the master is rounded to, ``None`` without
+    ``wire_out`` (``wire`` is then ignored)."""
+    if wire_out is None:
+        return None
+    _mx_format(wire, who)
+    nb = mx_wire_bytes(grad.numel(), 1, wire=wire)
+    if not isinstance(wire_out, torch.Tensor) or wire_out.dtype != torch.uint8 or wire_out.numel() != nb \
+            or wire_out.device != grad.device or not wire_out.is_contiguous() or wire_out.data_ptr() % 16:
+        raise ValueError(f"{who}: wire_out must be a contiguous, 16-byte aligned uint8 tensor of {nb} bytes on {grad.device}")
+    if wire_dtype is None and param_out is None:
+        raise ValueError(f"{who}: wire_out without param_out needs wire_dtype")
+    dt = param_out.dtype if wire_dtype is None else wire_dtype
+    if dt not in (torch.float32, grad.dtype) or (param_out is not None and param_out.dtype != dt):
+        raise ValueError(f"{who}: wire_dtype must be float32 or {grad.dtype}, and param_out's dtype when both are given, "
+                         f"got {wire_dtype}")
+    return dt
+
+
+def _adamw_check(grad, master, exp_avg, exp_avg_sq, param_out, total, max_norm, who: str, packed: bool = False,
+                 state_offset=None) -> None:
     if not isinstance(grad, torch.Tensor) or grad.dtype not in CLIP_DTYPES:
         raise ValueError(f"{who}: grad must be a float32, bfloat16 or float16 tensor")
+    if state_offset is not None:
+        if not packed:
+            raise ValueError(f"{who}: state_offset comes with state_format only")
+        nb = exp_avg.numel() if isinstance(exp_avg, torch.Tensor) else 0
+        if isinstance(state_offset, bool) or not isinstance(state_offset, int) or state_offset < 0 or state_offset % MX_BLOCK \
+                or grad.numel() % MX_BLOCK or nb % (MX_BLOCK + 1) or state_offset + grad.numel() > nb // (MX_BLOCK + 1) * MX_BLOCK:
+            raise ValueError(f"{who}: state_offset ({state_offset!r}) and numel ({grad.numel()}) must be multiples of "
+                             f"{MX_BLOCK} inside the state's {nb // (MX_BLOCK + 1) * MX_BLOCK} elements")
     for name, t in (("master", master), ("exp_avg", exp_avg), ("exp_avg_sq", exp_avg_sq)):
         if packed and name != "master":
-            nb = mx_wire_bytes(grad.numel(), 1)
+            nb = mx_wire_bytes(grad.numel(), 1) if state_offset is None else exp_avg.numel()
             if not isinstance(t, torch.Tensor) or t.dtype != torch.uint8 or t.numel() != nb or t.device != grad.device \
                     or not t.is_contiguous() or t.data_ptr() % 16:
                 raise ValueError(f"{who}: with state_format {name} must be a contiguous, 16-byte aligned uint8 wire of "
@@ -1085,18 +1113,29 @@ def adamw_state_unpack(exp_avg: torch.Tensor, exp_avg_sq: torch.Tensor, numel: i
 def adamw_step_reference(grad: torch.Tensor, master: torch.Tensor, exp_avg: torch.Tensor, exp_avg_sq: torch.Tensor, *,
                          lr: float, betas, eps: float, weight_decay: float, step: int,
                          param_out: torch.Tensor | None = None, total: torch.Tensor | None = None,
-                         max_norm: float | None = None, state_format: str | None = None) -> None:
+                         max_norm: float | None = None, state_format: str | None = None,
+                         wire_out: torch.Tensor | None = None, wire: str = "mxfp8_e4m3",
+                         wire_dtype: torch.dtype | None = None, state_offset: int | None = None) -> None:
     """Plain-PyTorch :func:`adamw_step`: the same sequence, one f32 operation per rounding, the scalars of the same
-    function rounded to f32 once. With ``state_format`` the state is unpacked, stepped and packed again."""
-    packed = _adamw_state_format(state_format, "adamw_step_reference")
-    _adamw_check(grad, master, exp_avg, exp_avg_sq, param_out, total, max_norm, "adamw_step_reference", packed)
+    function rounded to f32 once. With ``state_format`` the state is unpacked, stepped and packed again (with
+    ``state_offset``: the span's blocks of it). ``wire_out`` receives
+    ``mx_quantize_reference(p.to(wire_dtype), 1, wire=wire)`` of the new master ``p``."""
+    who = "adamw_step_reference"
+    packed = _adamw_state_format(state_format, who)
+    _adamw_check(grad, master, exp_avg, exp_avg_sq, param_out, total, max_norm, who, packed, state_offset)
+    wire_dtype = _adamw_check_wire(grad, param_out, wire_out, wire, wire_dtype, who)
     b1, omb1, b2, omb2, decay, step_size, inv_sqrt_bc2, e = (
         torch.tensor(x, dtype=torch.float32, device=grad.device) for x in _adamw_scalars(lr, betas, eps, weight_decay, step))
     g = grad.detach().to(torch.float32).reshape(-1)
     if total is not None:
         g = g * _clip_coef(total, max_norm)
-    m0, v0 = (adamw_state_unpack(exp_avg, exp_avg_sq, g.numel()) if packed
-              else (exp_avg.detach().reshape(-1), exp_avg_sq.detach().reshape(-1)))
+    if state_offset is not None:  # the span's payload rows and scale bytes inside the two buffers
+        spans = [_adamw_span(t, state_offset, g.numel()) for t in (exp_avg, exp_avg_sq)]
+        m0, s0 = (_mx_dequantize_blocks(q, s).reshape(-1) for q, s in spans)
+        v0 = s0 * s0
+    else:
+        m0, v0 = (adamw_state_unpack(exp_avg, exp_avg_sq, g.numel()) if packed
+                  else (exp_avg.detach().reshape(-1), exp_avg_sq.detach().reshape(-1)))
     m = b1 * m0 + omb1 * g
     v = b2 * v0 + omb2 * (g * g)
     p = master.detach().reshape(-1) * decay
@@ -1104,14 +1143,31 @@ def adamw_step_reference(grad: torch.Tensor, master: torch.Tensor, exp_avg: torc
     p = p - step_size * (m / (s * inv_sqrt_bc2 + e))
     if packed:
         m, v = _adamw_pack_one(m, False), _adamw_pack_one(s, True)
+    if state_offset is not None:
+        for (q, sc), new in zip(spans, (m, v)):
+            nq, ns = _mx_split(new, 1)
+            q.copy_(nq[:q.shape[0]]), sc.copy_(ns[:q.shape[0]])
+        m = v = None
     for dst, src in ((exp_avg, m), (exp_avg_sq, v), (master, p)) + (() if param_out is None else ((param_out, p),)):
-        dst.detach().copy_(src.view_as(dst))
+        if src is not None:
+            dst.detach().copy_(src.view_as(dst))
+    if wire_out is not None:
+        wire_out.detach().copy_(mx_quantize_reference(p.to(wire_dtype), 1, wire=wire))
+
+
+def _adamw_span(buf: torch.Tensor, state_offset: int, numel: int) -> tuple:
+    """Views of the payload rows ``[blocks, 32]`` and the scale bytes of the span ``[state_offset, state_offset +
+    numel)`` inside a packed state buffer of ``buf.numel() / 33`` blocks."""
+    cb, b0, nb = buf.numel() // (MX_BLOCK + 1), state_offset // MX_BLOCK, numel // MX_BLOCK
+    flat = buf.detach().view(-1)
+    return flat[MX_BLOCK * b0:MX_BLOCK * (b0 + nb)].view(nb, MX_BLOCK), flat[MX_BLOCK * cb + b0:MX_BLOCK * cb + b0 + nb]
 
 
 def adamw_step(grad: torch.Tensor, master: torch.Tensor, exp_avg: torch.Tensor, exp_avg_sq: torch.Tensor, *,
                lr: float, betas, eps: float, weight_decay: float, step: int, param_out: torch.Tensor | None = None,
                total: torch.Tensor | None = None, max_norm: float | None = None, max_blocks: int = 0,
-               state_format: str | None = None) -> None:
+               state_format: str | None = None, wire_out: torch.Tensor | None = None, wire: str = "mxfp8_e4m3",
+               wire_dtype: torch.dtype | None = None, state_offset: int | None = None) -> None:
     """One AdamW step (decoupled weight decay, torch's formula) on the float32 ``master``, ``exp_avg`` and
     ``exp_avg_sq`` in place, from a float32 / bfloat16 / float16 ``grad`` read once; ``step`` counts from 1.
 
@@ -1133,20 +1189,38 @@ def adamw_step(grad: torch.Tensor, master: torch.Tensor, exp_avg: torch.Tensor, 
     ``exp_avg_sq`` are the 16-byte aligned uint8 buffers of :func:`adamw_state_pack`, ``mx_wire_bytes(numel, 1)``
     bytes each, the second one holding ``sqrt(exp_avg_sq)``. The kernel dequantizes them (``v = s * s``), runs the
     sequence above, gives ``master`` and ``param_out`` the unquantized ``m`` and ``sqrt(v)`` of this step, and
-    requantizes both moments in place in the same pass (docs/collectives.md "8-bit AdamW state")."""
+    requantizes both moments in place in the same pass (docs/collectives.md "8-bit AdamW state").
+
+    ``wire_out`` (default ``None``; docs/collectives.md "Parameter wire from the step"): a contiguous, 16-byte aligned
+    uint8 tensor of ``mx_wire_bytes(numel, 1, wire=wire)`` bytes that the same kernel fills with the wire of the new
+    master rounded once to ``wire_dtype`` -- byte for byte ``mx_quantize(p.to(wire_dtype), 1, wire=wire)``, blank tail
+    blocks included -- so the parameter all-gather needs no quantizer. ``wire`` is any of ``MX_WIRES`` and ignored
+    without ``wire_out``. ``wire_dtype`` is float32 or ``grad``'s dtype; it defaults to ``param_out.dtype``, is
+    required when ``param_out`` is ``None`` and must agree with it when both are given. On the GPU every f32 side
+    must then be 16-byte and every 16-bit side 8-byte aligned (``ValueError`` otherwise); ``numel`` is arbitrary.
+
+    ``state_offset`` (with ``state_format`` only): ``grad``, ``master``, ``param_out`` and ``wire_out`` hold the
+    elements ``[state_offset, state_offset + numel)`` of the shard whose packed state ``exp_avg`` / ``exp_avg_sq``
+    are; the state buffers are then whole chunks of ``cb = bytes / 33`` blocks, ``state_offset`` and ``numel`` are
+    multiples of 32 and ``state_offset + numel <= 32 cb``. Only the span's payload and scale bytes are touched."""
     packed = _adamw_state_format(state_format, "adamw_step")
-    _adamw_check(grad, master, exp_avg, exp_avg_sq, param_out, total, max_norm, "adamw_step", packed)
+    _adamw_check(grad, master, exp_avg, exp_avg_sq, param_out, total, max_norm, "adamw_step", packed, state_offset)
+    wire_dtype = _adamw_check_wire(grad, param_out, wire_out, wire, wire_dtype, "adamw_step")
     if grad.device.type == "cpu":
         return adamw_step_reference(grad, master, exp_avg, exp_avg_sq, lr=lr, betas=betas, eps=eps,
                                     weight_decay=weight_decay, step=step, param_out=param_out, total=total,
-                                    max_norm=max_norm, state_format=state_format)
+                                    max_norm=max_norm, state_format=state_format, wire_out=wire_out, wire=wire,
+                                    wire_dtype=wire_dtype, state_offset=state_offset)
     if not all(t.is_contiguous() for t in (grad, master, exp_avg, exp_avg_sq) + (() if param_out is None else (param_out,))):
         raise ValueError("adamw_step: the tensors must be contiguous")
     fn = _C().adamw8_step if packed else _C().adamw_step
+    new = () if wire_out is None and state_offset is None else (
+        (None if wire_out is None else wire_out.detach(), wire, "" if wire_dtype is None else str(wire_dtype)[6:])
+        + ((state_offset,) if packed else ()))
     fn(grad.detach(), master.detach(), exp_avg.detach(), exp_avg_sq.detach(),
        list(_adamw_scalars(lr, betas, eps, weight_decay, step)),
        None if param_out is None else param_out.detach(), None if total is None else total.detach(),
-       0.0 if max_norm is None else float(max_norm), int(max_blocks))
+       0.0 if max_norm is None else float(max_norm), int(max_blocks), *new)
 
 
 __all__ = ["reduce_nway", "reduce_nway_reference", "multi_copy", "pack", "unpack",

@@ -351,7 +351,7 @@ def reduce_scatter_compressed(output: torch.Tensor, input: torch.Tensor, op=dist
 
 def all_gather_compressed(output: torch.Tensor, input: torch.Tensor, group=None, wire: str = "mxfp8_e4m3",
                           async_op: bool = False, *, rounding: str = "nearest", seed: int = 0,
-                          rotation: str | None = None, rotation_seed: int = 0):
+                          rotation: str | None = None, rotation_seed: int = 0, input_wire: torch.Tensor | None = None):
     """All-gather of ``input`` (``m`` elements; f32, bf16 or f16) into ``output`` (``W * m`` elements)
     over the wire format ``wire``: every rank ends with the same bits, the dequantized wire of every
     rank's shard -- its own slot included. At world 1 ``input`` is copied bit for bit. Streams and
@@ -363,12 +363,25 @@ def all_gather_compressed(output: torch.Tensor, input: torch.Tensor, group=None,
     from it and pay twice the worst-case error.
 
     ``rotation="hadamard"`` with ``rotation_seed`` (the same on every rank): this rank's blocks are rotated
-    before they are quantized and every gathered shard is rotated back."""
+    before they are quantized and every gathered shard is rotated back.
+
+    ``input_wire`` (default ``None``): this rank's shard already quantized -- a uint8 tensor on ``input``'s device
+    with the bytes of ``ops.mx_quantize(input, 1, wire=wire)``, as ``ops.adamw_step(wire_out=...)`` writes them. The
+    call then skips its quantizer and gathers ``input_wire``; at world > 1 on the GPU ``input`` is only checked
+    (numel, dtype, device), not read. Not together with ``rounding="stochastic"`` or ``rotation``."""
     who = "all_gather_compressed"
     world = _check_pair(who, output, input, wire, group, output, input)
     sr, _ = _rounding_args(who, rounding, seed, group)
     rot = _rotation_args(who, rotation, rotation_seed)
     m = input.numel()
+    if input_wire is not None:
+        if sr or rot:
+            raise ValueError(f"{who}: input_wire holds nearest-rounded, unrotated bytes: not with rounding='stochastic' "
+                             "or rotation")
+        nb = ops.mx_wire_bytes(m, 1, wire=wire)
+        if not isinstance(input_wire, torch.Tensor) or input_wire.dtype != torch.uint8 or input_wire.numel() != nb \
+                or input_wire.device != input.device or not input_wire.is_contiguous():
+            raise ValueError(f"{who}: input_wire must be a contiguous uint8 tensor of {nb} bytes on {input.device}")
     if m == 0:
         return _done(async_op)
     if world == 1:
@@ -377,16 +390,16 @@ def all_gather_compressed(output: torch.Tensor, input: torch.Tensor, group=None,
         return _done(async_op)
     if not input.is_cuda:
         with torch.no_grad():
-            mine = ops.mx_quantize_reference(input, 1, wire=wire, **sr, **rot)
+            mine = ops.mx_quantize_reference(input, 1, wire=wire, **sr, **rot) if input_wire is None else input_wire.view(-1)
             every = torch.empty(mine.numel() * world, dtype=torch.uint8)
             dist.all_gather_into_tensor(every, mine, group=group)
             output.copy_(ops.mx_dequantize_shards_reference(every, m, output.dtype, world, wire=wire, **rot).view_as(output))
         return _done(async_op)
 
     def run():
-        mine = ops.mx_quantize(input, 1, wire=wire, **sr, **rot)
+        mine = ops.mx_quantize(input, 1, wire=wire, **sr, **rot) if input_wire is None else input_wire.view(-1)
         every = torch.empty(mine.numel() * world, dtype=torch.uint8, device=mine.device)
         dist.all_gather_into_tensor(every, mine, group=group)
         ops.mx_dequantize_shards(every, m, output.dtype, world, out=output, wire=wire, **rot)
 
-    return _issue_gpu(run, (output, input), async_op)
+    return _issue_gpu(run, (output, input) if input_wire is None else (output, input, input_wire), async_op)

@@ -214,16 +214,27 @@ class _FusedAdamW:
                 for t in (exp_avg, exp_avg_sq))
         return ops.adamw_state_pack(m, v) if self.packed else (m, v)
 
-    def step(self, spaces, total, max_norm) -> None:
+    def step(self, spaces, total, max_norm, param_wire=None) -> None:
+        """One step of every space. A space with ``param_wires`` (one buffer per bucket; ShardedOptimizer's
+        ``fused_param_wire``) is stepped bucket by bucket, each launch writing the bucket's ``param_wire`` wire instead
+        of ``param_shard`` (docs/collectives.md "Parameter wire from the step")."""
         from .. import ops
 
         g = self.param_groups[0]
         self.steps += 1
+        kw = dict(lr=g["lr"], betas=g["betas"], eps=g["eps"], weight_decay=g["weight_decay"], step=self.steps,
+                  total=total, max_norm=None if total is None else max_norm)
         for i, s in enumerate(spaces):
-            ops.adamw_step(s.grad_shard, s.master, self.state[i]["exp_avg"], self.state[i]["exp_avg_sq"], lr=g["lr"],
-                           betas=g["betas"], eps=g["eps"], weight_decay=g["weight_decay"], step=self.steps,
-                           param_out=s.param_shard, total=total, max_norm=None if total is None else max_norm,
-                           **({"state_format": self.state_format} if self.packed else {}))
+            m, v = self.state[i]["exp_avg"], self.state[i]["exp_avg_sq"]
+            if s.param_wires is None:
+                ops.adamw_step(s.grad_shard, s.master, m, v, param_out=s.param_shard, **kw,
+                               **({"state_format": self.state_format} if self.packed else {}))
+                continue
+            for b, w in zip(s.buckets, s.param_wires):
+                sl = slice(b.soff, b.soff + b.shard)
+                state = (dict(state_format=self.state_format, state_offset=b.soff) if self.packed else {})
+                ops.adamw_step(s.grad_shard[sl], s.master[sl], *((m, v) if self.packed else (m[sl], v[sl])), wire_out=w,
+                               wire=param_wire, wire_dtype=s.dtype, **kw, **state)
 
     def _f32_state(self, i) -> dict:
         from .. import ops
@@ -304,6 +315,12 @@ class ShardedOptimizer:
     float32 master, else ``ValueError``. ``param_groups[0]`` is read at every step; ``state_dict()["inner"]`` has
     ``torch.optim.AdamW.state_dict()``'s format, so a checkpoint of ``optimizer_cls=torch.optim.AdamW`` loads into
     ``"adamw"`` and the reverse. Any other string raises ``ValueError``; a class behaves as it always did.
+
+    With ``"adamw"`` and a ``param_wire``, on the GPU at world > 1 and without ``param_rotation``, the step emits the
+    parameter wire itself (read-only ``fused_param_wire``; docs/collectives.md "Parameter wire from the step"): one
+    ``ops.adamw_step(wire_out=...)`` per bucket writes the bucket's wire, which the all-gather sends as it is, instead
+    of ``param_shard`` and a quantizer that reads it back. ``param_shard`` is not maintained in this mode (it holds
+    what the last checkpoint load left there); ``flat`` and the masters are exactly what the unfused sequence gives.
 
     ``state_format="mxfp8_e4m3"`` (with ``"adamw"`` only; default ``None``: f32 state) holds ``exp_avg`` and the square
     root of ``exp_avg_sq`` as block-scaled 8-bit buffers, 2 x 33/32 bytes per element instead of 8, read and
@@ -405,6 +422,16 @@ class ShardedOptimizer:
                 # (the built-in step needs neither: its kernel takes the coefficient)
                 if not self._fused:
                     s.master_grad = s.grad_shard if s.master.dtype == s.dtype else torch.empty_like(s.master)
+        # the built-in step writes the parameter wire itself where the gather would only quantize param_shard again:
+        # per bucket one wire buffer, allocated once (None: the space keeps param_shard and today's path)
+        for s in self.spaces:
+            s.param_wires = None
+            if self._fused and self.world > 1 and param_rotation is None and self._on_wire(s, param_wire) \
+                    and s.device.type == "cuda":
+                from .. import ops
+
+                s.param_wires = [torch.empty(ops.mx_wire_bytes(b.shard, 1, wire=param_wire), dtype=torch.uint8,
+                                             device=s.device) for b in s.buckets]
         self.inner = (_FusedAdamW(self.spaces, **opt_kwargs) if self._fused
                       else optimizer_cls([s.master for s in self.spaces], **opt_kwargs))
         self._avg = self._fused_avg()
@@ -426,6 +453,11 @@ class ShardedOptimizer:
     @property
     def param_groups(self):
         return self.inner.param_groups
+
+    @property
+    def fused_param_wire(self) -> bool:
+        """Whether the built-in step emits the parameter wire itself (class docstring, ``param_wire``)."""
+        return any(s.param_wires is not None for s in self.spaces)
 
     @contextlib.contextmanager
     def no_sync(self):
@@ -517,7 +549,7 @@ class ShardedOptimizer:
         if self._fused:  # one kernel per space: coefficient, update and the cast into param_shard
             total = self._sumsq_total() if self.max_grad_norm is not None else None
             self.grad_rounding_step += 1
-            self.inner.step(self.spaces, total, self.max_grad_norm)
+            self.inner.step(self.spaces, total, self.max_grad_norm, self.param_wire)
             self._gather(cast=False)
             return
         if self.max_grad_norm is not None:
@@ -550,18 +582,19 @@ class ShardedOptimizer:
     @torch.no_grad()
     def _gather(self, cast: bool = True) -> None:
         """All-gather the parameter shards; ``cast``: fill them from the masters first (the built-in step's kernel
-        has written them already)."""
+        has written them already, or with ``fused_param_wire`` the buckets' wires, which are gathered as they are)."""
         works = []
         for s in self.spaces:
             if cast:
                 s.param_shard.copy_(s.master)
-            for b in s.buckets:
+            for bi, b in enumerate(s.buckets):
                 if self._on_wire(s, self.param_wire):
                     from .compressed import all_gather_compressed
 
+                    ready = {} if cast or s.param_wires is None else {"input_wire": s.param_wires[bi]}
                     works.append(all_gather_compressed(s.flat[b.off:b.off + b.padded],
                                                        s.param_shard[b.soff:b.soff + b.shard], group=self.group,
-                                                       wire=self.param_wire, async_op=True, **self._param_rot))
+                                                       wire=self.param_wire, async_op=True, **self._param_rot, **ready))
                     continue
                 self._fence(s)
                 works.append(dist.all_gather_into_tensor(s.flat[b.off:b.off + b.padded],

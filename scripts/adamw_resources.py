@@ -19,7 +19,8 @@ import tempfile
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 from mx6_resources import DT, FIELDS, ROOT  # noqa: E402
 
-KERNEL = re.compile(r"k_adamw8?ILNS\w+?5DTypeE(\d)ELS\w+?_(\d)ELb(\d)ELb(\d)EE")
+# (the instantiations without a parameter wire, WF = -1; the others: scripts/adamw_wire_resources.py)
+KERNEL = re.compile(r"k_adamw8?ILNS\w+?5DTypeE(\d)ELS\w+?_(\d)ELb(\d)ELb(\d)ELin1EE")
 
 
 def resources(hipcc, name):
